@@ -21,7 +21,14 @@ real-time caller's view instead: one call per block and a host wait for that blo
 before the next call. The convolver's default streaming form is the level pipeline
 (upols_levels.hip): every step runs the block step (window r2c, FDL insert, the 8 newest
 partitions, c2r) plus 1/T of the next window of each partition level, so every step does
-the same work and the line is the same at any --steps. `roofline` holds the step kernel with
+the same work and the line is the same at any --steps.
+
+A plain run sets up, warms up, times the --steps steps and prints the headline line (value,
+ms_per_step, config); `--dump-outputs DIR` also writes the output blocks of the last timed step
+(DIR/y.npy, [channels][B] float32; workload c2: a seeded sample of the transforms, DIR/y.npy and
+its row numbers DIR/rows.npy). The input is a cyclic stream of fixed seed and the warm-up ends at
+the start of a cycle, so the same arguments give the same step the same input history in every run.
+Everything below is measured only with `--full`, after the headline. `roofline` holds the step kernel with
 its HIP-event time, algorithmic bytes by role and PMC traffic. `latency` is the per-step GPU
 time distribution plus the host round trip, `parity` the last timed blocks against the
 oracle, `per_block_step` the plain one-pass-per-block step, `offline` the batched form
@@ -29,9 +36,10 @@ oracle, `per_block_step` the plain one-pass-per-block step, `offline` the batche
 host memory, PCIe-inclusive, one synchronous call per block), all timed in the same run;
 `c2_fft` the 4096 x 65536 batched FFT.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5full|c5|c4|c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c5full|c5|c4|c3|c2] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
-        --master-port P bench.py --gpus N --steps K --warmup W
+        --master-port P bench.py --gpus N --steps K --warmup W [--full]
 """
 from __future__ import annotations
 
@@ -50,6 +58,11 @@ PEAK_FP32_TFLOPS = 157.3  # MI355X fp32 vector (packed FMA) peak, 256 CU x 4 SIM
 # the first ~20 ms of sustained HBM load measurably slower (clock ramp; measured 0.93 vs
 # 0.74 ms for the 4096 x 65536 FFT), which a few warm-up steps do not cover.
 WARM_SECONDS = 0.25
+# The cyclic input's length in blocks is a multiple of this: the far window (128 blocks, a
+# multiple of every level window and step group) times every far window group K <= 4 (12), so a
+# step at the same place of the cycle is also at the same place of every level's schedule.
+CYCLE_BLOCKS = 1536
+DUMP_LIMIT_BYTES = 60 << 20  # --dump-outputs writes at most this much in all
 
 WORKLOADS = {
     # name: (channels, block, taps); c5full's 2048 are split over the ranks (strong scaling),
@@ -82,6 +95,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=128)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="c5full", choices=sorted(WORKLOADS) + ["c2"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else the line can carry (roofline, "
+                         "per-kernel times, latency, parity, the plain / offline / host-buffer forms, c2_fft, CPU "
+                         "baseline); the --no-* options below pick among those")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ahead", action="store_true", help="headline = the plain one-pass-per-block step")
     ap.add_argument("--no-offline", action="store_true", help="skip the batched (blocks up front) line")
@@ -323,6 +342,41 @@ class Feed:
             self.g += k
             n -= k
 
+    def align(self):
+        """Steps up to the start of the next input cycle: the steps after it see the same input
+        history (and, stepped from block 0 on, the same level windows) in every run."""
+        if self.g % self.nx:
+            self.run(self.nx - self.g % self.nx)
+
+    def last_output(self):
+        """A copy of the output block [C][B] of the last step run."""
+        i = (self.g - 1) % self.nx
+        return self.y[:, i * self.B:(i + 1) * self.B].clone()
+
+
+def sample_rows(rows: int, row_bytes: int, limit: int):
+    """All `rows` row numbers if they fit `limit` bytes, else a fixed (seeded) sorted sample that does."""
+    import numpy as np
+
+    keep = max(1, limit // row_bytes)
+    if rows <= keep:
+        return np.arange(rows)
+    return np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+
+
+def dump_outputs(directory: str, y) -> None:
+    """--dump-outputs: the float32 device tensor y [rows][...] as DIR/y.npy, DUMP_LIMIT_BYTES in
+    all; a larger one as a seeded sample of its rows, their numbers in DIR/rows.npy (float64)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    rows = sample_rows(y.shape[0], 4 * y[0].numel() + 8, DUMP_LIMIT_BYTES)
+    if len(rows) < y.shape[0]:
+        y = y[torch.from_numpy(rows).to(y.device)]
+        np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(directory, "y.npy"), np.ascontiguousarray(y.cpu().numpy(), dtype=np.float32))
+
 
 def far_group(nseg: int, units: int) -> int:
     """Windows per far phase-1 pass, as upols_levels.hip far_group: round(sqrt(2 (nseg - 1)))
@@ -433,7 +487,7 @@ def rank_channels(workload: str, world: int, rank: int, strong: bool = None):
     return C, C * world
 
 
-def host_io_times(conv, C, B, nblocks, kind, seed=0):
+def host_io_times(conv, C, B, nblocks, kind, seed=0, last=None):
     """One synchronous neo_hip_upols_process call per block on a host buffer [C][B] (the
     plugin's processFrame pattern, DenseConvolution.cpp:62-74): kind "pageable" (numpy, the
     handle's mapped staging) or "pinned" (page-locked torch tensor, read and written in place
@@ -459,6 +513,8 @@ def host_io_times(conv, C, B, nblocks, kind, seed=0):
         t0 = time.perf_counter()
         conv(buf)
         dt.append(time.perf_counter() - t0)
+    if last is not None:
+        last["y"] = arr.copy()  # the last call's output [C][B]
     return dt
 
 
@@ -540,10 +596,12 @@ def run_upols(args, world, rank, local):
     plan = neo.convolution.level_plan(P)
     g = torch.Generator(device=dev).manual_seed(8 + rank)
     ir = torch.rand((C, L), generator=g, device=dev).mul_(2).sub_(1)  # synthetic white-noise IR
-    irh = ir.cpu().numpy() if (rank == 0 and not args.no_parity) else None
+    full = args.full
+    irh = ir.cpu().numpy() if (full and rank == 0 and not args.no_parity) else None
     conv.set_impulse(ir, normalize=True)
     del ir
-    nx = P + 192  # cyclic input: covers the parity check's history window (P + 5 blocks)
+    # cyclic input: covers the parity check's history window (P + 5 blocks), whole CYCLE_BLOCKS
+    nx = -(-(P + 192) // CYCLE_BLOCKS) * CYCLE_BLOCKS
     x = torch.rand((C, nx * B), generator=g, device=dev).mul_(2).sub_(1)
     y = torch.empty_like(x)
     # a stream of its own (not the null stream): the steps and the events around them
@@ -559,6 +617,8 @@ def run_upols(args, world, rank, local):
         while time.perf_counter() - t_warm < WARM_SECONDS:  # untimed
             feed.run(64)
             torch.cuda.synchronize()
+        feed.align()  # and at the start of an input cycle: the timed steps' inputs are the same in every run
+        torch.cuda.synchronize()
         # end the warm-up on a step-group boundary: a timed region then starts with its group's
         # background launch, as every group does in steady state (starting k calls into a group,
         # the region would open with k blocks and no background work beside them, then still
@@ -570,10 +630,12 @@ def run_upols(args, world, rank, local):
 
     gpu_ms = {}
 
+    last = {}  # the headline region's last output block (--dump-outputs)
+
     def timed_region(tag):
         """args.steps single-block steps, nothing else in the timed region (wall clock); then
-        the same number of steps again with HIP events on the launch stream around them: the
-        GPU time per step (gpu_ms[tag]) and the host's enqueue time."""
+        (--full) the same number of steps again with HIP events on the launch stream around
+        them: the GPU time per step (gpu_ms[tag]) and the host's enqueue time."""
         mark = os.environ.get("NEO_BENCH_MARK") == "1"  # diagnostic: marker kernels around the region in traces
         if mark:
             torch.zeros(1, device=dev).add_(1)
@@ -586,6 +648,11 @@ def run_upols(args, world, rank, local):
         t1 = time.perf_counter()
         if mark:
             torch.zeros(1, device=dev).mul_(3)
+        if tag == "levels" and args.dump_outputs and rank == 0:
+            last["y"] = feed.last_output()
+        gpu_ms[tag + "_per_rank_ms"] = [v * 1e3 / args.steps for v in gather_over_ranks(t1 - t0, world)]
+        if not full:
+            return max_over_ranks(t1 - t0, world)
         if os.environ.get("NEO_BENCH_NO_CHECK") != "1":  # role-masked diagnostic builds compute garbage
             assert torch.isfinite(y).all().item()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -599,7 +666,6 @@ def run_upols(args, world, rank, local):
         torch.cuda.synchronize()
         gpu_ms[tag] = max_over_ranks(e0.elapsed_time(e1) / args.steps, world)
         gpu_ms[tag + "_host_launch_ms"] = (t3 - t2) * 1e3
-        gpu_ms[tag + "_per_rank_ms"] = [v * 1e3 / args.steps for v in gather_over_ranks(t1 - t0, world)]
         return max_over_ranks(t1 - t0, world)
 
     def wall_region(n):
@@ -624,21 +690,59 @@ def run_upols(args, world, rank, local):
         return [max_over_ranks(d, world) if d is not None else None for d in det]
 
     samples = C_total * B * args.steps  # all ranks
-    # the plain single-block step: one pass over filter + FDL per block (k_upols_step)
-    conv.set_ahead(False)
-    warm()
-    el_plain = timed_region("plain")
-    det_plain = instrumented()
-    bytes_plain = C * (16 * P * B + 20 * B)  # filter + FDL stream (packed bins) + FDL row write + in/prev
-    gbs_plain = bytes_plain / (det_plain[0] * 1e-3) / 1e9
-    plain = {"value": samples / el_plain / 1e6, "ms_per_step": el_plain * 1e3 / args.steps,
-             "kernel": f"k_upols_step<{B}>", "kernel_avg_ms": det_plain[0], "algorithmic_bytes_per_launch": bytes_plain,
-             "achieved_gbs": gbs_plain, "frac": gbs_plain / PEAK_HBM_GBS,
-             "traffic": load_pmc_traffic(_pmc_sfx(pmc_workload(args.workload, C), "_plain"), "k_upols_step")}
-    if levels:
-        conv.set_ahead(True)
+    if full:
+        # the plain single-block step: one pass over filter + FDL per block (k_upols_step)
+        conv.set_ahead(False)
+        warm()
+        el_plain = timed_region("plain")
+        det_plain = instrumented()
+        bytes_plain = C * (16 * P * B + 20 * B)  # filter + FDL stream (packed bins) + FDL row write + in/prev
+        gbs_plain = bytes_plain / (det_plain[0] * 1e-3) / 1e9
+        plain = {"value": samples / el_plain / 1e6, "ms_per_step": el_plain * 1e3 / args.steps,
+                 "kernel": f"k_upols_step<{B}>", "kernel_avg_ms": det_plain[0],
+                 "algorithmic_bytes_per_launch": bytes_plain, "achieved_gbs": gbs_plain, "frac": gbs_plain / PEAK_HBM_GBS,
+                 "traffic": load_pmc_traffic(_pmc_sfx(pmc_workload(args.workload, C), "_plain"), "k_upols_step")}
+        if levels:
+            feed.align()  # the levels start over at the next step: at a cycle's start, as in a plain run
+            torch.cuda.synchronize()
+            conv.set_ahead(True)
+    elif not levels and conv.ahead_info()[0]:
+        conv.set_ahead(False)  # --no-ahead
     warm()
     elapsed = timed_region("levels")
+    if last:
+        dump_outputs(args.dump_outputs, last["y"])
+    hl = ("levels" if levels else "plain") if full else "levels"  # the region whose event times the line reports
+    res = {
+        "metric": "Msamples/sec UPOLS convolver (block=512, IR=10s@48k); achieved HBM GB/s",
+        "value": samples / elapsed / 1e6,
+        "unit": "Msamples/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed * 1e3 / args.steps,
+        "gpu_ms_per_step": gpu_ms.get(hl),  # --full: HIP events around the same steps
+        "host_launch_ms": gpu_ms.get(hl + "_host_launch_ms"),  # --full: t0 -> all steps enqueued
+        "per_rank_ms": gpu_ms.get(hl + "_per_rank_ms"),  # each rank's wall ms per step
+        "higher_is_better": True,
+        "scaling": "strong" if args.workload in STRONG else "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (U[-1,1) white-noise input and IR, torch.rand on device)",
+        "config": {"workload": f"UPOLS {args.workload}: {C_total} channels in all, {C} on rank 0 of {world} GPU(s) "
+                               f"({'split over the ranks' if args.workload in STRONG else 'per GPU'}), B={B}, "
+                               f"L={L} taps (P={P}), one block per step",
+                   "channels_per_gpu": C, "channels_total": C_total, "shard_of": SHARD_OF, "block": B, "taps": L,
+                   "partitions": P, "far_group": conv_far_group, "step_group": G,
+                   "far_form": {0: "none", 1: "transform, stored spectra", 2: "transform recomputed every window",
+                                3: "128-block Toeplitz"}[conv_far_form],
+                   "streaming": ("levels: block step p<%d, Toeplitz %s, far %d segments" %
+                                 (plan["a0"], list(zip(plan["T"], plan["a"], plan["b"])), plan["nseg"])
+                                 if levels else "plain step"),
+                   "parallelism": f"channel-shard x{world} (no collective)"},
+    }
+    if not full:
+        return res
     parity = None
     if irh is not None:
         irn = None
@@ -882,33 +986,7 @@ def run_upols(args, world, rank, local):
         conv.close()
         del conv
         weak = run_weak(args, world, rank, local, B, L)
-    res = {
-        "metric": "Msamples/sec UPOLS convolver (block=512, IR=10s@48k); achieved HBM GB/s",
-        "value": samples / elapsed / 1e6,
-        "unit": "Msamples/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed * 1e3 / args.steps,
-        "gpu_ms_per_step": gpu_ms.get("levels" if levels else "plain"),  # HIP events around the same steps
-        "host_launch_ms": gpu_ms.get(("levels" if levels else "plain") + "_host_launch_ms"),  # t0 -> all steps enqueued
-        "per_rank_ms": gpu_ms.get(("levels" if levels else "plain") + "_per_rank_ms"),  # each rank's wall ms per step
-        "higher_is_better": True,
-        "scaling": "strong" if args.workload in STRONG else "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (U[-1,1) white-noise input and IR, torch.rand on device)",
-        "config": {"workload": f"UPOLS {args.workload}: {C_total} channels in all, {C} on rank 0 of {world} GPU(s) "
-                               f"({'split over the ranks' if args.workload in STRONG else 'per GPU'}), B={B}, "
-                               f"L={L} taps (P={P}), one block per step",
-                   "channels_per_gpu": C, "channels_total": C_total, "shard_of": SHARD_OF, "block": B, "taps": L, "partitions": P,
-                   "far_group": conv_far_group, "step_group": G,
-                   "far_form": {0: "none", 1: "transform, stored spectra", 2: "transform recomputed every window",
-                                3: "128-block Toeplitz"}[conv_far_form],
-                   "streaming": ("levels: block step p<%d, Toeplitz %s, far %d segments" %
-                                 (plan["a0"], list(zip(plan["T"], plan["a"], plan["b"])), plan["nseg"])
-                                 if levels else "plain step"),
-                   "parallelism": f"channel-shard x{world} (no collective)"},
+    res.update({
         "roofline": roof,
         "steady": steady,
         "ir_change": ir_change,
@@ -918,7 +996,7 @@ def run_upols(args, world, rank, local):
         "per_block_step": plain,
         "offline": offline,
         "host_io": host_io,
-    }
+    })
     if weak is not None:
         res["weak"] = weak
     if args.workload == "c3":
@@ -1080,7 +1158,10 @@ def run_upols_host_io(args, world, rank, local):
         dt = host_io_times(conv, C, B, args.steps, kind, seed=rank)
         barrier(world)
         out[kind] = host_io_summary(dt, C, B)
-    el = max_over_ranks(sum(host_io_times(conv, C, B, args.steps, "pinned", seed=rank)), world)
+    last = {} if args.dump_outputs and rank == 0 else None
+    el = max_over_ranks(sum(host_io_times(conv, C, B, args.steps, "pinned", seed=rank, last=last)), world)
+    if last:  # every call's input is the same block: from P + 1 calls on, so is its output
+        dump_outputs(args.dump_outputs, torch.from_numpy(last["y"]))
     return {"metric": "Msamples/sec UPOLS convolver, host buffers (PCIe-inclusive, not the headline)",
             "value": C_total * B * args.steps / el / 1e6, "unit": "Msamples/s", "n_gpus": world,
             "steps": args.steps, "ms_per_step": el * 1e3 / args.steps, "host_io": out,
@@ -1124,9 +1205,9 @@ def run_fft(args, world, rank, local):
     kms = e0.elapsed_time(e1) / args.steps
     elapsed = max_over_ranks(t1 - t0, world)
     kms = max_over_ranks(kms, world)
-    bytes_launch = 16 * N * batch
-    achieved = bytes_launch / (kms * 1e-3) / 1e9
-    return {
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, torch.view_as_real(y).reshape(batch, 2 * N))
+    res = {
         "metric": "Msamples/sec batched c2c FFT 4096 x 65536 (complex points per transform)",
         "value": world * N * batch * args.steps / elapsed / 1e6,
         "unit": "Msamples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1134,11 +1215,15 @@ def run_fft(args, world, rank, local):
         "vs_baseline": None, "dtype": "f32", "data": "synthetic (U[-1,1) complex, torch.rand on device)",
         "config": {"workload": "C2 batched c2c FFT, N=4096, batch 65536 per GPU, out of place",
                    "parallelism": f"batch-shard x{world}"},
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                     "frac": achieved / PEAK_HBM_GBS, "traffic": load_pmc_traffic("c2"),
-                     "kernel": "k_c2c_lds<4096,-1>", "kernel_avg_ms": kms, "algorithmic_bytes_per_launch": bytes_launch,
-                     "d2d_copy_gbs": copy_ceiling_gbs(dev)},
     }
+    if args.full:
+        bytes_launch = 16 * N * batch
+        achieved = bytes_launch / (kms * 1e-3) / 1e9
+        res["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                           "frac": achieved / PEAK_HBM_GBS, "traffic": load_pmc_traffic("c2"),
+                           "kernel": "k_c2c_lds<4096,-1>", "kernel_avg_ms": kms,
+                           "algorithmic_bytes_per_launch": bytes_launch, "d2d_copy_gbs": copy_ceiling_gbs(dev)}
+    return res
 
 
 def main():
@@ -1155,14 +1240,14 @@ def main():
         args.no_cpu_baseline = True
     else:
         res = run_upols(args, world, rank, local)
-        if not args.no_fft:
+        if args.full and not args.no_fft:
             import argparse as _ap
 
-            f = run_fft(_ap.Namespace(steps=20, warmup=5), world, rank, local)
+            f = run_fft(_ap.Namespace(steps=20, warmup=5, full=True, dump_outputs=None), world, rank, local)
             res["c2_fft"] = {"value": f["value"], "unit": f["unit"], "ms_per_step": f["ms_per_step"],
                              "metric": f["metric"], "roofline": f["roofline"]}
     if rank == 0:
-        if not args.no_cpu_baseline:  # rank 0, after every timed region (N > 1 too: the other ranks wait)
+        if args.full and not args.no_cpu_baseline:  # rank 0, after every timed region (N > 1 too: the other ranks wait)
             C, B, L = WORKLOADS.get(args.workload, (0, 0, 0))
             res["cpu_baseline"] = (cpu_baseline_fft(args.cpu_threads) if args.workload == "c2"
                                    else cpu_baseline_upols(C, B, L, args.cpu_threads))

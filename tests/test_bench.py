@@ -92,3 +92,56 @@ def test_pmc_summary_follows_rank_shape():
     assert bench.pmc_workload("c2", 0) == "c2"
     assert bench.load_pmc_traffic(None) is None
     assert bench._pmc_sfx(None, "_plain") is None and bench._pmc_sfx("c5", "_plain") == "c5_plain"
+
+
+def test_plain_and_full_options(monkeypatch):
+    """--full and --dump-outputs exist and are off by default; --steps sets the timed steps"""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d"
+
+
+def test_feed_aligns_to_the_input_cycle():
+    """the warm-up ends at the start of an input cycle, whatever number of steps it took: the timed
+    steps then read the same blocks after the same history; the cycle holds whole far windows of
+    every window group"""
+    class Conv:
+        def process_blocks_ptr(self, *a):
+            pass
+
+    class Buf:
+        def data_ptr(self):
+            return 0
+
+    assert bench.CYCLE_BLOCKS % (128 * 12) == 0
+    for first in (0, 1, 999, 1536, 4000):
+        f = bench.Feed(Conv(), Buf(), Buf(), 1536, 512, 0)
+        f.run(first)
+        f.align()
+        assert f.g % 1536 == 0 and f.g >= first and f.g - first < 1536
+
+
+def test_dump_outputs_sample_and_format(tmp_path):
+    """--dump-outputs: float32 .npy; an output above the size limit as a fixed sample of its rows"""
+    np = pytest.importorskip("numpy")
+    torch = pytest.importorskip("torch")
+    y = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), y)
+    got = np.load(tmp_path / "a" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.numpy()) and not (tmp_path / "a" / "rows.npy").exists()
+    rows = bench.sample_rows(65536, 32776, bench.DUMP_LIMIT_BYTES)
+    assert len(rows) * 32776 <= bench.DUMP_LIMIT_BYTES <= 64 << 20 and len(set(rows.tolist())) == len(rows)
+    assert np.array_equal(rows, bench.sample_rows(65536, 32776, bench.DUMP_LIMIT_BYTES))  # the same every time
+    assert rows.min() >= 0 and rows.max() < 65536 and np.all(np.diff(rows) > 0)
+    monkey = bench.DUMP_LIMIT_BYTES
+    try:
+        bench.DUMP_LIMIT_BYTES = 2 * (4 * 4 + 8)  # two rows of y
+        bench.dump_outputs(str(tmp_path / "b"), y)
+    finally:
+        bench.DUMP_LIMIT_BYTES = monkey
+    r = np.load(tmp_path / "b" / "rows.npy")
+    assert r.dtype == np.float64 and len(r) == 2
+    assert np.array_equal(np.load(tmp_path / "b" / "y.npy"), y.numpy()[r.astype(int)])
