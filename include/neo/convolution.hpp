@@ -142,6 +142,11 @@ auto normalize_impulse(Obj obj) noexcept -> void
 struct upola_v2_tag {};
 inline constexpr upola_v2_tag upola_v2{};
 
+/// selects a sparse handle (neo_hip_upols_create_sparse: sparse_upols_convolver /
+/// sparse_upola_convolver, sparse_convolver.hpp:12-17) in upols_multichannel
+struct sparse_tag {};
+inline constexpr sparse_tag sparse{};
+
 namespace detail {
 struct upols_deleter {
     void operator()(neo_hip_upols* h) const noexcept { neo_hip_upols_destroy(h); }
@@ -174,10 +179,38 @@ struct upols_multichannel {
         _h.reset(h);
     }
 
+    /// C sparse convolvers (method::upols or method::upola): only the filter bins a mask keeps
+    /// take part, kept as 128-byte tiles; filter_sparse() sets the filter (filter() and impulse()
+    /// throw), and the latency mode, paced work and offline windows do not apply (they throw)
+    upols_multichannel(sparse_tag, std::size_t channels, std::size_t block_size, std::size_t partitions,
+                       int device = neo::hip::detail::default_device(), method m = method::upols)
+        : _C{channels}, _B{block_size}, _P{partitions}
+    {
+        if (m != method::upols && m != method::upola)
+            throw std::invalid_argument{"neo_hip: sparse convolvers support method::upols and method::upola"};
+        neo_hip_upols* h = nullptr;
+        neo::hip::check(neo_hip_upols_create_sparse(int(channels), int(block_size), int(partitions), device,
+                                                    m == method::upola ? 1 : 0, nullptr, &h));
+        _h.reset(h);
+    }
+
     /// filter [C][P][B+1] complex<float>, contiguous host memory; resets state
     auto filter(std::complex<float> const* partitions) -> void
     {
         neo::hip::check(neo_hip_upols_set_filter(_h.get(), partitions, 0));
+    }
+    /// sparse handles: filter [C][P][B+1] and mask [C][P][B+1] (nonzero = keep), contiguous host
+    /// memory; resets state
+    auto filter_sparse(std::complex<float> const* partitions, std::uint8_t const* mask) -> void
+    {
+        neo::hip::check(neo_hip_upols_set_filter_sparse(_h.get(), partitions, mask, 0));
+    }
+    /// sparse handles: kept columns and kept 128-byte tiles of the current filter
+    [[nodiscard]] auto sparse_kept() const -> std::pair<std::int64_t, std::int64_t>
+    {
+        std::int64_t bins = 0, tiles = 0;
+        neo::hip::check(neo_hip_upols_sparse_info(_h.get(), &bins, &tiles, nullptr));
+        return {bins, tiles};
     }
     /// normalize_impulse (optional) + uniform_partition of ir [C][length] on the GPU
     auto impulse(float const* ir, std::size_t length, bool normalize = true) -> void
@@ -333,6 +366,72 @@ private:
     bool _latency = false;
     double _idle_ms = 50.0;
 };
+
+/// The mask a sparsity predicate gives over a filter matrix [P][B+1]: mask[p (B+1) + k] =
+/// sparsity(p, k, filter(p, k)), the call sparse_filter::filter makes per element
+/// (sparse_filter.hpp:25-28, csr_matrix.hpp:32-34). Host only.
+template<typename InMat, typename Sparsity>
+    requires neo::hip::detail::matrix_like<InMat>
+[[nodiscard]] auto sparsity_mask(InMat filter, Sparsity&& sparsity) -> std::vector<std::uint8_t>
+{
+    auto const P = std::size_t(filter.extent(0)), bins = std::size_t(filter.extent(1));
+    std::vector<std::uint8_t> mask(P * bins);
+    for (std::size_t p = 0; p < P; ++p)
+        for (std::size_t k = 0; k < bins; ++k)
+            mask[p * bins + k] = sparsity(p, k, neo::hip::detail::at(filter, p, k)) ? 1 : 0;
+    return mask;
+}
+
+/// Single-channel drop-in for sparse_upols_convolver<complex<float>> and, with M = method::upola,
+/// sparse_upola_convolver (sparse_convolver.hpp:12-17): filter([P][B+1], sparsity) with sparsity
+/// callable as (row, col, value) -> bool; operator()(block[B]) in place. One channel on a sparse
+/// handle of its own.
+template<typename Complex, method M = method::upols>
+struct hip_sparse_upols_convolver {
+    static_assert(std::same_as<Complex, std::complex<float>>);
+    using value_type = Complex;
+    using accumulator_type = neo::hip::array<Complex, 1>;
+
+    hip_sparse_upols_convolver() = default;
+
+    template<typename InMat, typename Sparsity>
+        requires neo::hip::detail::matrix_like<InMat>
+    auto filter(InMat filter, Sparsity&& sparsity) -> void
+    {
+        auto const P = std::size_t(filter.extent(0)), bins = std::size_t(filter.extent(1));
+        std::vector<Complex> h(P * bins);
+        for (std::size_t p = 0; p < P; ++p)
+            for (std::size_t k = 0; k < bins; ++k) h[p * bins + k] = Complex(neo::hip::detail::at(filter, p, k));
+        auto const mask = sparsity_mask(filter, sparsity);
+        if (!_impl || _impl->partitions() != P || _impl->block_size() != bins - 1)
+            _impl = std::make_unique<upols_multichannel>(sparse, 1, bins - 1, P, neo::hip::detail::default_device(), M);
+        _impl->filter_sparse(h.data(), mask.data());
+        _block.resize(bins - 1);
+    }
+
+    template<typename Vec>
+        requires neo::hip::detail::vector_like<Vec>
+    auto operator()(Vec block) -> void
+    {
+        if (neo::hip::detail::contiguous(block)) {
+            (*_impl)(block.data_handle());
+            return;
+        }
+        neo::hip::detail::gather(block, _block.data());
+        (*_impl)(_block.data());
+        neo::hip::detail::scatter(_block.data(), block);
+    }
+
+private:
+    std::unique_ptr<upols_multichannel> _impl;
+    std::vector<float> _block;
+};
+
+template<typename Complex>
+using sparse_upols_convolver = hip_sparse_upols_convolver<Complex>;
+
+template<typename Complex>
+using sparse_upola_convolver = hip_sparse_upols_convolver<Complex, method::upola>;
 
 /// Single-channel drop-in for upola_convolver_v2<complex<float>> (dense_convolver.hpp:28,
 /// overlap_add_convolver.hpp:20-136): operator()(samples) takes any number of samples.

@@ -54,8 +54,9 @@ typedef struct neo_hip_upols neo_hip_upols;
 
 /* -- library ------------------------------------------------------------ */
 /* ABI version of this header. neo_hip_upols_opts grows with it (0.1.0: 6 ints; 0.2.0: the 10
- * below), so a caller checks neo_hip_version() == NEO_HIP_VERSION before passing one. */
-#define NEO_HIP_VERSION 200 /* 0.2.0 */
+ * below), so a caller checks neo_hip_version() == NEO_HIP_VERSION before passing one.
+ * 0.3.0: the sparse convolvers (neo_hip_upols_create_sparse and what goes with it). */
+#define NEO_HIP_VERSION 300 /* 0.3.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -139,6 +140,42 @@ typedef struct neo_hip_upols_opts {
 } neo_hip_upols_opts;
 NEO_HIP_API int neo_hip_upols_create_ex(int channels, int block, int partitions, int device, int method,
                                         const neo_hip_upols_opts* opts, neo_hip_upols** h);
+/* -- Sparse convolvers ----------------------------------------------------------
+ * C instances of sparse_upols_convolver / sparse_upola_convolver (method 0 / 1;
+ * src/neo/convolution/sparse_convolver.hpp:12-17) over sparse_filter (sparse_filter.hpp:25-45),
+ * as the plugin's sparse_convolve steps them (extra/plugin/src/dsp/DenseConvolution.cpp:124-186):
+ * only the filter bins a mask keeps take part in the sums (the reference's CSR multiply_add,
+ * src/neo/algorithm/multiply_add.hpp:303-324). The reference stores single bins; here the unit is
+ * a TILE of 16 packed bins (128 B, one memory request) of a packed filter row: packed index 0 =
+ * {DC, Nyquist}, so reference columns 0 and B both lie in tile 0 and column k in [1, B) in tile
+ * k / 16. A tile is kept if the mask keeps any of its columns; the columns it drops inside a kept
+ * tile are stored as zero (DC and Nyquist each on its own), so the results are those of the dense
+ * convolver on the filter with the dropped columns zeroed. Per filter row the handle keeps a
+ * bitmap of NW = max(1, B / 512) uint32 words (tile t = bit t % 32 of word t / 32) and an offset
+ * in tiles into its channel's compacted values ([C][P + 1], the exclusive prefix sum of the rows'
+ * popcounts); a block step reads the kept tiles of the filter and of the FDL rows only.
+ * A sparse handle holds no dense filter buffer and no streaming-level, batch or offline buffers.
+ * Of opts only fused and split_workgroups apply (the partitions are cut at equal row counts, as
+ * the dense plain step cuts them; with the same cuts and the same fused choice its outputs equal
+ * the dense plain step's on the zeroed filter bit for bit, up to the sign of zero). method 2
+ * (sub-block input) is EINVAL. On a sparse handle process, process_device, process_blocks (one
+ * block per pass), process_samples (multiples of B), reset, info, destroy and the timing calls
+ * work; set_filter and set_impulse (it takes set_filter_sparse), set_ahead(1), set_offline(1),
+ * set_batch(1), set_persistent(1) and set_paced(1 / 2) return EINVAL and name the reason, and the
+ * getters report off. Groups and the multi-device convolver take no sparse members. */
+NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partitions, int device, int method,
+                                            const neo_hip_upols_opts* opts, neo_hip_upols** h);
+/* filter [C][P][B+1] complex and mask [C][P][B+1] bytes (nonzero = keep), both host or both device
+ * memory; sparse handles only. Resets all state, like filter(). The bitmaps, offsets and compacted
+ * tiles are made on the device; the call waits on the handle's stream, never on the device. */
+NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device);
+/* the current filter's kept columns and kept tiles over all channels, and the device bytes that
+ * stand in for a dense handle's [C][R][B] filter buffer (tiles, bitmaps, offsets) */
+NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, int64_t* kept_tiles, int64_t* filter_bytes);
+/* The format on the host (no device needed; it is what set_filter_sparse computes on the device):
+ * mask [C][P][B+1] -> tile_mask [C][P][NW], row_off [C][P+1], kept columns, kept tiles. */
+NEO_HIP_API int neo_hip_upols_sparse_plan(const uint8_t* mask, int channels, int block, int partitions,
+                                          uint32_t* tile_mask, uint32_t* row_off, int64_t* kept_bins, int64_t* kept_tiles);
 NEO_HIP_API int neo_hip_upols_destroy(neo_hip_upols* h);
 /* filter [C][P][B+1] complex (uniform_partition layout), host or device memory;
  * like uniform_partitioned_convolver::filter() it also resets all state. */

@@ -1,0 +1,56 @@
+// sparse_plan.hpp — the tile-compacted sparse filter format, on the host (no HIP header: the
+// plan needs no device and a plain C++ compiler builds it).
+//
+// The reference's sparse_filter (src/neo/convolution/sparse_filter.hpp:25-45) keeps single bins
+// in CSR. Here the unit is a TILE: 16 packed complex bins, 128 B, of one packed filter row
+// (packed index 0 = {DC, Nyquist}, packed index k = bin k for 1 <= k < B). Reference column
+// k in [1, B) lies in tile k / 16; columns 0 (DC) and B (Nyquist) both lie in tile 0. A row has
+// NT = B / 16 tiles and a bitmap of NW = max(1, B / 512) uint32 words (tile t = bit t % 32 of
+// word t / 32). A tile is kept if the mask keeps any of its columns; dropped columns inside a
+// kept tile are stored as zero. Row (c, p) starts at tile row_off[c][p] of channel c's compacted
+// values ([C][P + 1], the exclusive prefix sum of the rows' popcounts).
+#pragma once
+
+#include <cstdint>
+
+namespace neo_hip {
+
+constexpr int kSparseTile = 16;  // packed complex bins per tile (128 B)
+
+constexpr int sparse_words(int block) { return block / 512 > 1 ? block / 512 : 1; }
+
+constexpr bool sparse_block_ok(int b) { return b >= 16 && b <= 4096 && (b & (b - 1)) == 0; }
+
+// mask [C][P][B + 1] (nonzero = keep) -> tile_mask [C][P][NW], row_off [C][P + 1], the kept
+// columns and the kept tiles over all channels. false: bad arguments (nothing written).
+inline bool sparse_plan(const uint8_t* mask, int channels, int block, int partitions, uint32_t* tile_mask,
+                        uint32_t* row_off, int64_t* kept_bins, int64_t* kept_tiles)
+{
+    if (!mask || !tile_mask || !row_off || channels < 1 || partitions < 1 || !sparse_block_ok(block)) return false;
+    const int NW = sparse_words(block);
+    int64_t bins = 0, tiles = 0;
+    for (int64_t c = 0; c < channels; ++c) {
+        uint32_t off = 0;
+        for (int64_t p = 0; p < partitions; ++p) {
+            const int64_t r = c * partitions + p;
+            const uint8_t* m = mask + r * (int64_t(block) + 1);
+            uint32_t* w = tile_mask + r * NW;
+            for (int i = 0; i < NW; ++i) w[i] = 0;
+            for (int k = 0; k <= block; ++k) {
+                if (!m[k]) continue;
+                const int t = k == block ? 0 : k / kSparseTile;  // Nyquist shares packed bin 0 with DC
+                w[t >> 5] |= uint32_t(1) << (t & 31);
+                ++bins;
+            }
+            row_off[c * (int64_t(partitions) + 1) + p] = off;
+            for (int i = 0; i < NW; ++i) off += uint32_t(__builtin_popcount(w[i]));
+        }
+        row_off[c * (int64_t(partitions) + 1) + partitions] = off;
+        tiles += off;
+    }
+    if (kept_bins) *kept_bins = bins;
+    if (kept_tiles) *kept_tiles = tiles;
+    return true;
+}
+
+}  // namespace neo_hip

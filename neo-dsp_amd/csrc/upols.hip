@@ -31,6 +31,8 @@
 // and normalization. upols_device.hpp / upols_handle.hpp: what they share.
 #include "upols_device.hpp"
 #include "upols_handle.hpp"
+#include "sparse_plan.hpp"
+#include "upols_step.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -41,266 +43,7 @@
 
 namespace neo_hip {
 
-// One whole block step for every channel (grid C x S, 256 lanes). Workgroup (c, s)
-// accumulates partitions [p0, p1) into a partial spectrum; split 0 first runs the
-// window r2c and inserts FDL row w. Each workgroup publishes its slab, and the last
-// of a channel's S workgroups to arrive (agent-scope release -> counter -> acquire,
-// cdna_hip_programming.md §6 G16 / split-K seam) sums the slabs in the fixed order
-// s = 0..S-1 and runs the c2r: one launch per block, deterministic results.
-// TAIL (upola_convolver_v2 sub-block pieces): no window / insert, partitions p >= 1 only
-// (overlap_add_convolver.hpp:96-108), slabs summed by k_upola2_piece.
-// latency-mode probe builds (NEO_PS_PROBE): thread 0 stamps point i of the plain step into mk
-#ifdef NEO_PS_PROBE
-#define NEO_STEP_MARK(i)                                    \
-    do {                                                    \
-        if (mk && threadIdx.x == 0) mk[i] = wall_clock64(); \
-    } while (0)
-#else
-#define NEO_STEP_MARK(i) \
-    do {                 \
-    } while (0)
-#endif
-
-// the LDS of one step workgroup (k_upols_step, k_plain_persist)
-template<int B>
-struct step_lds {
-    using K = upols_cfg<B>;
-    __attribute__((aligned(16))) cf xnew[B];  // new spectrum; later the summed spectrum
-    cf fft[K::LL];
-    cf tw[K::TW1 + K::TW2];
-    __attribute__((aligned(16))) float4 red[K::RPI > 1 ? 256 * 2 * K::VPT : 1];
-    int last;
-};
-
-// The step of workgroup (c, s): returns true in the workgroup that ran the channel's tail (FUSED:
-// the last split to arrive). WT (the latency mode's persistent plain step): the input block read
-// at system scope and the output stored write-through.
-template<int B, bool FUSED, bool OLA, bool TAIL, int UNROLL, bool WT = false>
-__device__ __forceinline__ bool upols_step_wg(step_lds<B>& L, int c, int s,
-    const float* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out, float* __restrict__ prev,
-    const cf* __restrict__ H, cf* __restrict__ fdl, cf* __restrict__ part, int* __restrict__ arrivals,
-    const cf* __restrict__ twg, int P, int ring, int S, int rows, int w, int64_t cstride, int64_t pstride, int pc,
-    unsigned long long* mk = nullptr)
-{
-    (void)mk;
-    using K = upols_cfg<B>;
-    static_assert(!(TAIL && FUSED), "the v2 tail is summed by k_upola2_piece");
-    cf* xnew = L.xnew;
-    cf* fft = L.fft;
-    cf* tw = L.tw;
-    float4* red = L.red;
-    int& last = L.last;
-
-    const int tid = threadIdx.x;
-    const int p0 = s * rows, p1 = min(P, p0 + rows);
-    const int64_t crow = int64_t(c) * cstride;  // channel base in H / FDL (complex units); row p at + p * pstride
-    const int64_t ps4 = pstride / 2;            // row stride in float4 units
-
-    if (!TAIL && s == 0) {
-        const float* in_c = in + int64_t(c) * ld_in;
-        float* prev_c = prev + int64_t(c) * B;
-        window_fft<B, OLA, (B / 8 <= 256 ? 8 : B / 256), WT>(prev_c, in_c, fft, tw, tid, twg);
-        NEO_STEP_MARK(1);
-        cf* row = fdl + crow + int64_t(w) * pstride;
-        for (int k = tid; k < B; k += 256) {
-            const cf x = r2c_split<B>(fft, tw + K::TW1, k);
-            xnew[k] = x;
-            row[k] = x;
-        }
-        if constexpr (!OLA && !WT) {  // the window's second half becomes the next call's first half (WT: window_fft)
-            for (int i = tid; i < B / 4; i += 256)
-                reinterpret_cast<float4*>(prev_c)[i] = reinterpret_cast<const float4*>(in_c)[i];
-        }
-        __syncthreads();
-    }
-
-    const int rs = tid / K::QT, q0 = tid - rs * K::QT;
-    acc4 a[2 * K::VPT];
-#pragma unroll
-    for (int v = 0; v < 2 * K::VPT; ++v) a[v] = {0.f, 0.f, 0.f, 0.f};
-
-    const float4* H4 = reinterpret_cast<const float4*>(H + crow);
-    const float4* F4 = reinterpret_cast<const float4*>(fdl + crow);
-    int pstart = p0;
-    if (TAIL && p0 == 0) pstart = 1;
-    if (!TAIL && p0 == 0) {
-        if (rs == 0) {
-            const float4* Xn = reinterpret_cast<const float4*>(xnew);
-#pragma unroll
-            for (int v = 0; v < K::VPT; ++v) {
-                const int q = q0 + v * K::QT;
-                mac2(a[2 * v], a[2 * v + 1], H4[q], Xn[q]);
-            }
-        }
-        pstart = 1;
-    }
-    // main loop over [pbeg, pend): UNROLL row-groups in flight, no bounds checks inside.
-    // Filter rows below `pc` use the default (cacheable) policy so they can stay resident
-    // in the 256 MiB Infinity Cache across steps; everything else streams nontemporally.
-    auto mac_rows = [&]<bool NTH>(int pbeg, int pend) {
-        int p = pbeg + rs;
-        for (; p + (UNROLL - 1) * K::RPI < pend; p += UNROLL * K::RPI) {
-            float4 hv[UNROLL][K::VPT], xv[UNROLL][K::VPT];
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u) {
-                const int pp = p + u * K::RPI;
-                const int fr = w >= pp ? w - pp : w - pp + ring;  // fdl_index.hpp:28-31 ring
-#pragma unroll
-                for (int v = 0; v < K::VPT; ++v) {
-                    const int q = q0 + v * K::QT;
-                    hv[u][v] = ld4<NTH>(H4 + int64_t(pp) * ps4 + q);
-                    xv[u][v] = ld4_nt(F4 + int64_t(fr) * ps4 + q);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < UNROLL; ++u)
-#pragma unroll
-                for (int v = 0; v < K::VPT; ++v) mac2(a[2 * v], a[2 * v + 1], hv[u][v], xv[u][v]);
-        }
-        for (; p < pend; p += K::RPI) {
-            const int fr = w >= p ? w - p : w - p + ring;
-#pragma unroll
-            for (int v = 0; v < K::VPT; ++v) {
-                const int q = q0 + v * K::QT;
-                mac2(a[2 * v], a[2 * v + 1], ld4<NTH>(H4 + int64_t(p) * ps4 + q), ld4_nt(F4 + int64_t(fr) * ps4 + q));
-            }
-        }
-    };
-    const int pmid = min(p1, max(pstart, pc));
-    if (pmid > pstart) mac_rows.template operator()<false>(pstart, pmid);
-    if (p1 > pmid) mac_rows.template operator()<true>(pmid, p1);
-    if (s < 2) NEO_STEP_MARK(2 + s);  // MAC loop issued (its loads land at the first use below)
-
-    if constexpr (K::RPI > 1) {
-        // fold the row groups into group 0 (fixed order -> deterministic)
-#pragma unroll
-        for (int v = 0; v < K::VPT; ++v) {
-            red[(tid * K::VPT + v) * 2 + 0] = make_float4(a[2 * v].rr, a[2 * v].ii, a[2 * v].ri, a[2 * v].ir);
-            red[(tid * K::VPT + v) * 2 + 1] =
-                make_float4(a[2 * v + 1].rr, a[2 * v + 1].ii, a[2 * v + 1].ri, a[2 * v + 1].ir);
-        }
-        __syncthreads();
-        if (rs == 0) {
-            for (int g = 1; g < K::RPI; ++g) {
-#pragma unroll
-                for (int v = 0; v < K::VPT; ++v) {
-                    const int idx = ((g * K::QT + q0) * K::VPT + v) * 2;
-                    const float4 r0 = red[idx], r1 = red[idx + 1];
-                    a[2 * v].rr += r0.x; a[2 * v].ii += r0.y; a[2 * v].ri += r0.z; a[2 * v].ir += r0.w;
-                    a[2 * v + 1].rr += r1.x; a[2 * v + 1].ii += r1.y; a[2 * v + 1].ri += r1.z; a[2 * v + 1].ir += r1.w;
-                }
-            }
-        }
-    }
-    float* out_c = out + int64_t(c) * ld_out;
-
-    if (FUSED && S == 1) {  // whole channel in this workgroup: finish straight from registers
-        __syncthreads();  // xnew reads (p = 0) done before it is overwritten
-        if (rs == 0) {
-#pragma unroll
-            for (int v = 0; v < K::VPT; ++v) {
-                const int q = q0 + v * K::QT;
-                const cf b0 = finish(a[2 * v], q == 0), b1 = finish(a[2 * v + 1], false);
-                reinterpret_cast<float4*>(xnew)[q] = make_float4(b0.x, b0.y, b1.x, b1.y);
-            }
-        }
-        __syncthreads();
-        c2r_tail<B, OLA, (B / 4 <= 256 ? 4 : B / 256), false, false, WT>(xnew, fft, tw, out_c, prev + int64_t(c) * B, tid);
-        return true;
-    }
-
-    // publish this split's slab
-    float4* slab = reinterpret_cast<float4*>(part + (int64_t(c) * S + s) * B);
-    if (rs == 0) {
-#pragma unroll
-        for (int v = 0; v < K::VPT; ++v) {
-            const int q = q0 + v * K::QT;
-            const cf b0 = finish(a[2 * v], q == 0), b1 = finish(a[2 * v + 1], false);
-            slab[q] = make_float4(b0.x, b0.y, b1.x, b1.y);
-        }
-    }
-    if constexpr (!FUSED) return false;  // k_upols_finish sums the slabs in the next launch
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
-    __syncthreads();
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // keep the release's wait (G16 pitfall)
-        const int before = __hip_atomic_fetch_add(arrivals + c, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        last = before == S - 1;
-    }
-    __syncthreads();
-    if (!last) return false;  // uniform per workgroup
-    if (tid == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(arrivals + c, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next step
-    }
-    NEO_STEP_MARK(4);  // the tail: every split arrived
-    if (s != 0)
-        for (int i = tid; i < K::TW1 + K::TW2; i += 256) tw[i] = twg[i];
-    __syncthreads();
-
-    // sum the S slabs in order s = 0..S-1, 8 loads in flight
-    const float4* p4 = reinterpret_cast<const float4*>(part + int64_t(c) * S * B);
-    if constexpr (K::Q > 256) {
-        // B >= 1024: QI float4 per lane and slab; every lane's loads of SB slabs in flight at once
-        // (one trip to memory per SB slabs instead of one per float4: the latency-bound one-channel
-        // step at B = 4096), the same order per bin
-        constexpr int QI = K::Q / 256, SB = QI >= 8 ? 2 : 16 / QI;
-        float4 sum[QI];
-#pragma unroll
-        for (int i = 0; i < QI; ++i) sum[i] = p4[tid + i * 256];
-        int t = 1;
-        for (; t + SB - 1 < S; t += SB) {
-            float4 r[SB][QI];
-#pragma unroll
-            for (int u = 0; u < SB; ++u)
-#pragma unroll
-                for (int i = 0; i < QI; ++i) r[u][i] = p4[int64_t(t + u) * K::Q + tid + i * 256];
-#pragma unroll
-            for (int u = 0; u < SB; ++u)
-#pragma unroll
-                for (int i = 0; i < QI; ++i) {
-                    sum[i].x += r[u][i].x; sum[i].y += r[u][i].y; sum[i].z += r[u][i].z; sum[i].w += r[u][i].w;
-                }
-        }
-        for (; t < S; ++t) {
-            float4 r[QI];
-#pragma unroll
-            for (int i = 0; i < QI; ++i) r[i] = p4[int64_t(t) * K::Q + tid + i * 256];
-#pragma unroll
-            for (int i = 0; i < QI; ++i) {
-                sum[i].x += r[i].x; sum[i].y += r[i].y; sum[i].z += r[i].z; sum[i].w += r[i].w;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < QI; ++i) reinterpret_cast<float4*>(xnew)[tid + i * 256] = sum[i];
-    } else
-    for (int q = tid; q < K::Q; q += 256) {
-        float4 sum = p4[q];
-        int t = 1;
-        for (; t + 7 < S; t += 8) {
-            float4 r[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) r[u] = p4[int64_t(t + u) * K::Q + q];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                sum.x += r[u].x; sum.y += r[u].y; sum.z += r[u].z; sum.w += r[u].w;
-            }
-        }
-        for (; t < S; ++t) {
-            const float4 r = p4[int64_t(t) * K::Q + q];
-            sum.x += r.x; sum.y += r.y; sum.z += r.z; sum.w += r.w;
-        }
-        reinterpret_cast<float4*>(xnew)[q] = sum;
-    }
-    __syncthreads();
-    NEO_STEP_MARK(5);  // slabs summed
-    c2r_tail<B, OLA, (B / 4 <= 256 ? 4 : B / 256), false, false, WT>(xnew, fft, tw, out_c, prev + int64_t(c) * B, tid);
-    NEO_STEP_MARK(6);  // output stores issued
-    return true;
-}
-
+// the step of one workgroup: upols_step_wg (upols_step.hpp)
 template<int B, bool FUSED, bool OLA, bool TAIL = false, int UNROLL = upols_cfg<B>::U>
 __global__ __launch_bounds__(256, (B <= 1024 ? 8 : 2)) void k_upols_step(
     const float* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out, float* __restrict__ prev,
@@ -603,6 +346,10 @@ void destroy(upols_t* h)
     // device buffers back to the pool (dmem.hip): no device-wide synchronization; the caller
     // joined every stream that used them
     dfree(h->H);  // the FDL shares H's allocation (rows [nrows, 2 nrows))
+    if (h->sparse) {  // no dense filter: the FDL is an allocation of its own
+        dfree(h->fdl);
+        sparse_free(h);
+    }
     dfree(h->part);
     dfree(h->prev);
     dfree(h->arrivals);
@@ -628,8 +375,22 @@ int launch_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t 
 
 }  // namespace
 
+int neo_hip::launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s)
+{
+    if (h->ola) {
+        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, true>), dim3(unsigned(h->C)), dim3(256), 0,
+                                                    s, h->part, out, ld_out, h->prev, h->tw, h->S))
+    } else {
+        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, false>), dim3(unsigned(h->C)), dim3(256),
+                                                    0, s, h->part, out, ld_out, h->prev, h->tw, h->S))
+    }
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
 int neo_hip::launch_step_normal(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
+    if (h->sparse) return launch_sparse_step(h, in, ld_in, out, ld_out, s);
     if (h->ahead) return launch_levels(h, in, ld_in, out, ld_out, s);
     if (int rc = lvl_join(h, s)) return rc;
     upols_t::ev_group* ev = nullptr;
@@ -650,16 +411,8 @@ int neo_hip::launch_step_normal(upols_t* h, const float* in, int64_t ld_in, floa
     NEO_HIP_LAUNCH_CHECK();
     h->fdl_zero = false;
     if (int rc = timing_mark(ev, 1, s)) return rc;
-    if (!h->fused) {
-        if (h->ola) {
-            NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, true>), dim3(unsigned(h->C)), dim3(256), 0,
-                                                        s, h->part, out, ld_out, h->prev, h->tw, h->S))
-        } else {
-            NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, false>), dim3(unsigned(h->C)), dim3(256),
-                                                        0, s, h->part, out, ld_out, h->prev, h->tw, h->S))
-        }
-        NEO_HIP_LAUNCH_CHECK();
-    }
+    if (!h->fused)
+        if (int rc = launch_finish(h, out, ld_out, s)) return rc;
     h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;  // fdl_index.hpp:35-37
     h->lv_n = -1;
     return NEO_HIP_OK;
@@ -906,7 +659,127 @@ int neo_hip::create_handle(int channels, int block, int partitions, int device, 
     return rc;
 }
 
+namespace {
+// A sparse handle (sparse_upols_convolver / sparse_upola_convolver, src/neo/convolution/
+// sparse_convolver.hpp:12-17): the FDL ring, the step state and the bitmaps / offsets; the
+// compacted tiles come with the filter (sparse_set_filter). No dense filter buffer, no level,
+// batch or offline buffers.
+int create_sparse(int channels, int block, int partitions, int device, bool ola, const neo_hip_upols_opts* opt,
+                  neo_hip_upols** out)
+{
+    if (!out) return fail(NEO_HIP_EINVAL, "handle pointer is null");
+    *out = nullptr;
+    const int o_fused = opt ? opt->fused : -1, o_split = opt ? opt->split_workgroups : 0;
+    if (o_fused < -1 || o_fused > 1 || o_split < 0) return fail(NEO_HIP_EINVAL, "invalid convolver options");
+    if (channels < 1) return fail(NEO_HIP_EINVAL, "channels must be >= 1");
+    if (!valid_block(block)) return fail(NEO_HIP_EINVAL, "block must be a power of two in [16, 4096], got %d", block);
+    if (partitions < 1) return fail(NEO_HIP_EINVAL, "partitions must be >= 1");
+    // the step reads a channel's FDL ring (and its tiles, never more bytes than P rows) through one
+    // buffer descriptor each
+    if ((int64_t(partitions) + kMaxBatch - 1) * block * int64_t(sizeof(cf)) >= (int64_t(1) << 31))
+        return fail(NEO_HIP_EINVAL, "sparse convolvers take channels whose FDL ring spans < 2 GiB (%d partitions of %d)",
+                    partitions, block);
+    device_guard g(device);
+    if (g.rc) return g.rc;
+    auto* h = new upols_t{};
+    (void)hipGetDevice(&h->device);
+    h->sparse = true;
+    h->C = channels;
+    h->B = block;
+    h->P = partitions;
+    h->ring = partitions + kMaxBatch - 1;
+    h->ola = ola;
+    h->batch = false;  // process_blocks: one block per pass through the sparse step
+    // one launch or two, and the splits: the dense plain step's rules (create_convolver) on the
+    // dense shape, so a sparse handle and a dense one of the same shape and options cut the
+    // partitions alike (equal row counts; the order per bin is the dense order)
+    h->fused = 2.0 * 8.0 * double(channels) * double(partitions) * double(block) < double(kFusedMaxBytes);
+    if (o_fused >= 0) h->fused = o_fused != 0;
+    h->cstride = int64_t(h->ring) * block;
+    h->pstride = block;
+    const int target = o_split ? o_split : 1024;
+    const int min_rows = o_split ? 1 : h->fused ? (block > 512 ? 8 : 16) : 8;
+    const int S = std::max(1, std::min({(target + channels - 1) / channels, (partitions + min_rows - 1) / min_rows, 64}));
+    h->rows = (partitions + S - 1) / S;
+    h->S = (partitions + h->rows - 1) / h->rows;
+    const size_t rowbytes = size_t(block) * sizeof(cf);
+    auto bail = [&](int code) {
+        destroy(h);
+        return code;
+    };
+    if (int rc = shared_stream(&h->stream)) return bail(rc);
+    if (dalloc(&h->fdl, size_t(channels) * size_t(h->ring) * rowbytes) ||
+        dalloc(&h->part, size_t(channels) * h->S * rowbytes) || dalloc(&h->prev, size_t(channels) * block * sizeof(float)) ||
+        dalloc(&h->arrivals, size_t(channels) * sizeof(int)) || sparse_alloc(h))
+        return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(channels) * size_t(h->ring) * rowbytes));
+    int rc = shared_tw(&h->tw, block);
+    if (rc) return bail(rc);
+    if ((rc = reset_state(h, h->stream))) return bail(rc);
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(NEO_HIP_ERUNTIME, "sync failed"));
+    *out = h;
+    return NEO_HIP_OK;
+}
+}  // namespace
+
 extern "C" {
+
+NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partitions, int device, int method,
+                                            const neo_hip_upols_opts* opts, neo_hip_upols** out)
+{
+    if (method < 0 || method > 1)
+        return fail(NEO_HIP_EINVAL, "sparse convolvers: method must be 0 (upols) or 1 (upola); whole blocks only");
+    return create_sparse(channels, block, partitions, device, method == 1, opts, out);
+}
+
+NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device)
+{
+    if (!h || !filter || !mask) return fail(NEO_HIP_EINVAL, "null handle, filter or mask");
+    if (!h->sparse) return fail(NEO_HIP_EINVAL, "set_filter_sparse: not a sparse handle (neo_hip_upols_create_sparse)");
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device filter's producer)
+    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
+    const cf* src = static_cast<const cf*>(filter);
+    const uint8_t* msk = mask;
+    cf* tmp = nullptr;
+    uint8_t* tmpm = nullptr;
+    int rc = NEO_HIP_OK;
+    if (!is_device) {
+        if (dalloc(&tmp, n * sizeof(cf)) || dalloc(&tmpm, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+        else if (hipMemcpyAsync(tmp, filter, n * sizeof(cf), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+                 hipMemcpyAsync(tmpm, mask, n, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
+        src = tmp;
+        msk = tmpm;
+    }
+    if (!rc) rc = sparse_set_filter(h, src, msk, h->stream);
+    if (!rc) rc = reset_state(h, h->stream);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(tmp);  // the stream was joined above
+    dfree(tmpm);
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, int64_t* kept_tiles, int64_t* filter_bytes)
+{
+    if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (!h->sparse) return fail(NEO_HIP_EINVAL, "sparse_info: not a sparse handle");
+    if (kept_bins) *kept_bins = h->sp_bins;
+    if (kept_tiles) *kept_tiles = h->sp_tiles;
+    if (filter_bytes)  // the compacted tiles, the bitmaps and the offsets: what stands in for the [C][R][B] filter
+        *filter_bytes = h->sp_tiles * int64_t(kSparseTile * sizeof(cf)) +
+                        int64_t(h->C) * (int64_t(h->P) * sparse_words(h->B) + h->P + 1) * int64_t(sizeof(uint32_t));
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_upols_sparse_plan(const uint8_t* mask, int channels, int block, int partitions,
+                                          uint32_t* tile_mask, uint32_t* row_off, int64_t* kept_bins, int64_t* kept_tiles)
+{
+    if (!sparse_plan(mask, channels, block, partitions, tile_mask, row_off, kept_bins, kept_tiles))
+        return fail(NEO_HIP_EINVAL, "sparse_plan: null pointer, channels or partitions < 1, or block not a power of two "
+                                    "in [16, 4096]");
+    return NEO_HIP_OK;
+}
 
 NEO_HIP_API int neo_hip_upols_create(int channels, int block, int partitions, int device, neo_hip_upols** out)
 {
@@ -966,6 +839,8 @@ NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h)
 NEO_HIP_API int neo_hip_upols_set_filter(neo_hip_upols* h, const void* filter, int is_device)
 {
     if (!h || !filter) return fail(NEO_HIP_EINVAL, "null handle or filter");
+    if (h->sparse)
+        return fail(NEO_HIP_EINVAL, "set_filter: a sparse handle keeps no dense filter (neo_hip_upols_set_filter_sparse)");
     device_guard g(h->device);
     if (g.rc) return g.rc;
     if (int rc = persist_stop(h)) return rc;
@@ -994,6 +869,9 @@ NEO_HIP_API int neo_hip_upols_set_impulse(neo_hip_upols* h, const float* ir, int
                                           int is_device)
 {
     if (!h || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
+    if (h->sparse)
+        return fail(NEO_HIP_EINVAL, "set_impulse: a sparse handle takes a partitioned filter and its mask "
+                                    "(neo_hip_upols_set_filter_sparse)");
     if (partitions_for(length, h->B) != h->P)
         return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
                     (long long)partitions_for(length, h->B), h->P);
@@ -1123,6 +1001,7 @@ NEO_HIP_API int neo_hip_upols_batch_info(neo_hip_upols* h, int* blocks_per_pass,
 NEO_HIP_API int neo_hip_upols_set_batch(neo_hip_upols* h, int enable)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle runs one block per pass (no batched passes)");
     h->batch = enable != 0;
     return NEO_HIP_OK;
 }
@@ -1130,6 +1009,7 @@ NEO_HIP_API int neo_hip_upols_set_batch(neo_hip_upols* h, int enable)
 NEO_HIP_API int neo_hip_upols_set_offline(neo_hip_upols* h, int enable)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle has no offline windows (no dense filter spectra)");
     if (enable && (h->v2 || h->P < kOffMinP))
         return fail(NEO_HIP_EINVAL, "offline windows take whole-block handles of >= %d partitions", kOffMinP);
     h->off = enable != 0;
@@ -1147,6 +1027,7 @@ NEO_HIP_API int neo_hip_upols_get_offline(neo_hip_upols* h, int* enabled, int* s
 NEO_HIP_API int neo_hip_upols_set_ahead(neo_hip_upols* h, int enable)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle has no streaming levels (no dense filter)");
     if (enable && h->v2) return fail(NEO_HIP_EINVAL, "streaming levels are for whole-block upols / upola handles");
     if (enable && h->B > 1024) return fail(NEO_HIP_EINVAL, "streaming levels take blocks up to 1024");
     device_guard g(h->device);
@@ -1163,6 +1044,7 @@ NEO_HIP_API int neo_hip_upols_set_paced(neo_hip_upols* h, int enable)
     device_guard g(h->device);
     if (g.rc) return g.rc;
     if (enable < 0 || enable > 2) return fail(NEO_HIP_EINVAL, "paced: 0 off, 1 a piece per call, 2 two pieces per group");
+    if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle has no background work to pace (no streaming levels)");
     if (enable == h->paced) return NEO_HIP_OK;
     if (int rc = persist_stop(h)) return rc;  // a resident latency-mode kernel leaves first (lv_n restarts)
     if (int rc = lvl_join(h, h->stream)) return rc;
@@ -1178,6 +1060,7 @@ NEO_HIP_API int neo_hip_upols_set_persistent(neo_hip_upols* h, int enable, doubl
     device_guard g(h->device);
     if (g.rc) return g.rc;
     if (enable) {
+        if (h->sparse) return fail(NEO_HIP_EINVAL, "latency mode: a sparse handle has no persistent step");
         if (const char* why = persist_ineligible(h)) return fail(NEO_HIP_EINVAL, "latency mode: %s", why);
         if (!(idle_ms > 0.0 && idle_ms <= 10000.0)) return fail(NEO_HIP_EINVAL, "idle_ms must be in (0, 10000]");
         if (int rc = setup_join(h)) return rc;  // this handle's steps queued on any stream come first

@@ -242,6 +242,15 @@ struct neo_hip_upols {
     // Default [C][P][B]; NEO_HIP_LAYOUT=pcb selects partition-major [P][C][B] (A/B).
     int64_t cstride = 0, pstride = 0;
     int pc = 0;  // filter rows per channel read with the cacheable policy (kCacheBudgetBytes; NEO_HIP_CACHE_ROWS)
+    // sparse handle (neo_hip_upols_create_sparse, upols_sparse.hip; format: sparse_plan.hpp): no
+    // dense filter (H stays null, the FDL is an allocation of its own), no levels, batches or
+    // offline windows; every block is one k_upols_sparse_step
+    bool sparse = false;
+    uint32_t* sp_bits = nullptr;   // kept-tile bitmaps [C][P][NW]
+    uint32_t* sp_off = nullptr;    // row offsets [C][P + 1], tile units within the channel
+    int64_t* sp_base = nullptr;    // [C + 2]: channel c's first tile, the total at [C]; kept columns at [C + 1]
+    neo_hip::cf* sp_val = nullptr; // compacted tiles [kept tiles][16] (null until a filter is set, or none kept)
+    int64_t sp_tiles = 0, sp_bins = 0;
     struct ev_group {
         hipEvent_t e[4] = {};
         int n = 0;
@@ -326,6 +335,15 @@ inline int batch_blocks(const upols_t* h) { return batch_t(h->B, h->bNB, h->bT);
 // destroyed with the handle) instead of one of the device's shared streams (upols.hip)
 int create_handle(int channels, int block, int partitions, int device, int method, hipStream_t stream,
                   neo_hip_upols** out);
+// upols_sparse.hip: the sparse handle's buffers (bitmaps, offsets; the FDL and the step state are
+// the creator's), its filter (filter and mask [C][P][B + 1] on the device -> bitmaps, offsets and
+// compacted tiles; one 16-byte copy back, h->stream joined) and its block step
+int sparse_alloc(upols_t* h);
+void sparse_free(upols_t* h);
+int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s);
+int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
+// upols.hip: the unfused step's second launch (k_upols_finish: slabs summed in order, c2r)
+int launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s);
 // upols_batch.hip: T whole blocks in one pass over the filter and the FDL
 int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch

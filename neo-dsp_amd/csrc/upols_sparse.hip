@@ -1,0 +1,247 @@
+// upols_sparse.hip — sparse (perceptually thinned) UPOLS / UPOLA convolvers on tile-compacted
+// filters: sparse_upols_convolver / sparse_upola_convolver (src/neo/convolution/
+// sparse_convolver.hpp:12-17) over sparse_filter (sparse_filter.hpp:25-45), whose CSR
+// multiply_add (src/neo/algorithm/multiply_add.hpp:303-324) adds exactly the kept terms.
+//
+// Format (sparse_plan.hpp): the unit is a 128-B tile of 16 packed bins, not a bin -- a gather of
+// single 8-B bins would still move whole 128-B requests. Per filter row a bitmap of kept tiles
+// and a tile offset into the channel's compacted values; the FDL stays [C][R][B] and every step
+// inserts the whole new row (later partitions keep other tiles).
+//
+// Step: k_upols_sparse_step is the dense plain step (upols_step.hpp: window r2c, FDL insert,
+// acc4 accumulators, row-group fold, slabs, last-arriver tail or k_upols_finish) with the loop
+// over the partitions reading only the kept tiles of the filter AND of the FDL rows. The order
+// of the sums per bin is the dense order with the dropped terms left out, so with the same
+// splits a sparse handle equals the dense plain step on the zeroed filter bit for bit (a 0 * x
+// term leaves a float sum unchanged), up to the sign of zero.
+#include "sparse_plan.hpp"
+#include "upols_handle.hpp"
+#include "upols_step.hpp"
+
+#include <algorithm>
+
+namespace neo_hip {
+
+// Rows in flight per lane and workgroups per CU, so that no instantiation spills: B < 128 (a wave
+// spans several rows: the bitmap words and offsets are per-lane loads) 2 rows; B = 128 .. 512 4
+// rows in the 64 registers of 8 waves per SIMD, as the dense step; B = 1024 (two float4 per lane
+// and row) 4 rows at 4 waves per SIMD -- the dense step's 2 rows at 8 waves, with the bitmap
+// arithmetic on top, spilled 6 registers; B >= 2048 as the dense step. 8 rows in flight at 4
+// waves per SIMD for B = 128 .. 1024 measured no faster at any density: below a
+// quarter of the tiles the step is bound by the instructions per row, not by bytes in flight.
+template<int B>
+constexpr int sparse_unroll() { return upols_cfg<B>::QT < 64 ? 2 : upols_cfg<B>::VPT >= 4 ? 1 : 4; }
+template<int B>
+constexpr int sparse_wgs() { return B < 1024 ? 8 : B == 1024 ? 4 : 2; }
+
+template<int B, bool FUSED, bool OLA>
+__global__ __launch_bounds__(256, sparse_wgs<B>()) void k_upols_sparse_step(
+    const float* __restrict__ in, int64_t ld_in, float* __restrict__ out, int64_t ld_out, float* __restrict__ prev,
+    const uint32_t* __restrict__ bits, const uint32_t* __restrict__ off, const int64_t* __restrict__ base,
+    const float4* __restrict__ val, cf* __restrict__ fdl, cf* __restrict__ part, int* __restrict__ arrivals,
+    const cf* __restrict__ twg, int P, int ring, int S, int rows, int w, int64_t cstride, int64_t pstride, int pc)
+{
+    __shared__ step_lds<B> L;
+    const int c = blockIdx.x / S, s = blockIdx.x - c * S;
+    const uint32_t* off_c = off + int64_t(c) * (P + 1);
+    // the channel's tiles and its FDL ring, each < 2 GiB (create_sparse)
+    const sparse_rows sp{bits + int64_t(c) * P * upols_cfg<B>::VPT, off_c,
+                         __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(val + base[c] * 8), 0,
+                                                           int(off_c[P]) * 128, 0x00020000),
+                         __builtin_amdgcn_make_buffer_rsrc(fdl + int64_t(c) * cstride, 0,
+                                                           int(int64_t(ring) * pstride * int64_t(sizeof(cf))), 0x00020000),
+                         int(pstride * int64_t(sizeof(cf)))};
+    (void)upols_step_wg<B, FUSED, OLA, false, sparse_unroll<B>(), false, sparse_rows>(
+        L, c, s, in, ld_in, out, ld_out, prev, nullptr, fdl, part, arrivals, twg, P, ring, S, rows, w, cstride, pstride,
+        pc, nullptr, sp);
+}
+
+// -- setup: bitmaps and counts, per-channel scan, channel bases, compaction ---------------------
+
+// One workgroup per filter row (c, p): lane t < NT looks at the 16 mask columns of tile t (tile 0
+// also at column B, the Nyquist bin packed beside DC); the wave ballots are the bitmap words.
+// off[c][p] = the row's popcount (scanned by k_sparse_scan); the kept columns add up in kept_cols.
+__global__ __launch_bounds__(256) void k_sparse_rows(const uint8_t* __restrict__ mask, int B, int P,
+                                                     uint32_t* __restrict__ bits, uint32_t* __restrict__ off,
+                                                     unsigned long long* __restrict__ kept_cols)
+{
+    __shared__ uint32_t wd[8];
+    __shared__ int cols;
+    const int tid = threadIdx.x, NT = B / kSparseTile, NW = sparse_words(B);
+    const int64_t r = blockIdx.x, c = r / P, p = r - c * P;
+    const uint8_t* m = mask + r * (int64_t(B) + 1);
+    if (tid == 0) cols = 0;
+    __syncthreads();
+    int n = 0;
+    if (tid < NT) {
+        for (int j = 0; j < kSparseTile; ++j) n += m[tid * kSparseTile + j] != 0;
+        if (tid == 0) n += m[B] != 0;
+    }
+    const unsigned long long bal = __ballot(n != 0);
+    if ((tid & 63) == 0) {
+        wd[2 * (tid >> 6)] = uint32_t(bal);
+        wd[2 * (tid >> 6) + 1] = uint32_t(bal >> 32);
+    }
+    if (n) atomicAdd(&cols, n);
+    __syncthreads();
+    if (tid < NW) bits[r * NW + tid] = wd[tid];
+    if (tid == 0) {
+        uint32_t k = 0;
+        for (int i = 0; i < NW; ++i) k += uint32_t(__popc(wd[i]));
+        off[c * (int64_t(P) + 1) + p] = k;
+        if (cols) atomicAdd(kept_cols, (unsigned long long)cols);
+    }
+}
+
+// One workgroup per channel: off[c][0..P) counts -> exclusive prefix sums, off[c][P] = the total.
+// Lane t scans the rows [t chunk, (t + 1) chunk); the 256 chunk sums are scanned by lane 0.
+__global__ __launch_bounds__(256) void k_sparse_scan(uint32_t* __restrict__ off, int P)
+{
+    __shared__ uint32_t sum[256];
+    const int tid = threadIdx.x;
+    uint32_t* o = off + int64_t(blockIdx.x) * (int64_t(P) + 1);
+    const int chunk = (P + 255) / 256, lo = min(P, tid * chunk), hi = min(P, lo + chunk);
+    uint32_t k = 0;
+    for (int p = lo; p < hi; ++p) k += o[p];
+    sum[tid] = k;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const uint32_t v = sum[i];
+            sum[i] = run;
+            run += v;
+        }
+        o[P] = run;
+    }
+    __syncthreads();
+    uint32_t run = sum[tid];
+    for (int p = lo; p < hi; ++p) {
+        const uint32_t v = o[p];
+        o[p] = run;
+        run += v;
+    }
+}
+
+// base[c] = channel c's first tile in the compacted values, base[C] = the total
+__global__ void k_sparse_base(const uint32_t* __restrict__ off, int C, int P, int64_t* __restrict__ base)
+{
+    if (blockIdx.x || threadIdx.x) return;
+    int64_t run = 0;
+    for (int c = 0; c < C; ++c) {
+        base[c] = run;
+        run += off[int64_t(c) * (int64_t(P) + 1) + P];
+    }
+    base[C] = run;
+}
+
+// One workgroup per filter row: the kept tiles of filter [C][P][B + 1] (reference layout), packed
+// (bin 0 = {DC, Nyquist}), the columns the mask drops as zero, DC and Nyquist each on its own.
+__global__ __launch_bounds__(256) void k_sparse_pack(const cf* __restrict__ filter, const uint8_t* __restrict__ mask,
+                                                     int B, int P, const uint32_t* __restrict__ bits,
+                                                     const uint32_t* __restrict__ off, const int64_t* __restrict__ base,
+                                                     cf* __restrict__ val)
+{
+    const int NW = sparse_words(B);
+    const int64_t r = blockIdx.x, c = r / P, p = r - c * P;
+    const cf* src = filter + r * (int64_t(B) + 1);
+    const uint8_t* m = mask + r * (int64_t(B) + 1);
+    const uint32_t* wd = bits + r * NW;
+    const int64_t row0 = base[c] + off[c * (int64_t(P) + 1) + p];
+    for (int k = threadIdx.x; k < B; k += 256) {
+        const int t = k / kSparseTile, word = t >> 5, bit = t & 31;
+        const uint32_t b = wd[word];
+        if (!((b >> bit) & 1u)) continue;
+        int idx = __popc(b & ((1u << bit) - 1u));
+        for (int i = 0; i < word; ++i) idx += __popc(wd[i]);
+        cf v;
+        if (k == 0) v = cf{m[0] ? src[0].x : 0.f, m[B] ? src[B].x : 0.f};
+        else v = m[k] ? src[k] : cf{0.f, 0.f};
+        val[(row0 + idx) * kSparseTile + (k & (kSparseTile - 1))] = v;
+    }
+}
+
+int sparse_alloc(upols_t* h)
+{
+    const size_t rows = size_t(h->C) * size_t(h->P);
+    if (dalloc(&h->sp_bits, rows * sparse_words(h->B) * sizeof(uint32_t)) ||
+        dalloc(&h->sp_off, (rows + h->C) * sizeof(uint32_t)) || dalloc(&h->sp_base, size_t(h->C + 2) * sizeof(int64_t)))
+        return NEO_HIP_ENOMEM;
+    // an empty filter until the first one is set: no tile kept, every offset zero
+    NEO_HIP_CHECK(hipMemsetAsync(h->sp_bits, 0, rows * sparse_words(h->B) * sizeof(uint32_t), h->stream));
+    NEO_HIP_CHECK(hipMemsetAsync(h->sp_off, 0, (rows + h->C) * sizeof(uint32_t), h->stream));
+    NEO_HIP_CHECK(hipMemsetAsync(h->sp_base, 0, size_t(h->C + 2) * sizeof(int64_t), h->stream));
+    return NEO_HIP_OK;
+}
+
+void sparse_free(upols_t* h)
+{
+    dfree(h->sp_bits);
+    dfree(h->sp_off);
+    dfree(h->sp_base);
+    dfree(h->sp_val);
+    h->sp_bits = h->sp_off = nullptr;
+    h->sp_base = nullptr;
+    h->sp_val = nullptr;
+}
+
+int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s)
+{
+    const int64_t rows = int64_t(h->C) * h->P;
+    if (rows > 0x7fffffff) return fail(NEO_HIP_EINVAL, "too many partitions");
+    // the caller joined every stream this handle's steps ran on: the old tiles are free to go
+    dfree(h->sp_val);
+    h->sp_val = nullptr;
+    h->sp_tiles = h->sp_bins = 0;
+    unsigned long long* cols = reinterpret_cast<unsigned long long*>(h->sp_base + h->C + 1);
+    NEO_HIP_CHECK(hipMemsetAsync(cols, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_sparse_rows, dim3(unsigned(rows)), dim3(256), 0, s, mask, h->B, h->P, h->sp_bits, h->sp_off, cols);
+    NEO_HIP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sparse_scan, dim3(unsigned(h->C)), dim3(256), 0, s, h->sp_off, h->P);
+    NEO_HIP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sparse_base, dim3(1), dim3(64), 0, s, h->sp_off, h->C, h->P, h->sp_base);
+    NEO_HIP_LAUNCH_CHECK();
+    int64_t tot[2] = {0, 0};  // kept tiles, kept columns: all that comes back to the host
+    NEO_HIP_CHECK(hipMemcpyAsync(tot, h->sp_base + h->C, sizeof tot, hipMemcpyDeviceToHost, s));
+    NEO_HIP_CHECK(hipStreamSynchronize(s));  // the handle's stream, never the device
+    h->sp_tiles = tot[0];
+    h->sp_bins = tot[1];
+    const double bytes = double(h->sp_tiles) * kSparseTile * sizeof(cf);
+    // filter rows read cacheable (the Infinity Cache budget of the dense step, in kept bytes)
+    h->pc = bytes <= kCacheBudgetBytes ? h->P : int(double(h->P) * kCacheBudgetBytes / bytes);
+    if (!h->sp_tiles) return NEO_HIP_OK;
+    if (int rc = dalloc(&h->sp_val, size_t(h->sp_tiles) * kSparseTile * sizeof(cf))) return rc;
+    hipLaunchKernelGGL(k_sparse_pack, dim3(unsigned(rows)), dim3(256), 0, s, filter, mask, h->B, h->P, h->sp_bits,
+                       h->sp_off, h->sp_base, h->sp_val);
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    upols_t::ev_group* ev = nullptr;
+    if (int rc = timing_begin(h, 2, &ev)) return rc;
+    if (int rc = timing_mark(ev, 0, s)) return rc;
+    const unsigned grid = unsigned(h->C) * unsigned(h->S);
+#define NEO_SPARSE_STEP(FU, OL)                                                                                       \
+    NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_sparse_step<BB, FU, OL>), dim3(grid), dim3(256), 0, s, in, ld_in, \
+                                                out, ld_out, h->prev, h->sp_bits, h->sp_off, h->sp_base,                 \
+                                                reinterpret_cast<const float4*>(h->sp_val), h->fdl, h->part,            \
+                                                h->arrivals, h->tw, h->P, h->ring, h->S, h->rows, h->wpos, h->cstride,  \
+                                                h->pstride, h->pc))
+    if (h->fused) {
+        if (h->ola) NEO_SPARSE_STEP(true, true) else NEO_SPARSE_STEP(true, false)
+    } else {
+        if (h->ola) NEO_SPARSE_STEP(false, true) else NEO_SPARSE_STEP(false, false)
+    }
+#undef NEO_SPARSE_STEP
+    NEO_HIP_LAUNCH_CHECK();
+    h->fdl_zero = false;
+    if (int rc = timing_mark(ev, 1, s)) return rc;
+    if (!h->fused)
+        if (int rc = launch_finish(h, out, ld_out, s)) return rc;
+    h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;  // fdl_index.hpp:35-37
+    return NEO_HIP_OK;
+}
+
+}  // namespace neo_hip

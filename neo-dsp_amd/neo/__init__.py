@@ -10,7 +10,9 @@ from . import fft
 from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_convolve, direct_convolve, fft_convolve,
                           host_register, host_unregister, memory_info, memory_trim, normalize_impulse, overlap_add, overlap_save, OverlapStage, UpolsGroup,
                           num_partitions, split_upola_convolver, split_upols_convolver, uniform_partition,
-                          upola_convolver, upola_convolver_v2, upols_convolver)
+                          upola_convolver, upola_convolver_v2, upols_convolver,
+                          SparseUpolsConvolver, sparse_convolve, sparse_plan, sparse_upola_convolver,
+                          sparse_upols_convolver)
 
 __version__ = "0.1.0"
 
@@ -36,6 +38,11 @@ __all__ = [
     "memory_info",
     "memory_trim",
     "dense_convolve",
+    "SparseUpolsConvolver",
+    "sparse_upols_convolver",
+    "sparse_upola_convolver",
+    "sparse_plan",
+    "sparse_convolve",
     "convolve",
     "fft_convolve",
     "direct_convolve",

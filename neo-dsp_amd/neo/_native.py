@@ -52,6 +52,10 @@ SIGNATURES = {
     "neo_hip_upols_set_batch": (_i, [_vp, _i]),
     "neo_hip_upols_batch_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "neo_hip_upols_create_ex": (_i, [_i, _i, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
+    "neo_hip_upols_create_sparse": (_i, [_i, _i, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
+    "neo_hip_upols_set_filter_sparse": (_i, [_vp, _vp, _vp, _i]),
+    "neo_hip_upols_sparse_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
+    "neo_hip_upols_sparse_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "neo_hip_upols_destroy": (_i, [_vp]),
     "neo_hip_upols_set_filter": (_i, [_vp, _vp, _i]),
     "neo_hip_upols_set_impulse": (_i, [_vp, _vp, _i64, _i, _i]),
@@ -116,7 +120,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 200  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 300  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -12,6 +12,10 @@ Python; extra/python/src/main.cpp:227-234 only lists the `upols` method enum):
   - upola_convolver_v2     dense_convolver.hpp:28 (overlap_add_convolver.hpp:20-136,
                            sub-block input)
   - dense_convolve         extra/plugin/src/dsp/DenseConvolution.hpp:39-70
+  - sparse_upols_convolver / sparse_upola_convolver
+                           src/neo/convolution/sparse_convolver.hpp:12-17 (sparse_filter.hpp:25-45;
+                           kept in 128-byte tiles of 16 bins here, include/neo_hip.h)
+  - sparse_convolve        extra/plugin/src/dsp/DenseConvolution.cpp:124-186 (the mask is the caller's)
 Everything runs on the GPU through libneo_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -39,6 +43,11 @@ __all__ = [
     "split_upola_convolver",
     "upola_convolver_v2",
     "dense_convolve",
+    "SparseUpolsConvolver",
+    "sparse_upols_convolver",
+    "sparse_upola_convolver",
+    "sparse_plan",
+    "sparse_convolve",
     "fft_convolve",
     "direct_convolve",
     "convolve",
@@ -824,6 +833,160 @@ def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, m
         out[:, lo:hi] = buf[:, : hi - lo]
     conv.close()
     return out
+
+
+def sparse_plan(mask, block_size: int) -> dict:
+    """The tile-compacted format of a sparse filter for `mask` ([C][P][B+1] or [P][B+1], true =
+    keep), on the host (neo_hip_upols_sparse_plan; no device needed): per row a bitmap of kept
+    128-byte tiles (16 packed bins; columns 0 and B both in tile 0) `tile_mask` [C][P][NW] uint32
+    and `row_off` [C][P+1], the exclusive prefix sum of the rows' kept tiles within a channel;
+    `kept_bins`, `kept_tiles` over all channels."""
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[2] != block_size + 1:
+        raise ValueError(f"mask must be [C][P][{block_size + 1}], got {m.shape}")
+    C, P, _ = m.shape
+    nw = max(1, block_size // 512)
+    tm = np.zeros((C, P, nw), dtype=np.uint32)
+    ro = np.zeros((C, P + 1), dtype=np.uint32)
+    kb, kt = ctypes.c_int64(), ctypes.c_int64()
+    _native.check(_native.load().neo_hip_upols_sparse_plan(_ptr(m), C, int(block_size), P, _ptr(tm), _ptr(ro),
+                                                           ctypes.byref(kb), ctypes.byref(kt)))
+    return {"tile_mask": tm, "row_off": ro, "kept_bins": kb.value, "kept_tiles": kt.value}
+
+
+class SparseUpolsConvolver(UpolsConvolver):
+    """C independent sparse UPOLS / UPOLA convolvers stepped together (neo_hip_upols_create_sparse):
+    only the filter bins a mask keeps take part, kept as 128-byte tiles of 16 packed bins; a block
+    step reads the kept tiles of the filter and of the FDL rows only. Results are those of the
+    dense convolver on the filter with the dropped columns zeroed. Of `options` only fused and
+    split_workgroups apply; there are no streaming levels, batched passes, offline windows or
+    latency mode (their setters raise), and set_impulse / the dense filter() form do not apply."""
+
+    def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
+                 options: dict | None = None):
+        methods = {"upols": 0, "upola": 1}
+        if method not in methods:
+            raise ValueError(f"method must be 'upols' or 'upola', got {method!r}")
+        opts = dict(self.OPTION_DEFAULTS)
+        for k, v in (options or {}).items():
+            if k not in ("fused", "split_workgroups"):
+                raise ValueError(f"sparse convolvers take the options fused and split_workgroups, got {k!r}")
+            opts[k] = int(v)
+        o = _native.UpolsOpts(**opts)
+        h = ctypes.c_void_p()
+        _native.check(_native.load().neo_hip_upols_create_sparse(int(channels), int(block_size), int(partitions),
+                                                                 int(device), methods[method], ctypes.byref(o),
+                                                                 ctypes.byref(h)))
+        self._h = h
+        self.channels, self.block_size, self.partitions, self.device = channels, block_size, partitions, device
+        self.method = method
+
+    def filter(self, partitions, mask) -> None:
+        """sparse_filter's filter(matrix, sparsity) for every channel: `partitions` [C][P][B+1]
+        complex64 and `mask` [C][P][B+1] (true = keep), host arrays or CUDA tensors (both on the
+        same side); resets FDL, window and write position."""
+        shape = (self.channels, self.partitions, self.block_size + 1)
+        lib = _native.load()
+        if _is_torch(partitions) and partitions.is_cuda:
+            import torch
+
+            m = mask if _is_torch(mask) else torch.as_tensor(np.asarray(mask))
+            m = (m != 0).to(device=partitions.device, dtype=torch.uint8).contiguous()
+            if partitions.dtype != torch.complex64 or not partitions.is_contiguous():
+                raise TypeError("filter takes a contiguous complex64 tensor")
+            if partitions.numel() != int(np.prod(shape)) or m.numel() != partitions.numel():
+                raise ValueError(f"filter and mask must be {shape}")
+            _producer_join(partitions)
+            torch.cuda.current_stream(partitions.device).synchronize()  # the mask made above
+            _native.check(lib.neo_hip_upols_set_filter_sparse(self._h, ctypes.c_void_p(partitions.data_ptr()),
+                                                              ctypes.c_void_p(m.data_ptr()), 1))
+            return
+        if _is_torch(partitions):
+            partitions = partitions.numpy()
+        if _is_torch(mask):
+            mask = mask.cpu().numpy()
+        H = np.ascontiguousarray(partitions, dtype=np.complex64)
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if H.ndim == 2:
+            H = H[None]
+        if m.ndim == 2:
+            m = m[None]
+        if H.shape != shape or m.shape != shape:
+            raise ValueError(f"filter shape {H.shape} / mask shape {m.shape} != {shape}")
+        _native.check(lib.neo_hip_upols_set_filter_sparse(self._h, _ptr(H), _ptr(m), 0))
+
+    def sparse_info(self) -> dict:
+        """The current filter's kept columns and kept 128-byte tiles over all channels, and the
+        device bytes (tiles, bitmaps, offsets) that stand in for a dense handle's filter buffer."""
+        kb, kt, fb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols_sparse_info(self._h, ctypes.byref(kb), ctypes.byref(kt),
+                                                               ctypes.byref(fb)))
+        return {"kept_bins": kb.value, "kept_tiles": kt.value, "filter_bytes": fb.value}
+
+
+class sparse_upols_convolver:
+    """Single-channel drop-in for sparse_upols_convolver<complex<float>> (sparse_convolver.hpp:
+    12-13): filter([P][B+1], sparsity) then __call__(block[B]) in place. `sparsity` is a bool
+    array [P][B+1] or a callable (row, col, value) -> bool, as sparse_filter::filter takes it
+    (sparse_filter.hpp:25-28, csr_matrix.hpp:32-34)."""
+
+    _method = "upols"
+
+    def __init__(self, device: int = 0):
+        self._impl = None
+        self._device = device
+
+    def filter(self, filt, sparsity) -> None:
+        H = np.ascontiguousarray(filt, dtype=np.complex64)
+        if H.ndim != 2:
+            raise ValueError("filter must be [P][B+1]")
+        P, bins = H.shape
+        if callable(sparsity):
+            mask = np.array([[bool(sparsity(r, c, H[r, c])) for c in range(bins)] for r in range(P)], dtype=bool)
+        else:
+            mask = np.asarray(sparsity) != 0
+        if mask.shape != H.shape:
+            raise ValueError(f"sparsity shape {mask.shape} != filter shape {H.shape}")
+        impl = self._impl
+        if impl is None or (impl.partitions, impl.block_size) != (P, bins - 1):
+            impl = SparseUpolsConvolver(1, bins - 1, P, self._device, method=self._method)
+        impl.filter(H[None], mask[None])
+        self._impl = impl
+
+    def __call__(self, block):
+        if self._impl is None:
+            raise RuntimeError("filter() must be called first")
+        return self._impl(block)
+
+
+class sparse_upola_convolver(sparse_upols_convolver):
+    """Single-channel drop-in for sparse_upola_convolver<complex<float>> (sparse_convolver.hpp:16-17)."""
+
+    _method = "upola"
+
+
+def sparse_convolve(signal, impulse_response, block_size: int, mask, method: str = "upola", device: int = 0,
+                    options: dict | None = None) -> np.ndarray:
+    """The plugin's sparse_convolve loop (DenseConvolution.cpp:124-186): normalize the IR matrix,
+    partition it, keep the filter bins `mask` ([C][P][B+1], true = keep; the plugin's A-weighted
+    threshold is the caller's to apply) and run every block (tail zero-padded) through
+    sparse_upola_convolver (or sparse_upols_convolver) per channel; output truncated to N."""
+    sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
+    ir = np.array(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)), order="C")
+    C, N = sig.shape
+    if ir.shape[0] != C:
+        raise ValueError("signal and impulse response channel counts differ")
+    parts = uniform_partition(normalize_impulse(ir, device), block_size, device)
+    conv = SparseUpolsConvolver(C, block_size, parts.shape[1], device, method=method, options=options)
+    conv.filter(parts, mask)
+    nb = -(-N // block_size)
+    buf = np.zeros((C, nb * block_size), dtype=np.float32)
+    buf[:, :N] = sig
+    conv.process(buf)
+    conv.close()
+    return buf[:, :N].copy()
 
 
 def _one_shot(name, signal, patch, device):
