@@ -190,7 +190,10 @@ NEO_HIP_API int neo_hip_upols_set_impulse(neo_hip_upols* h, const float* ir, int
  * polling the stream. Device memory: same as process_device on `stream`. */
 NEO_HIP_API int neo_hip_upols_process(neo_hip_upols* h, float* io, int io_is_device, void* stream);
 /* one block, device pointers, channel c at in + c*ld_in / out + c*ld_out
- * (in == out allowed); asynchronous on `stream` (NULL = HIP null stream). */
+ * (in == out allowed); asynchronous on `stream` (NULL = HIP null stream). Both pointers
+ * 16-byte aligned, ld_in and ld_out multiples of 4 and >= B (they may differ); anything else is
+ * EINVAL and leaves the state as it was. The call reads [c*ld_in, c*ld_in + B) of every channel
+ * and writes [c*ld_out, c*ld_out + B), nothing else; `in` is left as it was unless it is `out`. */
 NEO_HIP_API int neo_hip_upols_process_device(neo_hip_upols* h, const float* in, int64_t ld_in, float* out,
                                              int64_t ld_out, void* stream);
 /* nblocks consecutive blocks: channel c samples at in + c*ld + t*B (16-byte aligned, ld
@@ -221,7 +224,12 @@ NEO_HIP_API int neo_hip_upols_get_offline(neo_hip_upols* h, int* enabled, int* s
  * (in == out allowed), host (synchronous) or device (asynchronous on `stream`) memory.
  * upola_convolver_v2 handles accept any count, split at block boundaries like
  * overlap_add_convolver::operator() (:80-134); upols / upola handles need a multiple
- * of the block (the reference's operator() takes exactly one block). */
+ * of the block (the reference's operator() takes exactly one block). Device memory of upols /
+ * upola handles, and of any handle in latency mode: both pointers 16-byte aligned, ld_in and
+ * ld_out multiples of 4, as for process_device; upola_convolver_v2 handles take any (4-byte)
+ * alignment and any ld >= num_samples, and run batched passes and the UPOLA launch pair only
+ * where the alignment allows. Host memory: any alignment (it is staged). ld_in and ld_out may
+ * differ; a refused call (EINVAL) leaves the state as it was. */
 NEO_HIP_API int neo_hip_upols_process_samples(neo_hip_upols* h, const float* in, int64_t ld_in, float* out,
                                               int64_t ld_out, int64_t num_samples, int is_device, void* stream);
 NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h);

@@ -334,6 +334,14 @@ class UpolsConvolver:
                                                                   ctypes.c_void_p(out_ptr), int(ld), int(nblocks),
                                                                   ctypes.c_void_p(stream)))
 
+    def process_samples_ptr(self, in_ptr: int, ld_in: int, out_ptr: int, ld_out: int, n: int, is_device: bool,
+                            stream: int = 0) -> None:
+        """n samples per channel through neo_hip_upols_process_samples: channel c at
+        in_ptr + 4*c*ld_in / out_ptr + 4*c*ld_out, host (synchronous) or device pointers."""
+        _native.check(_native.load().neo_hip_upols_process_samples(self._h, ctypes.c_void_p(in_ptr), int(ld_in),
+                                                                   ctypes.c_void_p(out_ptr), int(ld_out), int(n),
+                                                                   int(bool(is_device)), ctypes.c_void_p(stream)))
+
     def set_batch(self, enable: bool) -> None:
         """process_blocks: T blocks per MAC pass (default) or one block per pass."""
         _native.check(_native.load().neo_hip_upols_set_batch(self._h, int(enable)))
@@ -526,6 +534,12 @@ class UpolsMultiConvolver:
         n = x.shape[1]
         _native.check(_native.load().neo_hip_upols_multi_process_samples(self._h, _ptr(x), n, _ptr(y), n, n))
         return y
+
+    def process_samples_ptr(self, in_ptr: int, ld_in: int, out_ptr: int, ld_out: int, n: int) -> None:
+        """n samples per channel through neo_hip_upols_multi_process_samples: channel c at
+        in_ptr + 4*c*ld_in / out_ptr + 4*c*ld_out, host pointers (synchronous)."""
+        _native.check(_native.load().neo_hip_upols_multi_process_samples(self._h, ctypes.c_void_p(in_ptr), int(ld_in),
+                                                                         ctypes.c_void_p(out_ptr), int(ld_out), int(n)))
 
     def reset(self) -> None:
         _native.check(_native.load().neo_hip_upols_multi_reset(self._h))

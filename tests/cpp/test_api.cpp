@@ -9,10 +9,14 @@
 
 #include "../../oracle/neo_oracle.h"
 
+#include <hip/hip_runtime_api.h>
+
 #include <cmath>
 #include <complex>
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <iterator>
 #include <vector>
 
@@ -430,6 +434,73 @@ static void test_latency_mode_and_paced()
     REQUIRE(same);
 }
 
+// process_device with separate padded device buffers (include/neo_hip.h: channel c at
+// in + c*ld_in / out + c*ld_out), the layout of tests/test_io_contract_gpu.py: arenas of C + 2 rows
+// holding a sentinel, the channels in rows 1..C, rows 0 and C + 1 guards (a stray access of up to a
+// channel stride stays inside the allocation). The input arena is left as it was, nothing outside
+// the output's [c*ld_out, c*ld_out + n) is written, and the payload equals the in-place run's on a
+// contiguous buffer bit for bit (strides move addresses only).
+static void test_process_device_separate_padded_buffers()
+{
+    std::size_t const C = 3, B = 128, P = 9, nb = 12, n = B * nb, ld_in = n + 36, ld_out = n + 4;
+    std::uint32_t const in_fill = 0x7FC0BEEFU, out_fill = 0x7FD1CAFEU;  // quiet NaNs with payloads
+    auto filt = cnoise(700, C * P * (B + 1));
+    for (auto& v : filt) v *= 0.05F;
+    auto const sig = rnoise(701, C * n);
+    auto device = [](std::size_t words, void const* init) {
+        void* p = nullptr;
+        REQUIRE(hipMalloc(&p, words * 4) == hipSuccess);
+        REQUIRE(hipMemcpy(p, init, words * 4, hipMemcpyHostToDevice) == hipSuccess);
+        return static_cast<float*>(p);
+    };
+    // A: in place on a contiguous [C][n] buffer
+    std::vector<float> A(C * n);
+    {
+        neo::convolution::upols_multichannel conv{C, B, P};
+        conv.filter(filt.data());
+        float* io = device(C * n, sig.data());
+        for (std::size_t t = 0; t < nb; ++t) conv.process_device(io + t * B, n, io + t * B, n);
+        REQUIRE(hipStreamSynchronize(nullptr) == hipSuccess);
+        REQUIRE(hipMemcpy(A.data(), io, C * n * 4, hipMemcpyDeviceToHost) == hipSuccess);
+        REQUIRE(hipFree(io) == hipSuccess);
+    }
+    double peak = 0;
+    for (float v : A) peak = std::isfinite(v) ? std::max(peak, double(std::abs(v))) : 1e30;
+    REQUIRE(peak > 1e-3 && peak < 1e3);  // a convolution came out, not the input or a poisoned sum
+    // B: from the input arena into the output arena
+    std::vector<std::uint32_t> ia((C + 2) * ld_in, in_fill), oa((C + 2) * ld_out, out_fill);
+    for (std::size_t c = 0; c < C; ++c) std::memcpy(&ia[(c + 1) * ld_in], &sig[c * n], n * 4);
+    auto const ia_before = ia;
+    {
+        neo::convolution::upols_multichannel conv{C, B, P};
+        conv.filter(filt.data());
+        float* in = device(ia.size(), ia.data());
+        float* out = device(oa.size(), oa.data());
+        for (std::size_t t = 0; t < nb; ++t)
+            conv.process_device(in + ld_in + t * B, ld_in, out + ld_out + t * B, ld_out);
+        REQUIRE(hipStreamSynchronize(nullptr) == hipSuccess);
+        REQUIRE(hipMemcpy(ia.data(), in, ia.size() * 4, hipMemcpyDeviceToHost) == hipSuccess);
+        REQUIRE(hipMemcpy(oa.data(), out, oa.size() * 4, hipMemcpyDeviceToHost) == hipSuccess);
+        REQUIRE(hipFree(in) == hipSuccess);
+        REQUIRE(hipFree(out) == hipSuccess);
+    }
+    REQUIRE(ia == ia_before);  // (a) the input is left as it was
+    std::size_t stray = 0, differ = 0;
+    for (std::size_t r = 0; r < C + 2; ++r)
+        for (std::size_t j = 0; j < ld_out; ++j) {
+            std::uint32_t const w = oa[r * ld_out + j];
+            if (r >= 1 && r <= C && j < n) {
+                std::uint32_t a = 0;
+                std::memcpy(&a, &A[(r - 1) * n + j], 4);
+                differ += w != a;
+            } else {
+                stray += w != out_fill;
+            }
+        }
+    REQUIRE(stray == 0);   // (b) nothing outside the output payload is written
+    REQUIRE(differ == 0);  // (c) the payload is the in-place run's
+}
+
 int main()
 {
     test_fdl_index();
@@ -451,6 +522,7 @@ int main()
     test_stft();
     test_overlap_stage<neo::convolution::overlap_save<cf>, 0>();
     test_overlap_stage<neo::convolution::overlap_add<cf>, 1>();
+    test_process_device_separate_padded_buffers();
     test_latency_mode_and_paced();
     std::printf(failures ? "FAILED (%d)\n" : "all C++ API tests passed\n", failures);
     return failures ? 1 : 0;
