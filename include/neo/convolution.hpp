@@ -15,6 +15,7 @@
 
 #include <neo/fft.hpp>
 #include <neo/hip/detail.hpp>
+#include <neo/perceptual.hpp>
 
 #include <algorithm>
 #include <complex>
@@ -22,6 +23,8 @@
 #include <cstddef>
 #include <memory>
 #include <stdexcept>
+#include <string>
+#include <type_traits>
 #include <map>
 #include <mutex>
 #include <array>
@@ -147,6 +150,31 @@ inline constexpr upola_v2_tag upola_v2{};
 struct sparse_tag {};
 inline constexpr sparse_tag sparse{};
 
+/// The plugin's sparsity rule (sparse_convolve, extra/plugin/src/dsp/DenseConvolution.cpp:110-170;
+/// neo_hip_perceptual in neo_hip.h): keep a bin iff its level relative to its channel's strongest
+/// bin plus its column's weight exceeds threshold_db. Argument errors throw std::invalid_argument
+/// where it is used (the block size is known there): validate(block_size).
+struct perceptual_sparsity {
+    double sample_rate{48000.0};      ///< Hz, > 0
+    float threshold_db{-40.0F};       ///< finite; the plugin passes -dynamicRange
+    int low_bins_to_keep{0};          ///< 0 .. B: columns below it are always kept
+    int weighting{1};                 ///< 1 = A-weighting, 0 = none
+
+    [[nodiscard]] auto c_struct() const noexcept -> neo_hip_perceptual
+    {
+        return neo_hip_perceptual{sample_rate, threshold_db, low_bins_to_keep, weighting};
+    }
+
+    /// throws std::invalid_argument naming what is wrong for blocks of block_size
+    auto validate(std::size_t block_size) const -> void
+    {
+        auto const p = c_struct();
+        std::vector<float> w(std::min<std::size_t>(block_size, 4096) + 1);  // a larger block is refused
+        if (neo_hip_perceptual_weights(block_size <= 4096 ? int(block_size) : -1, &p, w.data()) != NEO_HIP_OK)
+            throw std::invalid_argument{std::string{"neo_hip: "} + neo_hip_last_error()};
+    }
+};
+
 namespace detail {
 struct upols_deleter {
     void operator()(neo_hip_upols* h) const noexcept { neo_hip_upols_destroy(h); }
@@ -204,6 +232,22 @@ struct upols_multichannel {
     auto filter_sparse(std::complex<float> const* partitions, std::uint8_t const* mask) -> void
     {
         neo::hip::check(neo_hip_upols_set_filter_sparse(_h.get(), partitions, mask, 0));
+    }
+    /// sparse handles: filter [C][P][B+1] thinned by the plugin's rule, the mask made on the device
+    auto filter_perceptual(std::complex<float> const* partitions, perceptual_sparsity const& sparsity) -> void
+    {
+        sparsity.validate(_B);
+        auto const p = sparsity.c_struct();
+        neo::hip::check(neo_hip_upols_set_filter_perceptual(_h.get(), partitions, &p, 0));
+    }
+    /// sparse handles: normalize_impulse (optional), uniform_partition, mask and tiles of
+    /// ir [C][length], all on the GPU
+    auto impulse_perceptual(float const* ir, std::size_t length, perceptual_sparsity const& sparsity,
+                            bool normalize = true) -> void
+    {
+        sparsity.validate(_B);
+        auto const p = sparsity.c_struct();
+        neo::hip::check(neo_hip_upols_set_impulse_perceptual(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, &p, 0));
     }
     /// sparse handles: kept columns and kept 128-byte tiles of the current filter
     [[nodiscard]] auto sparse_kept() const -> std::pair<std::int64_t, std::int64_t>
@@ -395,7 +439,7 @@ struct hip_sparse_upols_convolver {
     hip_sparse_upols_convolver() = default;
 
     template<typename InMat, typename Sparsity>
-        requires neo::hip::detail::matrix_like<InMat>
+        requires(neo::hip::detail::matrix_like<InMat> && !std::same_as<std::remove_cvref_t<Sparsity>, perceptual_sparsity>)
     auto filter(InMat filter, Sparsity&& sparsity) -> void
     {
         auto const P = std::size_t(filter.extent(0)), bins = std::size_t(filter.extent(1));
@@ -406,6 +450,22 @@ struct hip_sparse_upols_convolver {
         if (!_impl || _impl->partitions() != P || _impl->block_size() != bins - 1)
             _impl = std::make_unique<upols_multichannel>(sparse, 1, bins - 1, P, neo::hip::detail::default_device(), M);
         _impl->filter_sparse(h.data(), mask.data());
+        _block.resize(bins - 1);
+    }
+
+    /// the plugin's rule instead of a callable: the mask is made on the device from the filter
+    template<typename InMat>
+        requires neo::hip::detail::matrix_like<InMat>
+    auto filter(InMat filter, perceptual_sparsity const& sparsity) -> void
+    {
+        auto const P = std::size_t(filter.extent(0)), bins = std::size_t(filter.extent(1));
+        sparsity.validate(bins - 1);
+        std::vector<Complex> h(P * bins);
+        for (std::size_t p = 0; p < P; ++p)
+            for (std::size_t k = 0; k < bins; ++k) h[p * bins + k] = Complex(neo::hip::detail::at(filter, p, k));
+        if (!_impl || _impl->partitions() != P || _impl->block_size() != bins - 1)
+            _impl = std::make_unique<upols_multichannel>(sparse, 1, bins - 1, P, neo::hip::detail::default_device(), M);
+        _impl->filter_perceptual(h.data(), sparsity);
         _block.resize(bins - 1);
     }
 

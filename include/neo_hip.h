@@ -55,8 +55,9 @@ typedef struct neo_hip_upols neo_hip_upols;
 /* -- library ------------------------------------------------------------ */
 /* ABI version of this header. neo_hip_upols_opts grows with it (0.1.0: 6 ints; 0.2.0: the 10
  * below), so a caller checks neo_hip_version() == NEO_HIP_VERSION before passing one.
- * 0.3.0: the sparse convolvers (neo_hip_upols_create_sparse and what goes with it). */
-#define NEO_HIP_VERSION 300 /* 0.3.0 */
+ * 0.3.0: the sparse convolvers (neo_hip_upols_create_sparse and what goes with it).
+ * 0.4.0: the perceptual sparsity predicate (neo_hip_perceptual_* and the two handle calls). */
+#define NEO_HIP_VERSION 400 /* 0.4.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -160,7 +161,8 @@ NEO_HIP_API int neo_hip_upols_create_ex(int channels, int block, int partitions,
  * the dense plain step's on the zeroed filter bit for bit, up to the sign of zero). method 2
  * (sub-block input) is EINVAL. On a sparse handle process, process_device, process_blocks (one
  * block per pass), process_samples (multiples of B), reset, info, destroy and the timing calls
- * work; set_filter and set_impulse (it takes set_filter_sparse), set_ahead(1), set_offline(1),
+ * work; set_filter and set_impulse (it takes set_filter_sparse, set_filter_perceptual or
+ * set_impulse_perceptual), set_ahead(1), set_offline(1),
  * set_batch(1), set_persistent(1) and set_paced(1 / 2) return EINVAL and name the reason, and the
  * getters report off. Groups and the multi-device convolver take no sparse members. */
 NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partitions, int device, int method,
@@ -176,6 +178,51 @@ NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, 
  * mask [C][P][B+1] -> tile_mask [C][P][NW], row_off [C][P+1], kept columns, kept tiles. */
 NEO_HIP_API int neo_hip_upols_sparse_plan(const uint8_t* mask, int channels, int block, int partitions,
                                           uint32_t* tile_mask, uint32_t* row_off, int64_t* kept_bins, int64_t* kept_tiles);
+/* -- Perceptual sparsity (the plugin's sparse_convolve threshold) -------------------
+ * Which bins of a filter [C][P][B+1] (uniform_partition layout) a sparse handle keeps, as the
+ * plugin decides it (extra/plugin/src/dsp/DenseConvolution.cpp:110-170; src/neo/unit/decibel.hpp,
+ * src/neo/math/a_weighting.hpp), on the device:
+ *   weights   w[k] = 100 for k < low_bins_to_keep; otherwise 0 (weighting 0) or the A-weighting in
+ *             dB at f = k sample_rate / (2 B) (weighting 1; A(0) = -inf, so DC is dropped unless
+ *             low_bins_to_keep >= 1). Computed in double on the host, rounded to float once.
+ *   scale     per CHANNEL: 1 / max over p, k of re^2 + im^2 (float)
+ *   level     x = (re^2 + im^2) scale; dB = max(-144, 20 log10 x) / 2 + w[k] for x > 0, else
+ *             -72 + w[k] (zero bins, and every bin of an all-zero channel)
+ *   keep      dB > threshold_db
+ * Unweighted, a threshold below -72 therefore keeps every bin, zeros included.
+ * The histograms count per channel the columns (hist_bins) and the 16-column tiles of the sparse
+ * format (hist_tiles; a tile's level is the maximum over its columns, column B in tile 0) by level:
+ * bucket j = min(143, floor(max(0, -dB))), [C][144] each. The tiles of channel c that an integer
+ * threshold -k (1 <= k <= 143) keeps are the sum of hist_tiles[c][j] over j < k. threshold_db
+ * plays no part in weights and histograms (it must be finite all the same). */
+typedef struct neo_hip_perceptual {
+    double sample_rate;   /* Hz, > 0 */
+    float threshold_db;   /* finite; the plugin passes -dynamicRange, -10 .. -90 */
+    int low_bins_to_keep; /* 0 .. B; columns below it are always kept */
+    int weighting;        /* 0 = none, 1 = A-weighting */
+} neo_hip_perceptual;
+/* Every call below checks its arguments before a device is touched (EINVAL names the reason). */
+NEO_HIP_API int neo_hip_perceptual_weights(int block, const neo_hip_perceptual* p, float* weights /* [B+1] */);
+/* the definition, on the host (csrc/perceptual_plan.hpp; no device needed) */
+NEO_HIP_API int neo_hip_perceptual_mask_host(const void* filter, int channels, int block, int partitions,
+                                             const neo_hip_perceptual* p, uint8_t* mask);
+NEO_HIP_API int neo_hip_perceptual_hist_host(const void* filter, int channels, int block, int partitions,
+                                             const neo_hip_perceptual* p, int64_t* hist_bins, int64_t* hist_tiles);
+/* the same on the device: filter and mask both host or both device memory; the histograms are
+ * always host memory. Synchronous (one of the library's streams, never the device). */
+NEO_HIP_API int neo_hip_perceptual_mask(const void* filter, int channels, int block, int partitions,
+                                        const neo_hip_perceptual* p, uint8_t* mask, int is_device, int device);
+NEO_HIP_API int neo_hip_perceptual_histogram(const void* filter, int channels, int block, int partitions,
+                                             const neo_hip_perceptual* p, int64_t* hist_bins, int64_t* hist_tiles,
+                                             int is_device, int device);
+/* Sparse handles only: set_filter_sparse with the mask made on the device from `filter`
+ * [C][P][B+1] (host or device memory), and the whole setup from an impulse response ir [C][length]
+ * (normalize_impulse if `normalize`, uniform_partition, mask, tiles; all on the device, on the
+ * handle's stream). Both reset all state, like filter(); a refused call leaves the handle as it was. */
+NEO_HIP_API int neo_hip_upols_set_filter_perceptual(neo_hip_upols* h, const void* filter, const neo_hip_perceptual* p,
+                                                    int is_device);
+NEO_HIP_API int neo_hip_upols_set_impulse_perceptual(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                                     const neo_hip_perceptual* p, int is_device);
 NEO_HIP_API int neo_hip_upols_destroy(neo_hip_upols* h);
 /* filter [C][P][B+1] complex (uniform_partition layout), host or device memory;
  * like uniform_partitioned_convolver::filter() it also resets all state. */

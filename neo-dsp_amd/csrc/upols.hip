@@ -31,6 +31,7 @@
 // and normalization. upols_device.hpp / upols_handle.hpp: what they share.
 #include "upols_device.hpp"
 #include "upols_handle.hpp"
+#include "perceptual_plan.hpp"
 #include "sparse_plan.hpp"
 #include "upols_step.hpp"
 
@@ -757,6 +758,84 @@ NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* fi
     if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
     dfree(tmp);  // the stream was joined above
     dfree(tmpm);
+    return rc;
+}
+
+// The perceptual forms: the mask is made on the device (perceptual.hip) from spectra that are
+// already there, then sparse_set_filter runs unchanged. Temporaries are pooled and go back before
+// the call returns; every wait is on the handle's stream.
+NEO_HIP_API int neo_hip_upols_set_filter_perceptual(neo_hip_upols* h, const void* filter, const neo_hip_perceptual* pp,
+                                                    int is_device)
+{
+    if (!h || !filter || !pp) return fail(NEO_HIP_EINVAL, "set_filter_perceptual: null handle, filter or parameters");
+    if (!h->sparse)
+        return fail(NEO_HIP_EINVAL, "set_filter_perceptual: not a sparse handle (neo_hip_upols_create_sparse)");
+    if (const char* why = perceptual_check(h->B, pp)) return fail(NEO_HIP_EINVAL, "set_filter_perceptual: %s", why);
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device filter's producer)
+    std::vector<float> w(size_t(h->B) + 1);
+    perceptual_weights(h->B, pp, w.data());
+    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
+    const cf* src = static_cast<const cf*>(filter);
+    cf* tmpf = nullptr;
+    uint8_t* mask = nullptr;
+    float* tmp = nullptr;
+    int rc = NEO_HIP_OK;
+    if (dalloc(&mask, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+    if (!rc && !is_device) {
+        if (dalloc(&tmpf, n * sizeof(cf))) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+        else if (hipMemcpyAsync(tmpf, filter, n * sizeof(cf), hipMemcpyHostToDevice, h->stream) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
+        src = tmpf;
+    }
+    if (!rc) rc = perceptual_mask_device(src, h->C, h->B, h->P, pp, w.data(), mask, &tmp, h->stream);
+    if (!rc) rc = sparse_set_filter(h, src, mask, h->stream);
+    if (!rc) rc = reset_state(h, h->stream);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(tmp);  // the stream was joined above
+    dfree(tmpf);
+    dfree(mask);
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_upols_set_impulse_perceptual(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                                     const neo_hip_perceptual* pp, int is_device)
+{
+    if (!h || !ir || !pp || length < 1)
+        return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: null handle, ir or parameters, or empty impulse");
+    if (!h->sparse)
+        return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: not a sparse handle (neo_hip_upols_create_sparse)");
+    if (const char* why = perceptual_check(h->B, pp)) return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: %s", why);
+    if (partitions_for(length, h->B) != h->P)
+        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
+                    (long long)partitions_for(length, h->B), h->P);
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device IR's producer)
+    std::vector<float> w(size_t(h->B) + 1);
+    perceptual_weights(h->B, pp, w.data());
+    const size_t bytes = size_t(h->C) * size_t(length) * sizeof(float);
+    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
+    float* d = nullptr;
+    cf* parts = nullptr;
+    uint8_t* mask = nullptr;
+    float* tmp = nullptr;
+    int rc = NEO_HIP_OK;
+    if (dalloc(&d, bytes) || dalloc(&parts, n * sizeof(cf)) || dalloc(&mask, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+    else if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream) !=
+             hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
+    if (!rc && normalize) rc = normalize_device(d, h->C, length, h->stream);
+    if (!rc) rc = partition_device(d, h->C, length, h->B, false, parts, h->tw, h->stream);
+    if (!rc) rc = perceptual_mask_device(parts, h->C, h->B, h->P, pp, w.data(), mask, &tmp, h->stream);
+    if (!rc) rc = sparse_set_filter(h, parts, mask, h->stream);
+    if (!rc) rc = reset_state(h, h->stream);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(tmp);  // the stream was joined above
+    dfree(d);
+    dfree(parts);
+    dfree(mask);
     return rc;
 }
 

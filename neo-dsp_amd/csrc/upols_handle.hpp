@@ -342,6 +342,10 @@ int sparse_alloc(upols_t* h);
 void sparse_free(upols_t* h);
 int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s);
 int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
+// perceptual.hip: mask [C][P][B + 1] of the perceptual predicate (perceptual_plan.hpp) for a device
+// filter, on s. *tmp (pooled) and the host weights [B + 1] stay alive until s is joined.
+int perceptual_mask_device(const cf* filter, int C, int B, int P, const neo_hip_perceptual* pp, const float* weights,
+                           uint8_t* mask, float** tmp, hipStream_t s);
 // upols.hip: the unfused step's second launch (k_upols_finish: slabs summed in order, c2r)
 int launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s);
 // upols_batch.hip: T whole blocks in one pass over the filter and the FDL

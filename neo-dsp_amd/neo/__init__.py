@@ -12,7 +12,9 @@ from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_c
                           num_partitions, split_upola_convolver, split_upols_convolver, uniform_partition,
                           upola_convolver, upola_convolver_v2, upols_convolver,
                           SparseUpolsConvolver, sparse_convolve, sparse_plan, sparse_upola_convolver,
-                          sparse_upols_convolver)
+                          sparse_upols_convolver, PerceptualSparsity, a_weighting, amplitude_to_db, perceptual_histogram,
+                          perceptual_histogram_host, perceptual_mask, perceptual_mask_host, perceptual_weights,
+                          threshold_for_tile_density, tile_density_curve)
 
 __version__ = "0.1.0"
 
@@ -43,6 +45,16 @@ __all__ = [
     "sparse_upola_convolver",
     "sparse_plan",
     "sparse_convolve",
+    "a_weighting",
+    "amplitude_to_db",
+    "PerceptualSparsity",
+    "perceptual_weights",
+    "perceptual_mask",
+    "perceptual_mask_host",
+    "perceptual_histogram",
+    "perceptual_histogram_host",
+    "tile_density_curve",
+    "threshold_for_tile_density",
     "convolve",
     "fft_convolve",
     "direct_convolve",

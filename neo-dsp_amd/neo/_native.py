@@ -30,6 +30,12 @@ class UpolsOpts(ctypes.Structure):
                 ("far_phase2", ctypes.c_int)]
 
 
+class Perceptual(ctypes.Structure):
+    """neo_hip_perceptual (include/neo_hip.h)."""
+    _fields_ = [("sample_rate", ctypes.c_double), ("threshold_db", ctypes.c_float),
+                ("low_bins_to_keep", ctypes.c_int), ("weighting", ctypes.c_int)]
+
+
 # every symbol declared in include/neo_hip.h: (name, restype, argtypes)
 _vp, _i, _i64, _fp = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_float)
 SIGNATURES = {
@@ -56,6 +62,13 @@ SIGNATURES = {
     "neo_hip_upols_set_filter_sparse": (_i, [_vp, _vp, _vp, _i]),
     "neo_hip_upols_sparse_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
     "neo_hip_upols_sparse_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "neo_hip_perceptual_weights": (_i, [_i, _vp, _vp]),
+    "neo_hip_perceptual_mask_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "neo_hip_perceptual_hist_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "neo_hip_perceptual_mask": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i]),
+    "neo_hip_perceptual_histogram": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i]),
+    "neo_hip_upols_set_filter_perceptual": (_i, [_vp, _vp, _vp, _i]),
+    "neo_hip_upols_set_impulse_perceptual": (_i, [_vp, _vp, _i64, _i, _vp, _i]),
     "neo_hip_upols_destroy": (_i, [_vp]),
     "neo_hip_upols_set_filter": (_i, [_vp, _vp, _i]),
     "neo_hip_upols_set_impulse": (_i, [_vp, _vp, _i64, _i, _i]),
@@ -120,7 +133,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 300  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 400  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -15,7 +15,9 @@ Python; extra/python/src/main.cpp:227-234 only lists the `upols` method enum):
   - sparse_upols_convolver / sparse_upola_convolver
                            src/neo/convolution/sparse_convolver.hpp:12-17 (sparse_filter.hpp:25-45;
                            kept in 128-byte tiles of 16 bins here, include/neo_hip.h)
-  - sparse_convolve        extra/plugin/src/dsp/DenseConvolution.cpp:124-186 (the mask is the caller's)
+  - sparse_convolve        extra/plugin/src/dsp/DenseConvolution.cpp:124-186 (a mask of the caller's, or
+                           the plugin's A-weighted threshold: PerceptualSparsity, perceptual_mask,
+                           perceptual_histogram; a_weighting, amplitude_to_db as main.cpp:260-267)
 Everything runs on the GPU through libneo_hip.so; there is no CPU fallback.
 """
 from __future__ import annotations
@@ -48,6 +50,16 @@ __all__ = [
     "sparse_upola_convolver",
     "sparse_plan",
     "sparse_convolve",
+    "a_weighting",
+    "amplitude_to_db",
+    "PerceptualSparsity",
+    "perceptual_weights",
+    "perceptual_mask",
+    "perceptual_mask_host",
+    "perceptual_histogram",
+    "perceptual_histogram_host",
+    "tile_density_curve",
+    "threshold_for_tile_density",
     "fft_convolve",
     "direct_convolve",
     "convolve",
@@ -870,13 +882,196 @@ def sparse_plan(mask, block_size: int) -> dict:
     return {"tile_mask": tm, "row_off": ro, "kept_bins": kb.value, "kept_tiles": kt.value}
 
 
+def a_weighting(frequency):
+    """neo::a_weighting (src/neo/math/a_weighting.hpp; extra/python/src/main.cpp:260-263): the
+    A-weighting in dB at `frequency` Hz, vectorised, in the input's float dtype (float64 for
+    anything that is not float32)."""
+    f = np.asarray(frequency)
+    dt = np.float32 if f.dtype == np.float32 else np.float64
+    f = f.astype(dt, copy=False)
+    c = np.array([12194.217, 20.598997, 107.65265, 737.86223], dtype=dt) ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        f2 = f * f
+        out = dt(2) + dt(20) * (np.log10(c[0]) + dt(2) * np.log10(f2) - np.log10(f2 + c[0]) - np.log10(f2 + c[1])
+                                - dt(0.5) * np.log10(f2 + c[2]) - dt(0.5) * np.log10(f2 + c[3]))
+    return out.astype(dt, copy=False) if out.ndim else dt(out)
+
+
+def amplitude_to_db(gain, infinity=-144.0):
+    """neo::amplitude_to_db (src/neo/unit/decibel.hpp; main.cpp:264-267): 20 log10(gain), floored
+    at `infinity`, which is also the value for gain <= 0; vectorised, in the input's float dtype."""
+    g = np.asarray(gain)
+    dt = np.float32 if g.dtype == np.float32 else np.float64
+    g = g.astype(dt, copy=False)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        db = np.maximum(dt(infinity), dt(20) * np.log10(g))
+    out = np.where(g <= 0, dt(infinity), db).astype(dt, copy=False)
+    return out if out.ndim else dt(out)
+
+
+class PerceptualSparsity:
+    """The plugin's sparsity rule (sparse_convolve, DenseConvolution.cpp:110-170; neo_hip_perceptual
+    in include/neo_hip.h): keep a filter bin iff its level relative to its channel's strongest bin,
+    in dB, plus the weight of its column (A-weighting at `sample_rate`, or none; 100 for the first
+    `low_bins_to_keep` columns) exceeds `threshold_db`. Accepted wherever a sparse filter takes a
+    mask; the mask is then made on the device."""
+
+    WEIGHTINGS = {"none": 0, "a": 1}
+
+    def __init__(self, sample_rate: float, threshold_db: float, low_bins_to_keep: int = 0, weighting: str = "a"):
+        if weighting not in self.WEIGHTINGS:
+            raise ValueError(f"weighting must be 'a' or 'none', got {weighting!r}")
+        self.sample_rate, self.threshold_db = float(sample_rate), float(threshold_db)
+        self.low_bins_to_keep, self.weighting = int(low_bins_to_keep), weighting
+
+    def _c(self) -> "_native.Perceptual":
+        return _native.Perceptual(self.sample_rate, self.threshold_db, self.low_bins_to_keep,
+                                  self.WEIGHTINGS[self.weighting])
+
+    def __repr__(self) -> str:
+        return (f"PerceptualSparsity(sample_rate={self.sample_rate}, threshold_db={self.threshold_db}, "
+                f"low_bins_to_keep={self.low_bins_to_keep}, weighting={self.weighting!r})")
+
+
+PERCEPTUAL_BUCKETS = 144
+
+
+def perceptual_weights(block_size: int, sparsity: PerceptualSparsity) -> np.ndarray:
+    """The weight table [B+1] float32 of `sparsity` for blocks of `block_size` (no device needed)."""
+    p = sparsity._c()
+    w = np.empty(min(max(0, int(block_size)), 4096) + 1, dtype=np.float32)  # other blocks are refused
+    _native.check(_native.load().neo_hip_perceptual_weights(int(block_size), ctypes.byref(p), _ptr(w)))
+    return w
+
+
+def _host_partitions(partitions) -> np.ndarray:
+    H = np.ascontiguousarray(partitions, dtype=np.complex64)
+    if H.ndim == 2:
+        H = H[None]
+    if H.ndim != 3 or H.shape[2] < 2:
+        raise ValueError(f"partitions must be [C][P][B+1], got {H.shape}")
+    return H
+
+
+def _device_partitions(t):
+    import torch
+
+    if t.dtype != torch.complex64 or not t.is_contiguous():
+        raise TypeError("partitions must be a contiguous complex64 tensor")
+    shape = (1,) + tuple(t.shape) if t.dim() == 2 else tuple(t.shape)
+    if len(shape) != 3 or shape[2] < 2:
+        raise ValueError(f"partitions must be [C][P][B+1], got {tuple(t.shape)}")
+    return shape
+
+
+def perceptual_mask_host(partitions, sparsity: PerceptualSparsity) -> np.ndarray:
+    """The definition of the predicate, on the host (neo_hip_perceptual_mask_host; no device
+    needed): `partitions` [C][P][B+1] complex64 -> bool mask of the same shape."""
+    H = _host_partitions(partitions)
+    C, P, bins = H.shape
+    p = sparsity._c()
+    m = np.empty(H.shape, dtype=np.uint8)
+    _native.check(_native.load().neo_hip_perceptual_mask_host(_ptr(H), C, bins - 1, P, ctypes.byref(p), _ptr(m)))
+    return m.view(np.bool_)
+
+
+def perceptual_mask(partitions, sparsity: PerceptualSparsity, device: int = 0):
+    """The predicate on the device (neo_hip_perceptual_mask): a host array gives a host bool array,
+    a CUDA tensor a CUDA bool tensor on its device (nothing crosses PCIe)."""
+    p = sparsity._c()
+    if _is_torch(partitions) and partitions.is_cuda:
+        import torch
+
+        C, P, bins = _device_partitions(partitions)
+        m = torch.empty((C, P, bins), dtype=torch.uint8, device=partitions.device)
+        _producer_join(partitions)
+        _native.check(_native.load().neo_hip_perceptual_mask(ctypes.c_void_p(partitions.data_ptr()), C, bins - 1, P,
+                                                             ctypes.byref(p), ctypes.c_void_p(m.data_ptr()), 1,
+                                                             partitions.device.index or 0))
+        return m.view(torch.bool)
+    if _is_torch(partitions):
+        partitions = partitions.numpy()
+    H = _host_partitions(partitions)
+    C, P, bins = H.shape
+    m = np.empty(H.shape, dtype=np.uint8)
+    _native.check(_native.load().neo_hip_perceptual_mask(_ptr(H), C, bins - 1, P, ctypes.byref(p), _ptr(m), 0,
+                                                         int(device)))
+    return m.view(np.bool_)
+
+
+def perceptual_histogram_host(partitions, sparsity: PerceptualSparsity) -> dict:
+    """perceptual_histogram on the host (neo_hip_perceptual_hist_host; no device needed)."""
+    H = _host_partitions(partitions)
+    C, P, bins = H.shape
+    p = sparsity._c()
+    hb = np.zeros((C, PERCEPTUAL_BUCKETS), dtype=np.int64)
+    ht = np.zeros((C, PERCEPTUAL_BUCKETS), dtype=np.int64)
+    _native.check(_native.load().neo_hip_perceptual_hist_host(_ptr(H), C, bins - 1, P, ctypes.byref(p), _ptr(hb),
+                                                              _ptr(ht)))
+    return {"bins": hb, "tiles": ht}
+
+
+def perceptual_histogram(partitions, sparsity: PerceptualSparsity, device: int = 0) -> dict:
+    """How many columns ("bins") and how many 128-byte tiles ("tiles") of every channel lie at which
+    level: [C][144] int64 each, bucket j = levels in (-j - 1, -j] dB (bucket 0 also everything above
+    0 dB, bucket 143 everything below). `sparsity.threshold_db` plays no part. The tiles an integer
+    threshold -k keeps are tiles[:, :k].sum(axis=1): see tile_density_curve. Host array or CUDA
+    tensor; computed on the device either way, the histograms are host arrays."""
+    p = sparsity._c()
+    if _is_torch(partitions) and partitions.is_cuda:
+        C, P, bins = _device_partitions(partitions)
+        ptr, on_device, device = ctypes.c_void_p(partitions.data_ptr()), 1, partitions.device.index or 0
+        _producer_join(partitions)
+    else:
+        H = _host_partitions(partitions.numpy() if _is_torch(partitions) else partitions)
+        C, P, bins = H.shape
+        ptr, on_device = _ptr(H), 0
+    hb = np.zeros((C, PERCEPTUAL_BUCKETS), dtype=np.int64)
+    ht = np.zeros((C, PERCEPTUAL_BUCKETS), dtype=np.int64)
+    _native.check(_native.load().neo_hip_perceptual_histogram(ptr, C, bins - 1, P, ctypes.byref(p), _ptr(hb), _ptr(ht),
+                                                              on_device, int(device)))
+    return {"bins": hb, "tiles": ht}
+
+
+def tile_density_curve(hist_tiles) -> np.ndarray:
+    """[C][144] kept-tile fractions per channel at the thresholds 0, -1, ..., -143 dB from
+    perceptual_histogram's "tiles": entry k is the fraction of the channel's tiles in buckets j < k
+    (exactly the tiles a threshold of -k dB keeps; 0 at a threshold of 0 dB, where only a level
+    above 0 dB would pass)."""
+    h = np.atleast_2d(np.asarray(hist_tiles, dtype=np.int64))
+    if h.shape[1] != PERCEPTUAL_BUCKETS:
+        raise ValueError(f"hist_tiles must be [C][{PERCEPTUAL_BUCKETS}], got {h.shape}")
+    kept = np.zeros(h.shape, dtype=np.float64)
+    kept[:, 1:] = np.cumsum(h, axis=1)[:, :-1]
+    total = h.sum(axis=1, keepdims=True)
+    return kept / np.maximum(total, 1)
+
+
+def threshold_for_tile_density(hist_tiles, target: float):
+    """The lowest integer threshold in dB (the widest dynamic range) among -1 .. -143, where the
+    histogram's counts are exact, at which the kept tiles over ALL channels are at most `target`
+    of all tiles, or None if none is (bucket 0 is kept at every one of them: levels above -1 dB,
+    low_bins_to_keep's +100 among them). Host logic on perceptual_histogram's "tiles"; a sparse
+    handle beats the dense step below about 2 % kept tiles."""
+    h = np.atleast_2d(np.asarray(hist_tiles, dtype=np.int64))
+    if h.shape[1] != PERCEPTUAL_BUCKETS:
+        raise ValueError(f"hist_tiles must be [C][{PERCEPTUAL_BUCKETS}], got {h.shape}")
+    total = int(h.sum())
+    if total == 0:
+        return None
+    kept = np.concatenate([[0], np.cumsum(h.sum(axis=0))[:-1]])  # at thresholds 0, -1, ..., -143
+    ok = np.nonzero(kept[1:] <= float(target) * total)[0]  # kept grows with k: the last one is the lowest
+    return -int(ok[-1] + 1) if ok.size else None
+
+
 class SparseUpolsConvolver(UpolsConvolver):
     """C independent sparse UPOLS / UPOLA convolvers stepped together (neo_hip_upols_create_sparse):
     only the filter bins a mask keeps take part, kept as 128-byte tiles of 16 packed bins; a block
     step reads the kept tiles of the filter and of the FDL rows only. Results are those of the
     dense convolver on the filter with the dropped columns zeroed. Of `options` only fused and
     split_workgroups apply; there are no streaming levels, batched passes, offline windows or
-    latency mode (their setters raise), and set_impulse / the dense filter() form do not apply."""
+    latency mode (their setters raise), and the dense forms filter(partitions) and
+    set_impulse(ir) do not apply: a sparse filter takes a mask or a PerceptualSparsity."""
 
     def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
                  options: dict | None = None):
@@ -900,9 +1095,25 @@ class SparseUpolsConvolver(UpolsConvolver):
     def filter(self, partitions, mask) -> None:
         """sparse_filter's filter(matrix, sparsity) for every channel: `partitions` [C][P][B+1]
         complex64 and `mask` [C][P][B+1] (true = keep), host arrays or CUDA tensors (both on the
-        same side); resets FDL, window and write position."""
+        same side); resets FDL, window and write position. `mask` may be a PerceptualSparsity: the
+        mask is then made on the device from the partitions (neo_hip_upols_set_filter_perceptual;
+        the same handle as filter(partitions, perceptual_mask(partitions, sparsity)))."""
         shape = (self.channels, self.partitions, self.block_size + 1)
         lib = _native.load()
+        if isinstance(mask, PerceptualSparsity):
+            p = mask._c()
+            if _is_torch(partitions) and partitions.is_cuda:
+                if _device_partitions(partitions) != shape:
+                    raise ValueError(f"filter must be {shape}")
+                _producer_join(partitions)
+                _native.check(lib.neo_hip_upols_set_filter_perceptual(self._h, ctypes.c_void_p(partitions.data_ptr()),
+                                                                      ctypes.byref(p), 1))
+                return
+            H = _host_partitions(partitions.numpy() if _is_torch(partitions) else partitions)
+            if H.shape != shape:
+                raise ValueError(f"filter shape {H.shape} != {shape}")
+            _native.check(lib.neo_hip_upols_set_filter_perceptual(self._h, _ptr(H), ctypes.byref(p), 0))
+            return
         if _is_torch(partitions) and partitions.is_cuda:
             import torch
 
@@ -931,6 +1142,39 @@ class SparseUpolsConvolver(UpolsConvolver):
             raise ValueError(f"filter shape {H.shape} / mask shape {m.shape} != {shape}")
         _native.check(lib.neo_hip_upols_set_filter_sparse(self._h, _ptr(H), _ptr(m), 0))
 
+    def set_impulse(self, impulse_response, sparsity=None, normalize: bool = True) -> None:
+        """normalize_impulse (optional), uniform_partition, the mask of `sparsity` (a
+        PerceptualSparsity) and the tiles, all on the device (neo_hip_upols_set_impulse_perceptual):
+        [C][L] float32, host array or CUDA tensor. Without a PerceptualSparsity there is no
+        rule to thin by: that form stays refused, as on every sparse handle."""
+        lib = _native.load()
+        if not isinstance(sparsity, PerceptualSparsity):
+            if isinstance(sparsity, (bool, np.bool_)):  # the base class's (impulse_response, normalize)
+                return super().set_impulse(impulse_response, bool(sparsity))
+            if sparsity is not None:
+                raise TypeError("set_impulse on a sparse convolver takes a PerceptualSparsity")
+            return super().set_impulse(impulse_response, normalize)
+        p = sparsity._c()
+        if _is_torch(impulse_response) and impulse_response.is_cuda:
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise TypeError("set_impulse takes a contiguous float32 tensor")
+            if (1 if t.dim() == 1 else t.shape[0]) != self.channels:
+                raise ValueError("impulse channel count mismatch")
+            _producer_join(t)
+            _native.check(lib.neo_hip_upols_set_impulse_perceptual(self._h, ctypes.c_void_p(t.data_ptr()), t.shape[-1],
+                                                                   int(normalize), ctypes.byref(p), 1))
+            return
+        if _is_torch(impulse_response):
+            impulse_response = impulse_response.numpy()
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)))
+        if ir.shape[0] != self.channels:
+            raise ValueError("impulse channel count mismatch")
+        _native.check(lib.neo_hip_upols_set_impulse_perceptual(self._h, _ptr(ir), ir.shape[1], int(normalize),
+                                                               ctypes.byref(p), 0))
+
     def sparse_info(self) -> dict:
         """The current filter's kept columns and kept 128-byte tiles over all channels, and the
         device bytes (tiles, bitmaps, offsets) that stand in for a dense handle's filter buffer."""
@@ -957,16 +1201,19 @@ class sparse_upols_convolver:
         if H.ndim != 2:
             raise ValueError("filter must be [P][B+1]")
         P, bins = H.shape
-        if callable(sparsity):
-            mask = np.array([[bool(sparsity(r, c, H[r, c])) for c in range(bins)] for r in range(P)], dtype=bool)
+        if isinstance(sparsity, PerceptualSparsity):  # the mask is made on the device
+            mask = sparsity
+        elif callable(sparsity):
+            mask = np.array([[bool(sparsity(r, c, H[r, c])) for c in range(bins)] for r in range(P)], dtype=bool)[None]
         else:
-            mask = np.asarray(sparsity) != 0
-        if mask.shape != H.shape:
-            raise ValueError(f"sparsity shape {mask.shape} != filter shape {H.shape}")
+            mask = (np.asarray(sparsity) != 0)
+            if mask.shape != H.shape:
+                raise ValueError(f"sparsity shape {mask.shape} != filter shape {H.shape}")
+            mask = mask[None]
         impl = self._impl
         if impl is None or (impl.partitions, impl.block_size) != (P, bins - 1):
             impl = SparseUpolsConvolver(1, bins - 1, P, self._device, method=self._method)
-        impl.filter(H[None], mask[None])
+        impl.filter(H[None], mask)
         self._impl = impl
 
     def __call__(self, block):
@@ -984,17 +1231,23 @@ class sparse_upola_convolver(sparse_upols_convolver):
 def sparse_convolve(signal, impulse_response, block_size: int, mask, method: str = "upola", device: int = 0,
                     options: dict | None = None) -> np.ndarray:
     """The plugin's sparse_convolve loop (DenseConvolution.cpp:124-186): normalize the IR matrix,
-    partition it, keep the filter bins `mask` ([C][P][B+1], true = keep; the plugin's A-weighted
-    threshold is the caller's to apply) and run every block (tail zero-padded) through
-    sparse_upola_convolver (or sparse_upols_convolver) per channel; output truncated to N."""
+    partition it, keep the filter bins `mask` ([C][P][B+1], true = keep, or a PerceptualSparsity:
+    the plugin's own A-weighted threshold from sampleRate, thresholdDB and lowBinsToKeep, applied
+    on the device) and run every block (tail zero-padded) through sparse_upola_convolver (or
+    sparse_upols_convolver) per channel; output truncated to N."""
     sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
     ir = np.array(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)), order="C")
     C, N = sig.shape
     if ir.shape[0] != C:
         raise ValueError("signal and impulse response channel counts differ")
-    parts = uniform_partition(normalize_impulse(ir, device), block_size, device)
-    conv = SparseUpolsConvolver(C, block_size, parts.shape[1], device, method=method, options=options)
-    conv.filter(parts, mask)
+    if isinstance(mask, PerceptualSparsity):
+        conv = SparseUpolsConvolver(C, block_size, num_partitions(ir.shape[1], block_size), device, method=method,
+                                    options=options)
+        conv.set_impulse(ir, mask, normalize=True)
+    else:
+        parts = uniform_partition(normalize_impulse(ir, device), block_size, device)
+        conv = SparseUpolsConvolver(C, block_size, parts.shape[1], device, method=method, options=options)
+        conv.filter(parts, mask)
     nb = -(-N // block_size)
     buf = np.zeros((C, nb * block_size), dtype=np.float32)
     buf[:, :N] = sig
