@@ -275,6 +275,12 @@ struct upols_multichannel {
         auto const n = std::int64_t(num_samples);
         neo::hip::check_or_abort(neo_hip_upols_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
     }
+    /// process() that throws std::runtime_error on a device failure instead of aborting
+    auto process_checked(float* io, std::size_t num_samples) -> void
+    {
+        auto const n = std::int64_t(num_samples);
+        neo::hip::check(neo_hip_upols_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
+    }
     auto reset() -> void { neo::hip::check(neo_hip_upols_reset(_h.get())); }
     /// latency mode (neo_hip_upols_set_persistent): one resident kernel steps every block; every
     /// call completes on return (shapes up to 16 channels, 256 partitions, B <= 512; throws otherwise)

@@ -119,6 +119,14 @@ struct hip_fft_plan {
         neo::hip::detail::scatter(_tmp.data(), out);
     }
 
+    /// one transform between contiguous host buffers (in == out allowed); throws std::runtime_error
+    /// on a device failure instead of aborting. A plan may be shared: calls from several threads
+    /// are serialised by the library (neo_hip.h, "Threads and streams").
+    auto execute_host(Complex const* in, Complex* out, direction dir) -> void
+    {
+        neo::hip::check(neo_hip_fft_execute_host(_plan.get(), in, out, int(dir)));
+    }
+
     /// batched device entry: `batch` contiguous transforms, device pointers, hipStream_t as void*
     auto execute_device(Complex const* in, Complex* out, std::size_t batch, direction dir, void* stream = nullptr) -> void
     {

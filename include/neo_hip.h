@@ -20,6 +20,26 @@
  * Every function returns NEO_HIP_OK (0) or a nonzero status; neo_hip_last_error()
  * then holds a message (thread-local). Construction errors map to the
  * reference's std::runtime_error (c2c_dit2_plan.hpp:97-104).
+ *
+ * Threads and streams:
+ *   - DISTINCT OBJECTS (FFT plans, convolver handles of every kind, overlap stages, groups,
+ *     multi-device convolvers) may be used at the same time from distinct threads with no
+ *     locking by the caller; what they share inside the library (the device-memory pool, the
+ *     four streams per device, the twiddle tables, the groups' page-lock table) is the
+ *     library's to protect. Results are bit-identical to the same calls made one thread after
+ *     the other.
+ *   - ONE-SHOT ENTRY POINTS are re-entrant: neo_hip_fft_convolve*, neo_hip_direct_convolve*,
+ *     neo_hip_stft*, neo_hip_uniform_partition, neo_hip_normalize_impulse, neo_hip_perceptual_*.
+ *   - ONE FFT PLAN may be executed from several threads and on several streams. The library
+ *     serialises what the plan's buffers require: neo_hip_fft_execute_host calls on one plan
+ *     run one after the other (one pair of staging buffers), and an execute of a multi-pass
+ *     plan (inner order above 12: the plan owns scratch) on another stream than the plan's
+ *     last execute first waits, on the device, for that execute. A call's result is that of
+ *     the call alone. Destroying a plan is for one thread, after its last call has returned.
+ *   - ONE CONVOLVER HANDLE, OVERLAP STAGE OR GROUP is for one thread at a time, as the
+ *     reference's stateful convolvers are: its calls carry state from block to block and take
+ *     no lock on the step path. A caller that moves one between threads orders the calls.
+ *   - neo_hip_last_error() is per thread: the message of the calling thread's last failed call.
  */
 #ifndef NEO_HIP_H
 #define NEO_HIP_H
@@ -389,7 +409,8 @@ NEO_HIP_API int neo_hip_upols_multi_reset(neo_hip_upols_multi* m);
  * host memory, in place, complete on return. A group belongs to ONE owner (one plugin
  * instance's convolvers; C++: neo::convolution::convolver_group). While the callers follow the
  * plugin's frame pattern (every member called once per frame on a buffer of its own that it
- * reuses) AND every member's buffer lies in a range the owner registered, the group steps every
+ * reuses) AND every member's buffer lies in a range the owner registered AND the members' shape
+ * runs the streaming levels (64 partitions and up, blocks up to 1024), the group steps every
  * member in ONE launch at a frame's first call, from the blocks in the other members'
  * registered buffers, and later calls only verify their block (a different block re-runs that
  * member's block step alone); any other pattern runs each member on a handle of its own. Either

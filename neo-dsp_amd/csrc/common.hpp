@@ -151,6 +151,8 @@ int null_join();
 // The streams a handle's (or plan's) asynchronous calls ran on since its last join: a setup call
 // or a destroy waits for these, not for the device. A stream given to such a call stays valid
 // until then. On overflow the remembered streams are joined first (their work is then complete).
+// Not synchronised: note() and join() are the owner's calls, one at a time (a handle is for one
+// thread at a time; an FFT plan, which several threads may execute, calls note() under its mutex).
 struct stream_set {
     static constexpr int kMax = 16;
     hipStream_t s[kMax] = {};

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cstring>
 #include <memory>
+#include <mutex>
 
 namespace neo_hip {
 
@@ -307,6 +308,17 @@ struct neo_hip_fft_plan {
     void* d_out = nullptr;
     size_t in_bytes = 0, out_bytes = 0;
     neo_hip::stream_set used;  // streams the plan's executes ran on (destroy joins them, not the device)
+    // One plan may be executed from several threads and on several streams (neo_hip.h). mu covers
+    // what an execute changes on the host (used, the staging pointers, last) and, for
+    // neo_hip_fft_execute_host, the staging buffers from the upload to the final stream sync.
+    std::mutex mu;
+    // Plans that own scratch (inner order above the LDS path): recorded after the last launch of
+    // every execute; an execute on another stream than the last one waits for it first, so its
+    // first pass does not overwrite scratch the earlier execute still reads. Null for LDS-path
+    // plans, which keep nothing on the device between their one kernel's load and store.
+    hipEvent_t scratch_done = nullptr;
+    hipStream_t last = nullptr;  // the stream scratch_done was recorded on
+    bool recorded = false;
 };
 
 namespace {
@@ -426,6 +438,7 @@ void free_plan(plan_t* p)
     for (auto* s : p->d_scratch) dfree(s);
     dfree(p->d_in);
     dfree(p->d_out);
+    if (p->scratch_done) (void)hipEventDestroy(p->scratch_done);
     // p->stream is one of the device's shared streams (dmem.hip)
     delete p;
 }
@@ -462,6 +475,7 @@ int setup_tables(plan_t* p)
         for (int i = 0; i < nscratch; ++i)
             if (dalloc(&p->d_scratch[i], size_t(inner * p->batch) * sizeof(C)))
                 return fail(NEO_HIP_ENOMEM, "scratch allocation failed");
+        NEO_HIP_CHECK(hipEventCreateWithFlags(&p->scratch_done, hipEventDisableTiming));
         if (p->kind != NEO_HIP_C2C) {
             p->lo_bits2 = (io + 2) / 2;
             if ((rc = upload(&p->d_split2, make_split_table<C>(io + 1, p->lo_bits2)))) return rc;
@@ -512,6 +526,20 @@ int execute(neo_hip_fft_plan* p, const void* in, void* out, int direction, hipSt
                        p->lo_bits2, m, p->batch);
     NEO_HIP_LAUNCH_CHECK();
     return run_c2c_global(p, io, static_cast<const C*>(z), static_cast<C*>(out), +1, s);
+}
+
+// One execute's launches on s; the caller holds p->mu.
+int enqueue(plan_t* p, const void* in, void* out, int direction, hipStream_t s)
+{
+    if (int rc = p->used.note(s)) return rc;
+    if (p->scratch_done && p->recorded && p->last != s) NEO_HIP_CHECK(hipStreamWaitEvent(s, p->scratch_done, 0));
+    const int rc = p->f64 ? execute<cd>(p, in, out, direction, s) : execute<cf>(p, in, out, direction, s);
+    if (p->scratch_done) {  // also after a failed launch: earlier passes may be queued
+        NEO_HIP_CHECK(hipEventRecord(p->scratch_done, s));
+        p->last = s;
+        p->recorded = true;
+    }
+    return rc;
 }
 
 }  // namespace
@@ -570,20 +598,23 @@ NEO_HIP_API int neo_hip_fft_execute(neo_hip_fft_plan* p, const void* in, void* o
         return fail(NEO_HIP_EINVAL, "direction must be -1 (forward) or +1 (backward)");
     device_guard g(p->device);
     if (g.rc) return g.rc;
-    hipStream_t s = as_stream(stream);  // NULL = the HIP null stream (torch's default stream)
-    if (int rc = p->used.note(s)) return rc;
-    return p->f64 ? execute<cd>(p, in, out, direction, s) : execute<cf>(p, in, out, direction, s);
+    std::lock_guard<std::mutex> lk(p->mu);
+    return enqueue(p, in, out, direction, as_stream(stream));  // NULL = the HIP null stream (torch's default stream)
 }
 
 NEO_HIP_API int neo_hip_fft_execute_host(neo_hip_fft_plan* p, const void* in, void* out, int direction)
 {
     if (!p || !in || !out) return fail(NEO_HIP_EINVAL, "null plan or buffer");
+    if (p->kind == NEO_HIP_C2C && direction != -1 && direction != 1)
+        return fail(NEO_HIP_EINVAL, "direction must be -1 (forward) or +1 (backward)");
     device_guard g(p->device);
     if (g.rc) return g.rc;
+    // one staging pair per plan: the next caller's upload waits until this one's result is on the host
+    std::lock_guard<std::mutex> lk(p->mu);
     if ((!p->d_in && dalloc(&p->d_in, p->in_bytes)) || (!p->d_out && dalloc(&p->d_out, p->out_bytes)))
         return fail(NEO_HIP_ENOMEM, "fft staging allocation failed");
     NEO_HIP_CHECK(hipMemcpyAsync(p->d_in, in, p->in_bytes, hipMemcpyHostToDevice, p->stream));
-    int rc = neo_hip_fft_execute(p, p->d_in, p->d_out, direction, p->stream);
+    int rc = enqueue(p, p->d_in, p->d_out, direction, p->stream);
     if (rc) return rc;
     NEO_HIP_CHECK(hipMemcpyAsync(out, p->d_out, p->out_bytes, hipMemcpyDeviceToHost, p->stream));
     NEO_HIP_CHECK(hipStreamSynchronize(p->stream));
