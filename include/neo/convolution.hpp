@@ -209,7 +209,8 @@ struct upols_multichannel {
 
     /// C sparse convolvers (method::upols or method::upola): only the filter bins a mask keeps
     /// take part, kept as 128-byte tiles; filter_sparse() sets the filter (filter() and impulse()
-    /// throw), and the latency mode, paced work and offline windows do not apply (they throw)
+    /// throw), and the latency mode, paced work and offline windows do not apply (they throw).
+    /// One block per pass unless batch(true) turns the batched passes on.
     upols_multichannel(sparse_tag, std::size_t channels, std::size_t block_size, std::size_t partitions,
                        int device = neo::hip::detail::default_device(), method m = method::upols)
         : _C{channels}, _B{block_size}, _P{partitions}
@@ -295,6 +296,9 @@ struct upols_multichannel {
     /// offline windows for batched calls of >= 128 blocks (on by default from 128 partitions;
     /// neo_hip_upols_set_offline): 128-block windows through partition-axis transforms
     auto offline(bool on) -> void { neo::hip::check(neo_hip_upols_set_offline(_h.get(), on ? 1 : 0)); }
+    /// batched passes (neo_hip_upols_set_batch): process() runs T blocks per pass over the filter
+    /// and the FDL. On by default on dense handles, off on sparse ones.
+    auto batch(bool on) -> void { neo::hip::check(neo_hip_upols_set_batch(_h.get(), on ? 1 : 0)); }
 
     [[nodiscard]] auto channels() const noexcept { return _C; }
     [[nodiscard]] auto block_size() const noexcept { return _B; }
@@ -855,6 +859,61 @@ inline auto dense_convolve(float const* signal, std::size_t channels, std::size_
         for (std::size_t c = 0; c < channels; ++c)
             std::copy(buf.data() + c * n, buf.data() + c * n + (hi - lo), out + c * num_samples + lo);
     }
+}
+
+namespace detail {
+// the loop of dense_convolve on a convolver whose filter is set: chunks of <= 2^26 samples, one
+// upload, batched passes, one download per chunk; the tail block is zero-padded
+inline auto convolve_chunks(upols_multichannel& conv, float const* signal, std::size_t channels,
+                            std::size_t num_samples, std::size_t block_size, float* out) -> void
+{
+    std::size_t const nb = (num_samples + block_size - 1) / block_size;
+    std::size_t chunk = std::max<std::size_t>(1, (std::size_t(1) << 26) / (channels * block_size));
+    chunk = std::max<std::size_t>(256, chunk / 256 * 256);
+    std::vector<float> buf;
+    for (std::size_t t0 = 0; t0 < nb; t0 += chunk) {
+        std::size_t const t1 = std::min(nb, t0 + chunk), lo = t0 * block_size,
+                          hi = std::min(num_samples, t1 * block_size), n = (t1 - t0) * block_size;
+        buf.assign(channels * n, 0.0F);
+        for (std::size_t c = 0; c < channels; ++c)
+            std::copy(signal + c * num_samples + lo, signal + c * num_samples + hi, buf.data() + c * n);
+        conv.process_checked(buf.data(), n);
+        for (std::size_t c = 0; c < channels; ++c)
+            std::copy(buf.data() + c * n, buf.data() + c * n + (hi - lo), out + c * num_samples + lo);
+    }
+}
+}  // namespace detail
+
+/// The plugin's sparse_convolve loop (extra/plugin/src/dsp/DenseConvolution.cpp:124-186) over plain
+/// arrays: signal [C][N], ir [C][L] -> out [C][N]; normalizes + partitions the IR, keeps the filter
+/// bins of mask [C][P][B+1] (nonzero = keep; P = num_partitions(L, B)), tail block zero-padded.
+/// Every block is known up front: the sparse handle runs batched passes.
+inline auto sparse_convolve(float const* signal, std::size_t channels, std::size_t num_samples, float const* ir,
+                            std::size_t ir_length, std::size_t block_size, std::uint8_t const* mask, float* out,
+                            method m = method::upola) -> void
+{
+    auto const P = num_partitions(ir_length, block_size);
+    int const device = neo::hip::detail::default_device();
+    std::vector<float> h(ir, ir + channels * ir_length);
+    neo::hip::check(neo_hip_normalize_impulse(h.data(), int(channels), std::int64_t(ir_length), 0, device));
+    std::vector<std::complex<float>> parts(channels * P * (block_size + 1));
+    neo::hip::check(neo_hip_uniform_partition(h.data(), int(channels), std::int64_t(ir_length), int(block_size),
+                                              parts.data(), 0, device));
+    upols_multichannel conv{sparse, channels, block_size, P, device, m};
+    conv.filter_sparse(parts.data(), mask);
+    conv.batch(true);
+    detail::convolve_chunks(conv, signal, channels, num_samples, block_size, out);
+}
+/// the same with the plugin's own rule instead of a mask: the mask is made on the device
+inline auto sparse_convolve(float const* signal, std::size_t channels, std::size_t num_samples, float const* ir,
+                            std::size_t ir_length, std::size_t block_size, perceptual_sparsity const& sparsity,
+                            float* out, method m = method::upola) -> void
+{
+    upols_multichannel conv{sparse, channels, block_size, num_partitions(ir_length, block_size),
+                            neo::hip::detail::default_device(), m};
+    conv.impulse_perceptual(ir, ir_length, sparsity, true);
+    conv.batch(true);
+    detail::convolve_chunks(conv, signal, channels, num_samples, block_size, out);
 }
 
 /// fft_convolve (fft_convolver.hpp:72-93): full linear convolution on the GPU, host arrays

@@ -76,8 +76,10 @@ typedef struct neo_hip_upols neo_hip_upols;
 /* ABI version of this header. neo_hip_upols_opts grows with it (0.1.0: 6 ints; 0.2.0: the 10
  * below), so a caller checks neo_hip_version() == NEO_HIP_VERSION before passing one.
  * 0.3.0: the sparse convolvers (neo_hip_upols_create_sparse and what goes with it).
- * 0.4.0: the perceptual sparsity predicate (neo_hip_perceptual_* and the two handle calls). */
-#define NEO_HIP_VERSION 400 /* 0.4.0 */
+ * 0.4.0: the perceptual sparsity predicate (neo_hip_perceptual_* and the two handle calls).
+ * 0.5.0: batched passes on sparse handles (set_batch(1) accepted; neo_hip_upols_sparse_window_plan,
+ *        neo_hip_upols_sparse_batch_info). */
+#define NEO_HIP_VERSION 500 /* 0.5.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -175,16 +177,23 @@ NEO_HIP_API int neo_hip_upols_create_ex(int channels, int block, int partitions,
  * bitmap of NW = max(1, B / 512) uint32 words (tile t = bit t % 32 of word t / 32) and an offset
  * in tiles into its channel's compacted values ([C][P + 1], the exclusive prefix sum of the rows'
  * popcounts); a block step reads the kept tiles of the filter and of the FDL rows only.
- * A sparse handle holds no dense filter buffer and no streaming-level, batch or offline buffers.
+ * A sparse handle holds no dense filter buffer and no streaming-level or offline buffers.
  * Of opts only fused and split_workgroups apply (the partitions are cut at equal row counts, as
  * the dense plain step cuts them; with the same cuts and the same fused choice its outputs equal
  * the dense plain step's on the zeroed filter bit for bit, up to the sign of zero). method 2
- * (sub-block input) is EINVAL. On a sparse handle process, process_device, process_blocks (one
- * block per pass), process_samples (multiples of B), reset, info, destroy and the timing calls
- * work; set_filter and set_impulse (it takes set_filter_sparse, set_filter_perceptual or
- * set_impulse_perceptual), set_ahead(1), set_offline(1),
- * set_batch(1), set_persistent(1) and set_paced(1 / 2) return EINVAL and name the reason, and the
- * getters report off. Groups and the multi-device convolver take no sparse members. */
+ * (sub-block input) is EINVAL. On a sparse handle process, process_device, process_blocks,
+ * process_samples (multiples of B), reset, info, destroy and the timing calls work. Batching is
+ * OFF by default (one block per pass, as a real-time caller steps it); set_batch(1) turns it on:
+ * process_blocks / process_samples then cut a call as on a dense handle, into the largest
+ * power-of-two batches <= 32 of the whole blocks left, and the T blocks of a batch share ONE pass
+ * over the kept filter tiles and over the FDL tiles of the window bitmaps (below); the rest run one
+ * block per pass. Batched and single passes mix in any order at block boundaries; the results are
+ * equal within float rounding (another summation order), and two runs of the same calls are equal
+ * bit for bit. The batch buffers are allocated at the first batched pass.
+ * set_filter and set_impulse (it takes set_filter_sparse, set_filter_perceptual or
+ * set_impulse_perceptual), set_ahead(1), set_offline(1), set_persistent(1) and set_paced(1 / 2)
+ * return EINVAL and name the reason, and their getters report off. Groups and the multi-device
+ * convolver take no sparse members. */
 NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partitions, int device, int method,
                                             const neo_hip_upols_opts* opts, neo_hip_upols** h);
 /* filter [C][P][B+1] complex and mask [C][P][B+1] bytes (nonzero = keep), both host or both device
@@ -198,6 +207,17 @@ NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, 
  * mask [C][P][B+1] -> tile_mask [C][P][NW], row_off [C][P+1], kept columns, kept tiles. */
 NEO_HIP_API int neo_hip_upols_sparse_plan(const uint8_t* mask, int channels, int block, int partitions,
                                           uint32_t* tile_mask, uint32_t* row_off, int64_t* kept_bins, int64_t* kept_tiles);
+/* The window bitmaps of a batched pass of `window` blocks (a power of two, 2..32), on the host (no
+ * device needed): the FDL row that enters the pass at partition p meets the filter rows
+ * p .. p + window - 1, so win_mask[c][p] = OR of tile_mask[c][q] over q in [p, min(P, p + window));
+ * tile_mask (from neo_hip_upols_sparse_plan) and win_mask [C][P][NW], not the same buffer;
+ * window_tiles (may be NULL) = the sum of win_mask's popcounts. */
+NEO_HIP_API int neo_hip_upols_sparse_window_plan(const uint32_t* tile_mask, int channels, int block, int partitions,
+                                                 int window, uint32_t* win_mask, int64_t* window_tiles);
+/* Sparse handles: the blocks per batched pass T and its splits per channel (whether batching is on
+ * or not; neo_hip_upols_batch_info reports what process_blocks does now), and the popcount sum of
+ * the window bitmaps the device made for T at the last filter change. */
+NEO_HIP_API int neo_hip_upols_sparse_batch_info(neo_hip_upols* h, int* blocks_per_pass, int* splits, int64_t* window_tiles);
 /* -- Perceptual sparsity (the plugin's sparse_convolve threshold) -------------------
  * Which bins of a filter [C][P][B+1] (uniform_partition layout) a sparse handle keeps, as the
  * plugin decides it (extra/plugin/src/dsp/DenseConvolution.cpp:110-170; src/neo/unit/decibel.hpp,

@@ -53,4 +53,32 @@ inline bool sparse_plan(const uint8_t* mask, int channels, int block, int partit
     return true;
 }
 
+constexpr bool sparse_window_ok(int w) { return w >= 2 && w <= 32 && (w & (w - 1)) == 0; }
+
+// The window bitmaps of a batched pass of `window` blocks (upols_sparse_batch.hip): the FDL row
+// that enters a workgroup's sliding window at partition p is multiplied by the filter rows
+// p .. p + window - 1, so a lane needs its tile only if one of those rows keeps the tile:
+// win_mask[c][p] = OR of tile_mask[c][q] over q in [p, min(P, p + window)). window_tiles: the
+// popcount sum. tile_mask and win_mask [C][P][NW]; false: bad arguments (nothing written).
+inline bool sparse_window_plan(const uint32_t* tile_mask, int channels, int block, int partitions, int window,
+                               uint32_t* win_mask, int64_t* window_tiles)
+{
+    if (!tile_mask || !win_mask || channels < 1 || partitions < 1 || !sparse_block_ok(block) || !sparse_window_ok(window))
+        return false;
+    const int NW = sparse_words(block);
+    int64_t tiles = 0;
+    for (int64_t c = 0; c < channels; ++c)
+        for (int64_t p = 0; p < partitions; ++p) {
+            const int64_t q1 = p + window < partitions ? p + window : partitions;
+            for (int i = 0; i < NW; ++i) {
+                uint32_t w = 0;
+                for (int64_t q = p; q < q1; ++q) w |= tile_mask[(c * partitions + q) * NW + i];
+                win_mask[(c * partitions + p) * NW + i] = w;
+                tiles += __builtin_popcount(w);
+            }
+        }
+    if (window_tiles) *window_tiles = tiles;
+    return true;
+}
+
 }  // namespace neo_hip

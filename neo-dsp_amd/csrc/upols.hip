@@ -663,8 +663,8 @@ int neo_hip::create_handle(int channels, int block, int partitions, int device, 
 namespace {
 // A sparse handle (sparse_upols_convolver / sparse_upola_convolver, src/neo/convolution/
 // sparse_convolver.hpp:12-17): the FDL ring, the step state and the bitmaps / offsets; the
-// compacted tiles come with the filter (sparse_set_filter). No dense filter buffer, no level,
-// batch or offline buffers.
+// compacted tiles come with the filter (sparse_set_filter). No dense filter buffer, no level or
+// offline buffers; the batch buffers come with the first batched pass.
 int create_sparse(int channels, int block, int partitions, int device, bool ola, const neo_hip_upols_opts* opt,
                   neo_hip_upols** out)
 {
@@ -690,7 +690,18 @@ int create_sparse(int channels, int block, int partitions, int device, bool ola,
     h->P = partitions;
     h->ring = partitions + kMaxBatch - 1;
     h->ola = ola;
-    h->batch = false;  // process_blocks: one block per pass through the sparse step
+    // process_blocks: one block per pass through the sparse step unless neo_hip_upols_set_batch
+    // turns the batched passes on (upols_sparse_batch.hip); their splits follow create_convolver's
+    // rule on the dense shape (one lane per bin, 512 workgroups, >= 2 T partitions per split, whole
+    // chunks of kMaxBatch); part_b and tail come with the first batched pass (launch_batch)
+    h->batch = false;
+    {
+        const int bgroups = std::max(1, block / 256);
+        const int Sb = std::max(1, std::min({(512 + channels * bgroups - 1) / (channels * bgroups),
+                                             partitions / (2 * batch_blocks(h)), 64}));
+        h->rows_b = ((partitions + Sb - 1) / Sb + kMaxBatch - 1) / kMaxBatch * kMaxBatch;
+        h->Sb = (partitions + h->rows_b - 1) / h->rows_b;
+    }
     // one launch or two, and the splits: the dense plain step's rules (create_convolver) on the
     // dense shape, so a sparse handle and a dense one of the same shape and options cut the
     // partitions alike (equal row counts; the order per bin is the dense order)
@@ -848,6 +859,25 @@ NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, 
     if (filter_bytes)  // the compacted tiles, the bitmaps and the offsets: what stands in for the [C][R][B] filter
         *filter_bytes = h->sp_tiles * int64_t(kSparseTile * sizeof(cf)) +
                         int64_t(h->C) * (int64_t(h->P) * sparse_words(h->B) + h->P + 1) * int64_t(sizeof(uint32_t));
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_upols_sparse_window_plan(const uint32_t* tile_mask, int channels, int block, int partitions,
+                                                 int window, uint32_t* win_mask, int64_t* window_tiles)
+{
+    if (!sparse_window_plan(tile_mask, channels, block, partitions, window, win_mask, window_tiles))
+        return fail(NEO_HIP_EINVAL, "sparse_window_plan: null pointer, channels or partitions < 1, block not a power of "
+                                    "two in [16, 4096], or window not a power of two in [2, 32]");
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_upols_sparse_batch_info(neo_hip_upols* h, int* blocks_per_pass, int* splits, int64_t* window_tiles)
+{
+    if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (!h->sparse) return fail(NEO_HIP_EINVAL, "sparse_batch_info: not a sparse handle");
+    if (blocks_per_pass) *blocks_per_pass = batch_blocks(h);
+    if (splits) *splits = h->Sb;
+    if (window_tiles) *window_tiles = h->sp_wtiles;
     return NEO_HIP_OK;
 }
 
@@ -1080,8 +1110,9 @@ NEO_HIP_API int neo_hip_upols_batch_info(neo_hip_upols* h, int* blocks_per_pass,
 NEO_HIP_API int neo_hip_upols_set_batch(neo_hip_upols* h, int enable)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
-    if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle runs one block per pass (no batched passes)");
-    h->batch = enable != 0;
+    if (enable && h->ring - h->P < batch_blocks(h) - 1)
+        return fail(NEO_HIP_EINVAL, "the FDL ring is too short for a batch of %d blocks", batch_blocks(h));
+    h->batch = enable != 0;  // (a sparse handle: off until asked for; its batched MAC is k_sparse_batch_mac)
     return NEO_HIP_OK;
 }
 

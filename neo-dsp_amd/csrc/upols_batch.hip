@@ -458,7 +458,9 @@ int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t
     int rc = timing_begin(h, 2, &ev);
     if (!rc) rc = timing_mark(ev, 0, s);
     if (rc) return rc;
-    if (h->bNB == 2) {
+    if (h->sparse) {  // the kept tiles only (upols_sparse_batch.hip); everything around it as below
+        rc = launch_sparse_batch_mac(h, T, s);
+    } else if (h->bNB == 2) {
         NEO_UPOLS_DISPATCH(B, rc = (launch_batch_mac<BB, 2>(h, T, s)))
     } else {
         NEO_UPOLS_DISPATCH(B, rc = (launch_batch_mac<BB, 1>(h, T, s)))

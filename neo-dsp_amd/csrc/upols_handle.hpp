@@ -243,14 +243,17 @@ struct neo_hip_upols {
     int64_t cstride = 0, pstride = 0;
     int pc = 0;  // filter rows per channel read with the cacheable policy (kCacheBudgetBytes; NEO_HIP_CACHE_ROWS)
     // sparse handle (neo_hip_upols_create_sparse, upols_sparse.hip; format: sparse_plan.hpp): no
-    // dense filter (H stays null, the FDL is an allocation of its own), no levels, batches or
-    // offline windows; every block is one k_upols_sparse_step
+    // dense filter (H stays null, the FDL is an allocation of its own), no levels or offline
+    // windows; a block is one k_upols_sparse_step, or with batching on (off by default) T blocks
+    // share one k_sparse_batch_mac pass over the kept tiles (upols_sparse_batch.hip)
     bool sparse = false;
     uint32_t* sp_bits = nullptr;   // kept-tile bitmaps [C][P][NW]
     uint32_t* sp_off = nullptr;    // row offsets [C][P + 1], tile units within the channel
     int64_t* sp_base = nullptr;    // [C + 2]: channel c's first tile, the total at [C]; kept columns at [C + 1]
     neo_hip::cf* sp_val = nullptr; // compacted tiles [kept tiles][16] (null until a filter is set, or none kept)
     int64_t sp_tiles = 0, sp_bins = 0;
+    uint32_t* sp_win = nullptr;    // window bitmaps [C][P][NW]: the OR of rows [p, min(P, p + kMaxBatch)) of sp_bits
+    int64_t sp_wtiles = 0;         // their popcount sum
     struct ev_group {
         hipEvent_t e[4] = {};
         int n = 0;
@@ -342,6 +345,9 @@ int sparse_alloc(upols_t* h);
 void sparse_free(upols_t* h);
 int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s);
 int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
+// upols_sparse_batch.hip: the MAC of a batched pass of a sparse handle (launch_batch, upols_batch.hip):
+// T blocks at write position h->wpos into the slabs part_b [C][Sb][T][B], over the kept tiles
+int launch_sparse_batch_mac(const upols_t* h, int T, hipStream_t s);
 // perceptual.hip: mask [C][P][B + 1] of the perceptual predicate (perceptual_plan.hpp) for a device
 // filter, on s. *tmp (pooled) and the host weights [B + 1] stay alive until s is joined.
 int perceptual_mask_device(const cf* filter, int C, int B, int P, const neo_hip_perceptual* pp, const float* weights,

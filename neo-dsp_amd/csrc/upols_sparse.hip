@@ -6,7 +6,8 @@
 // Format (sparse_plan.hpp): the unit is a 128-B tile of 16 packed bins, not a bin -- a gather of
 // single 8-B bins would still move whole 128-B requests. Per filter row a bitmap of kept tiles
 // and a tile offset into the channel's compacted values; the FDL stays [C][R][B] and every step
-// inserts the whole new row (later partitions keep other tiles).
+// inserts the whole new row (later partitions keep other tiles). Beside the bitmaps the setup
+// makes the window bitmaps of the batched pass (upols_sparse_batch.hip).
 //
 // Step: k_upols_sparse_step is the dense plain step (upols_step.hpp: window r2c, FDL insert,
 // acc4 accumulators, row-group fold, slabs, last-arriver tail or k_upols_finish) with the loop
@@ -93,6 +94,28 @@ __global__ __launch_bounds__(256) void k_sparse_rows(const uint8_t* __restrict__
     }
 }
 
+// The window bitmaps of the batched pass (sparse_plan.hpp sparse_window_plan, window kMaxBatch):
+// one lane per word, win[c][p][i] = OR of bits[c][q][i] over q in [p, min(P, p + kMaxBatch)); their
+// popcounts add up in win_tiles.
+__global__ __launch_bounds__(256) void k_sparse_win(const uint32_t* __restrict__ bits, int P, int NW, int64_t n,
+                                                    uint32_t* __restrict__ win, unsigned long long* __restrict__ win_tiles)
+{
+    __shared__ int tiles;
+    if (threadIdx.x == 0) tiles = 0;
+    __syncthreads();
+    const int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i < n) {
+        const int64_t r = i / NW;
+        const int p = int(r % P), q1 = min(P, p + kMaxBatch);
+        uint32_t wv = 0;
+        for (int q = p; q < q1; ++q) wv |= bits[i + int64_t(q - p) * NW];
+        win[i] = wv;
+        if (wv) atomicAdd(&tiles, __popc(wv));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && tiles) atomicAdd(win_tiles, (unsigned long long)tiles);
+}
+
 // One workgroup per channel: off[c][0..P) counts -> exclusive prefix sums, off[c][P] = the total.
 // Lane t scans the rows [t chunk, (t + 1) chunk); the 256 chunk sums are scanned by lane 0.
 __global__ __launch_bounds__(256) void k_sparse_scan(uint32_t* __restrict__ off, int P)
@@ -165,22 +188,25 @@ int sparse_alloc(upols_t* h)
 {
     const size_t rows = size_t(h->C) * size_t(h->P);
     if (dalloc(&h->sp_bits, rows * sparse_words(h->B) * sizeof(uint32_t)) ||
-        dalloc(&h->sp_off, (rows + h->C) * sizeof(uint32_t)) || dalloc(&h->sp_base, size_t(h->C + 2) * sizeof(int64_t)))
+        dalloc(&h->sp_win, rows * sparse_words(h->B) * sizeof(uint32_t)) ||
+        dalloc(&h->sp_off, (rows + h->C) * sizeof(uint32_t)) || dalloc(&h->sp_base, size_t(h->C + 3) * sizeof(int64_t)))
         return NEO_HIP_ENOMEM;
     // an empty filter until the first one is set: no tile kept, every offset zero
     NEO_HIP_CHECK(hipMemsetAsync(h->sp_bits, 0, rows * sparse_words(h->B) * sizeof(uint32_t), h->stream));
+    NEO_HIP_CHECK(hipMemsetAsync(h->sp_win, 0, rows * sparse_words(h->B) * sizeof(uint32_t), h->stream));
     NEO_HIP_CHECK(hipMemsetAsync(h->sp_off, 0, (rows + h->C) * sizeof(uint32_t), h->stream));
-    NEO_HIP_CHECK(hipMemsetAsync(h->sp_base, 0, size_t(h->C + 2) * sizeof(int64_t), h->stream));
+    NEO_HIP_CHECK(hipMemsetAsync(h->sp_base, 0, size_t(h->C + 3) * sizeof(int64_t), h->stream));
     return NEO_HIP_OK;
 }
 
 void sparse_free(upols_t* h)
 {
     dfree(h->sp_bits);
+    dfree(h->sp_win);
     dfree(h->sp_off);
     dfree(h->sp_base);
     dfree(h->sp_val);
-    h->sp_bits = h->sp_off = nullptr;
+    h->sp_bits = h->sp_win = h->sp_off = nullptr;
     h->sp_base = nullptr;
     h->sp_val = nullptr;
 }
@@ -192,23 +218,29 @@ int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStre
     // the caller joined every stream this handle's steps ran on: the old tiles are free to go
     dfree(h->sp_val);
     h->sp_val = nullptr;
-    h->sp_tiles = h->sp_bins = 0;
-    unsigned long long* cols = reinterpret_cast<unsigned long long*>(h->sp_base + h->C + 1);
-    NEO_HIP_CHECK(hipMemsetAsync(cols, 0, sizeof(unsigned long long), s));
+    h->sp_tiles = h->sp_bins = h->sp_wtiles = 0;
+    unsigned long long* cols = reinterpret_cast<unsigned long long*>(h->sp_base + h->C + 1);  // and the window tiles
+    NEO_HIP_CHECK(hipMemsetAsync(cols, 0, 2 * sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_sparse_rows, dim3(unsigned(rows)), dim3(256), 0, s, mask, h->B, h->P, h->sp_bits, h->sp_off, cols);
+    NEO_HIP_LAUNCH_CHECK();
+    const int64_t words = rows * sparse_words(h->B);
+    hipLaunchKernelGGL(k_sparse_win, dim3(unsigned((words + 255) / 256)), dim3(256), 0, s, h->sp_bits, h->P,
+                       sparse_words(h->B), words, h->sp_win, cols + 1);
     NEO_HIP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sparse_scan, dim3(unsigned(h->C)), dim3(256), 0, s, h->sp_off, h->P);
     NEO_HIP_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sparse_base, dim3(1), dim3(64), 0, s, h->sp_off, h->C, h->P, h->sp_base);
     NEO_HIP_LAUNCH_CHECK();
-    int64_t tot[2] = {0, 0};  // kept tiles, kept columns: all that comes back to the host
+    int64_t tot[3] = {0, 0, 0};  // kept tiles, kept columns, window tiles: all that comes back to the host
     NEO_HIP_CHECK(hipMemcpyAsync(tot, h->sp_base + h->C, sizeof tot, hipMemcpyDeviceToHost, s));
     NEO_HIP_CHECK(hipStreamSynchronize(s));  // the handle's stream, never the device
     h->sp_tiles = tot[0];
     h->sp_bins = tot[1];
+    h->sp_wtiles = tot[2];
     const double bytes = double(h->sp_tiles) * kSparseTile * sizeof(cf);
     // filter rows read cacheable (the Infinity Cache budget of the dense step, in kept bytes)
     h->pc = bytes <= kCacheBudgetBytes ? h->P : int(double(h->P) * kCacheBudgetBytes / bytes);
+    h->pcb = bytes <= kBatchCacheBudgetBytes ? h->P : int(double(h->P) * kBatchCacheBudgetBytes / bytes);
     if (!h->sp_tiles) return NEO_HIP_OK;
     if (int rc = dalloc(&h->sp_val, size_t(h->sp_tiles) * kSparseTile * sizeof(cf))) return rc;
     hipLaunchKernelGGL(k_sparse_pack, dim3(unsigned(rows)), dim3(256), 0, s, filter, mask, h->B, h->P, h->sp_bits,

@@ -62,6 +62,8 @@ SIGNATURES = {
     "neo_hip_upols_set_filter_sparse": (_i, [_vp, _vp, _vp, _i]),
     "neo_hip_upols_sparse_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
     "neo_hip_upols_sparse_plan": (_i, [_vp, _i, _i, _i, _vp, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "neo_hip_upols_sparse_window_plan": (_i, [_vp, _i, _i, _i, _i, _vp, ctypes.POINTER(_i64)]),
+    "neo_hip_upols_sparse_batch_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
     "neo_hip_perceptual_weights": (_i, [_i, _vp, _vp]),
     "neo_hip_perceptual_mask_host": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "neo_hip_perceptual_hist_host": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -133,7 +135,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 400  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 500  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -49,6 +49,7 @@ __all__ = [
     "sparse_upols_convolver",
     "sparse_upola_convolver",
     "sparse_plan",
+    "sparse_window_plan",
     "sparse_convolve",
     "a_weighting",
     "amplitude_to_db",
@@ -882,6 +883,26 @@ def sparse_plan(mask, block_size: int) -> dict:
     return {"tile_mask": tm, "row_off": ro, "kept_bins": kb.value, "kept_tiles": kt.value}
 
 
+def sparse_window_plan(tile_mask, block_size: int, window: int) -> dict:
+    """The window bitmaps of a batched sparse pass of `window` blocks (a power of two, 2..32), on
+    the host (neo_hip_upols_sparse_window_plan; no device needed): `tile_mask` [C][P][NW] uint32
+    (sparse_plan's) -> `win_mask` [C][P][NW], row p the OR of tile_mask rows [p, min(P, p + window)):
+    the FDL tiles the row entering the pass at partition p is needed for; `window_tiles`, the sum
+    of its popcounts."""
+    nw = max(1, int(block_size) // 512)
+    tm = np.ascontiguousarray(tile_mask, dtype=np.uint32)
+    if tm.ndim == 2:
+        tm = tm[None]
+    if tm.ndim != 3 or tm.shape[2] != nw:
+        raise ValueError(f"tile_mask must be [C][P][{nw}], got {tm.shape}")
+    C, P, _ = tm.shape
+    wm = np.zeros_like(tm)
+    wt = ctypes.c_int64()
+    _native.check(_native.load().neo_hip_upols_sparse_window_plan(_ptr(tm), C, int(block_size), P, int(window),
+                                                                  _ptr(wm), ctypes.byref(wt)))
+    return {"win_mask": wm, "window_tiles": wt.value}
+
+
 def a_weighting(frequency):
     """neo::a_weighting (src/neo/math/a_weighting.hpp; extra/python/src/main.cpp:260-263): the
     A-weighting in dB at `frequency` Hz, vectorised, in the input's float dtype (float64 for
@@ -1069,9 +1090,11 @@ class SparseUpolsConvolver(UpolsConvolver):
     only the filter bins a mask keeps take part, kept as 128-byte tiles of 16 packed bins; a block
     step reads the kept tiles of the filter and of the FDL rows only. Results are those of the
     dense convolver on the filter with the dropped columns zeroed. Of `options` only fused and
-    split_workgroups apply; there are no streaming levels, batched passes, offline windows or
-    latency mode (their setters raise), and the dense forms filter(partitions) and
-    set_impulse(ir) do not apply: a sparse filter takes a mask or a PerceptualSparsity."""
+    split_workgroups apply; there are no streaming levels, offline windows or latency mode (their
+    setters raise), and the dense forms filter(partitions) and set_impulse(ir) do not apply: a
+    sparse filter takes a mask or a PerceptualSparsity. Batched passes are off by default (one
+    block per pass); set_batch(True) lets process_blocks / process run T blocks per pass over the
+    kept tiles, as an offline caller wants them (sparse_convolve does)."""
 
     def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
                  options: dict | None = None):
@@ -1183,6 +1206,15 @@ class SparseUpolsConvolver(UpolsConvolver):
                                                                ctypes.byref(fb)))
         return {"kept_bins": kb.value, "kept_tiles": kt.value, "filter_bytes": fb.value}
 
+    def sparse_batch_info(self) -> dict:
+        """The batched pass of this handle, on or off (neo_hip_upols_sparse_batch_info): its blocks
+        per pass T, its splits per channel, and the popcount sum of the window bitmaps the device
+        made for T at the last filter change (sparse_window_plan's `window_tiles`)."""
+        t, sp, wt = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols_sparse_batch_info(self._h, ctypes.byref(t), ctypes.byref(sp),
+                                                                     ctypes.byref(wt)))
+        return {"blocks_per_pass": t.value, "splits": sp.value, "window_tiles": wt.value}
+
 
 class sparse_upols_convolver:
     """Single-channel drop-in for sparse_upols_convolver<complex<float>> (sparse_convolver.hpp:
@@ -1234,7 +1266,8 @@ def sparse_convolve(signal, impulse_response, block_size: int, mask, method: str
     partition it, keep the filter bins `mask` ([C][P][B+1], true = keep, or a PerceptualSparsity:
     the plugin's own A-weighted threshold from sampleRate, thresholdDB and lowBinsToKeep, applied
     on the device) and run every block (tail zero-padded) through sparse_upola_convolver (or
-    sparse_upols_convolver) per channel; output truncated to N."""
+    sparse_upols_convolver) per channel; output truncated to N. Every block is known up front, so
+    the handle runs batched passes (T blocks per pass over the kept tiles)."""
     sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
     ir = np.array(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)), order="C")
     C, N = sig.shape
@@ -1248,6 +1281,7 @@ def sparse_convolve(signal, impulse_response, block_size: int, mask, method: str
         parts = uniform_partition(normalize_impulse(ir, device), block_size, device)
         conv = SparseUpolsConvolver(C, block_size, parts.shape[1], device, method=method, options=options)
         conv.filter(parts, mask)
+    conv.set_batch(True)
     nb = -(-N // block_size)
     buf = np.zeros((C, nb * block_size), dtype=np.float32)
     buf[:, :N] = sig
