@@ -567,81 +567,153 @@ __device__ __forceinline__ void toep_role(const slice_args& sa, const toep_arg& 
 // Toeplitz levels: slab[c][j][k] = sum_{p = a}^{b-1} H[c][p][k] X[c][(tw + j - p) mod R][k],
 // j < T, for the next window (toep_lds_role below). Complex MAC in two packed FMAs, the
 // splat / swap / sign folded into operand modifiers: acc += (hr, hr)(xr, xi) + (-hi, hi)(xi, xr).
+// Written as instructions: from __builtin_elementwise_fma the compiler folds the splat and the
+// swap but builds (-hi, hi) in a register pair of its own, two more VALU instructions per
+// partition. The low half of the second product takes hi negated (neg_lo), the same value.
 __device__ __forceinline__ void cmac_pk(f2v& acc, cf h, cf x)
 {
-    const f2v xv = {x.x, x.y};
-    acc = __builtin_elementwise_fma(f2v{h.x, h.x}, xv, acc);
-    acc = __builtin_elementwise_fma(f2v{-h.y, h.y}, xv.yx, acc);
+    const f2v hv = {h.x, h.y}, xv = {x.x, x.y};
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(acc) : "v"(hv), "v"(xv));
+    asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[1,0,0]" : "+v"(acc) : "v"(hv), "v"(xv));
 }
 
-template<bool BIN0>
-__device__ __forceinline__ void t32_step(f2v (&acc)[4], cf (&xw)[4], cf h, cf xn, bool z0)
+template<bool BIN0, int NO>
+__device__ __forceinline__ void t32_step(f2v (&acc)[NO], cf (&xw)[NO], cf h, cf xn, bool z0)
 {
-    xw[3] = xw[2];
-    xw[2] = xw[1];
-    xw[1] = xw[0];
+#pragma unroll
+    for (int o = NO - 1; o > 0; --o) xw[o] = xw[o - 1];
     xw[0] = xn;
     if constexpr (BIN0) {
         const pk_coef hk(h, z0);
 #pragma unroll
-        for (int o = 0; o < 4; ++o) hk.mac(acc[o], xw[o]);
+        for (int o = 0; o < NO; ++o) hk.mac(acc[o], xw[o]);
     } else {
 #pragma unroll
-        for (int o = 0; o < 4; ++o) cmac_pk(acc[o], h, xw[o]);
+        for (int o = 0; o < NO; ++o) cmac_pk(acc[o], h, xw[o]);
     }
 }
 
-// partitions m = m0 .. m1 - 1 (p = a + m, m0 even): output j0 + o (o < 4) meets FDL value
+// partitions m = m0 .. m1 - 1 (p = a + m, m0 even): output j0 + o (o < NO) meets FDL value
 // i = ib - m + o (ib = j0 + nb - 1), so each partition brings one new value, xc[ib - m], and
-// the other three slide over. Partition pairs (m, m + 1) come as one 16-B LDS read of the
+// the other NO - 1 slide over. Partition pairs (m, m + 1) come as one 16-B LDS read of the
 // filter column and one of the FDL column (xc is offset so that xc + ib - m - 1 is 16-B
-// aligned), four pairs per chunk with all their reads issued first.
-template<bool BIN0>
-__device__ __forceinline__ void t32_walk(const cf* hc, const cf* xc, int ib, int m0, int m1, bool z0, f2v (&acc)[4])
+// aligned): 2 reads per 4 NO packed FMAs. NO = 4 walks four pairs per chunk with all their
+// reads issued first. NO = 8 runs two pairs per chunk in two register sets, each chunk's reads
+// issued before the previous chunk's FMAs, so the waits are counted and a read has 64 FMAs to
+// land behind. The level is bound by VALU issue as much as by HBM, so the loop
+// is written for its instruction count: 8 partitions slide the window once round, and two
+// double chunks per trip let the register sets alternate, where one per trip copied 9 register
+// pairs at every back edge: 270 VALU instructions per 256 FMAs.
+template<bool BIN0, int NO>
+__device__ __forceinline__ void t32_walk(const cf* hc, const cf* xc, int ib, int m0, int m1, bool z0, f2v (&acc)[NO])
 {
-    constexpr int KP = 4;
-    cf xw[4];
+    static_assert(NO == 4 || NO == 8, "outputs per lane");
+    cf xw[NO];
 #pragma unroll
-    for (int o = 0; o < 3; ++o) xw[o] = xc[ib - m0 + 1 + o];
+    for (int o = 0; o < NO - 1; ++o) xw[o] = xc[ib - m0 + 1 + o];
     int m = m0;
-    for (; m + 2 * KP <= m1; m += 2 * KP) {
-        float4 h2[KP], x2[KP];
+    if constexpr (NO == 4) {
+        constexpr int KP = 4;
+        for (; m + 2 * KP <= m1; m += 2 * KP) {
+            float4 h2[KP], x2[KP];
 #pragma unroll
-        for (int i = 0; i < KP; ++i) {
-            h2[i] = *reinterpret_cast<const float4*>(hc + m + 2 * i);
-            x2[i] = *reinterpret_cast<const float4*>(xc + ib - (m + 2 * i) - 1);
+            for (int i = 0; i < KP; ++i) {
+                h2[i] = *reinterpret_cast<const float4*>(hc + m + 2 * i);
+                x2[i] = *reinterpret_cast<const float4*>(xc + ib - (m + 2 * i) - 1);
+            }
+#pragma unroll
+            for (int i = 0; i < KP; ++i) {
+                t32_step<BIN0, NO>(acc, xw, cf{h2[i].x, h2[i].y}, cf{x2[i].z, x2[i].w}, z0);
+                t32_step<BIN0, NO>(acc, xw, cf{h2[i].z, h2[i].w}, cf{x2[i].x, x2[i].y}, z0);
+            }
         }
+    } else {
+        constexpr int KP = 2;
+        const int n = (m1 - m0) / (4 * KP);  // double chunks
+        if (n > 0) {
+            const int ml = m0 + (n - 1) * 4 * KP;  // the last double chunk (its first half is read again past the end)
+            float4 ha[KP], xa[KP], hb[KP], xb[KP];
+            const auto rd = [&](float4 (&h2)[KP], float4 (&x2)[KP], int mm) {
 #pragma unroll
-        for (int i = 0; i < KP; ++i) {
-            t32_step<BIN0>(acc, xw, cf{h2[i].x, h2[i].y}, cf{x2[i].z, x2[i].w}, z0);
-            t32_step<BIN0>(acc, xw, cf{h2[i].z, h2[i].w}, cf{x2[i].x, x2[i].y}, z0);
+                for (int i = 0; i < KP; ++i) {
+                    h2[i] = *reinterpret_cast<const float4*>(hc + mm + 2 * i);
+                    x2[i] = *reinterpret_cast<const float4*>(xc + ib - (mm + 2 * i) - 1);
+                }
+            };
+            const auto go = [&](const float4 (&h2)[KP], const float4 (&x2)[KP]) {
+#pragma unroll
+                for (int i = 0; i < KP; ++i) {
+                    t32_step<BIN0, NO>(acc, xw, cf{h2[i].x, h2[i].y}, cf{x2[i].z, x2[i].w}, z0);
+                    t32_step<BIN0, NO>(acc, xw, cf{h2[i].z, h2[i].w}, cf{x2[i].x, x2[i].y}, z0);
+                }
+            };
+            const auto two = [&](int mm) {  // the scheduler keeps reads and FMAs in this order
+                rd(hb, xb, mm + 2 * KP);
+                __builtin_amdgcn_sched_barrier(0);
+                go(ha, xa);
+                __builtin_amdgcn_sched_barrier(0);
+                rd(ha, xa, mm + 4 * KP < ml ? mm + 4 * KP : ml);
+                __builtin_amdgcn_sched_barrier(0);
+                go(hb, xb);
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            rd(ha, xa, m);
+            int it = 0;
+            for (; it + 2 <= n; it += 2, m += 8 * KP) {  // two by two: the register sets alternate without copies
+                two(m);
+                two(m + 4 * KP);
+            }
+            if (it < n) {
+                two(m);
+                m += 4 * KP;
+            }
+        }
+        for (; m + 2 <= m1; m += 2) {
+            const float4 h2 = *reinterpret_cast<const float4*>(hc + m);
+            const float4 x2 = *reinterpret_cast<const float4*>(xc + ib - m - 1);
+            t32_step<BIN0, NO>(acc, xw, cf{h2.x, h2.y}, cf{x2.z, x2.w}, z0);
+            t32_step<BIN0, NO>(acc, xw, cf{h2.z, h2.w}, cf{x2.x, x2.y}, z0);
         }
     }
-    for (; m < m1; ++m) t32_step<BIN0>(acc, xw, hc[m], xc[ib - m], z0);
+    for (; m < m1; ++m) t32_step<BIN0, NO>(acc, xw, hc[m], xc[ib - m], z0);
 }
 
 // Toeplitz level with window T through LDS, for every level (band [a, b), b - a <= NB):
 // 32 / T units of 16 columns per workgroup, each with the whole window. A unit's filter rows
 // and the FDL rows they meet (b - a and b - a + T - 1 rows of 16 columns: its distinct data,
-// loaded once, coalesced) go to an LDS tile, column-major; lane (col, q4, half) then owns
-// outputs 4 q4 .. 4 q4 + 3 of its column over half of the band (t32_walk), and the halves
-// meet through LDS.
-template<int T, int NB, int JH>
+// loaded once, coalesced) go to an LDS tile, column-major; lane (col, part, group) then owns
+// outputs NO part .. NO part + NO - 1 of its column over one of NG equal groups of the band
+// (t32_walk), and the groups meet through LDS, summed in the order of the band.
+//   T = 32 (NO = 8): 4 parts x 4 groups of 48 partitions; JH = 2: 2 parts x 8 groups of 24
+//   T = 16 (NO = 4): 4 parts x 2 groups of 16
+// LDS banks of the walk's 16-B reads (ds_read_b128: bank = (byte address / 4) mod 64, served
+// in groups of 16 lanes, lanes {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} of every 32): a lane
+// covers 4 banks, so a group is conflict-free when its 16 addresses / 16 differ mod 16. The
+// column strides HS / 2 and XS / 2 (in 16-B units: 97 and 113 or 105 at T = 32, 17 and 25 at
+// T = 16) are odd, so 16 columns at one partition and one part differ. A lane group holds
+// columns 0-3, 12-15 of one 16-lane row and 4-11 of the next: with (part, group) taken from
+// the plain row, the second row's reads sit 4 units (NO = 8: 8 outputs) or 2 units (NO = 4)
+// beside the first row's in the FDL columns and meet them 2-way on 4 or 2 columns. So the walk
+// swaps the two rows' roles for columns 4-11 (row ^ 1): every lane group then holds 16
+// columns of one row, in the filter reads and the FDL reads alike.
+template<int T, int NB, int JH, int NO>
 struct toep_tile {
     static constexpr int UPW = 32 / T, LPU = 256 / UPW, NQ = LPU / 16;  // units per workgroup, lanes per unit
-    static constexpr int TP = T / JH, QUADS = TP / 4, NG = NQ / QUADS;  // outputs per unit, lanes per column, band groups
+    static constexpr int TP = T / JH, PARTS = TP / NO, NG = NQ / PARTS;  // outputs per unit, lanes per column, band groups
     static constexpr int HS = NB + 2, XS = NB + TP + 2;                 // even column strides (16-B aligned pair reads)
     static constexpr int NH = (NB + NQ - 1) / NQ, NXL = (NB + TP - 1 + NQ - 1) / NQ;
     static constexpr int LDS = UPW * 16 * (HS + XS) * int(sizeof(cf));
-    static_assert(NG >= 2 && NQ % QUADS == 0 && TP % 4 == 0, "toeplitz tile geometry");
+    static_assert(NG >= 2 && NQ % PARTS == 0 && TP % NO == 0 && NQ % 2 == 0, "toeplitz tile geometry");
+    static_assert(HS / 2 % 2 == 1 && XS / 2 % 2 == 1, "odd column strides in 16-B units: conflict-free pair reads");
+    static_assert(UPW * NG * 16 * PARTS * NO * int(sizeof(f2v)) <= LDS, "the groups' partial sums fit the freed tile");
 };
 
 // unit u = (column group u / JH, window part u mod JH of T / JH outputs); JH = 2 where a step
 // has few units (one channel: the part halves the longest chain of the step)
-template<int T, int NB, int JH>
+template<int T, int NB, int JH, int NO>
 __device__ __forceinline__ void toep_lds_role(const slice_args& sa, const toep_arg& ta, int bid, char* smem)
 {
-    using G = toep_tile<T, NB, JH>;
+    using G = toep_tile<T, NB, JH, NO>;
     static_assert(G::LDS <= kSliceLds, "toeplitz tile");
     const int t = threadIdx.x, us = t / G::LPU, lt = t % G::LPU, col = lt & 15, q = lt >> 4;
     cf* hs = reinterpret_cast<cf*>(smem) + us * 16 * (G::HS + G::XS);  // hs[col][m] = H[p = a + m]
@@ -692,32 +764,37 @@ __device__ __forceinline__ void toep_lds_role(const slice_args& sa, const toep_a
     }
     __syncthreads();
     NEO_TL_MARK(sa);
-    // lane (col, quad, group): outputs 4 quad .. 4 quad + 3 of the part, partitions of band group
-    const int grp = q / G::QUADS, j0 = 4 * (q - grp * G::QUADS), nq = ((nb + G::NG - 1) / G::NG + 1) & ~1;
+    // lane (col, part, group), the rows of columns 4-11 swapped in pairs (toep_tile): outputs
+    // NO part .. NO part + NO - 1 of the unit, partitions of band group
+    const int qw = q ^ (((col + 4) >> 3) & 1);
+    const int grp = qw / G::PARTS, part = qw - grp * G::PARTS, j0 = NO * part, nq = ((nb + G::NG - 1) / G::NG + 1) & ~1;
     const int m0 = grp * nq < nb ? grp * nq : nb, m1 = m0 + nq < nb ? m0 + nq : nb;
-    f2v acc[4] = {f2v(0.f), f2v(0.f), f2v(0.f), f2v(0.f)};
+    f2v acc[NO];
+#pragma unroll
+    for (int o = 0; o < NO; ++o) acc[o] = f2v(0.f);
     const cf* hc = hs + col * G::HS;
     const cf* xc = xs + col * G::XS + odd;
     if (live && m0 < m1) {
-        if (g == 0) t32_walk<true>(hc, xc, j0 + nb - 1, m0, m1, col == 0, acc);  // uniform per unit
-        else t32_walk<false>(hc, xc, j0 + nb - 1, m0, m1, false, acc);
+        if (g == 0) t32_walk<true, NO>(hc, xc, j0 + nb - 1, m0, m1, col == 0, acc);  // uniform per unit
+        else t32_walk<false, NO>(hc, xc, j0 + nb - 1, m0, m1, false, acc);
     }
-    __syncthreads();  // the tiles are free: the band groups meet there
-    constexpr int LG = 16 * G::QUADS;          // lanes per band group
-    f2v* red = reinterpret_cast<f2v*>(smem);  // [units][NG - 1][LG][4]
-    const int lg = lt - grp * LG;
-    if (grp) {
+    __syncthreads();  // the tiles are free: the band groups meet there, and group r sums and
+                      // stores outputs r OPG .. of every lane's NO, each in the order of the band
+    constexpr int LG = 16 * G::PARTS, OPG = NO / G::NG;  // lanes per band group, outputs per lane of the sum
+    static_assert(NO % G::NG == 0, "the groups share the sum");
+    f2v* red = reinterpret_cast<f2v*>(smem) + us * G::NG * NO * LG;  // [units][NG][NO][LG]
+    const int lg = part * 16 + col;
 #pragma unroll
-        for (int o = 0; o < 4; ++o) red[((us * (G::NG - 1) + grp - 1) * LG + lg) * 4 + o] = acc[o];
-    }
+    for (int o = 0; o < NO; ++o) red[(grp * NO + o) * LG + lg] = acc[o];
     __syncthreads();
-    if (!grp && live) {
-        cf* o = ta.slab + int64_t(c) * ta.cs + int64_t(jpart + j0) * sa.B + k;
+    if (live) {
+        const int o0 = grp * OPG;
+        cf* o = ta.slab + int64_t(c) * ta.cs + int64_t(jpart + j0 + o0) * sa.B + k;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            f2v v = acc[i];
+        for (int i = 0; i < OPG; ++i) {
+            f2v v = red[(o0 + i) * LG + lg];
 #pragma unroll
-            for (int r = 1; r < G::NG; ++r) v += red[((us * (G::NG - 1) + r - 1) * LG + lg) * 4 + i];
+            for (int r = 1; r < G::NG; ++r) v += red[(r * NO + o0 + i) * LG + lg];
             o[int64_t(i) * sa.B] = cf{v.x, v.y};
         }
     }
@@ -780,8 +857,8 @@ __device__ __forceinline__ void toep_big_role(const slice_args& sa, const toep_a
         if (m0 < m1) {
             const cf* hc = hs + col * kBigHS;
             const cf* xc = xs + col * kBigXS + odd;
-            if (g == 0) t32_walk<true>(hc, xc, nc - 1 + 4 * quad, m0, m1, col == 0, acc);  // uniform branch
-            else t32_walk<false>(hc, xc, nc - 1 + 4 * quad, m0, m1, false, acc);
+            if (g == 0) t32_walk<true, 4>(hc, xc, nc - 1 + 4 * quad, m0, m1, col == 0, acc);  // uniform branch
+            else t32_walk<false, 4>(hc, xc, nc - 1 + 4 * quad, m0, m1, false, acc);
         }
     }
     __syncthreads();  // the tile is free: the quarters meet there
@@ -1409,11 +1486,11 @@ __device__ __forceinline__ bool toep_level(const slice_args& a, int& bid, char* 
     } else if constexpr (L == 1) {
         if (NEO_ROLES & 2) toep_role<8, 16, 1, 1>(a, ta, bid, smem);
     } else if constexpr (L == 2) {
-        if (NEO_ROLES & 2) toep_lds_role<16, 32, 1>(a, ta, bid, smem);
+        if (NEO_ROLES & 2) toep_lds_role<16, 32, 1, 4>(a, ta, bid, smem);
     } else if constexpr (L == 3) {
         if (NEO_ROLES & 4) {
-            if (ta.jh == 2) toep_lds_role<32, kT32Band, 2>(a, ta, bid, smem);  // uniform per launch
-            else toep_lds_role<32, kT32Band, 1>(a, ta, bid, smem);
+            if (ta.jh == 2) toep_lds_role<32, kT32Band, 2, 8>(a, ta, bid, smem);  // uniform per launch
+            else toep_lds_role<32, kT32Band, 1, 8>(a, ta, bid, smem);
         }
     } else {
         if (NEO_ROLES & 4) toep_big_role(a, ta, bid, smem);
