@@ -547,6 +547,93 @@ private:
 };
 
 namespace detail {
+struct matrix_deleter {
+    void operator()(neo_hip_matrix* m) const noexcept { neo_hip_matrix_destroy(m); }
+};
+}  // namespace detail
+
+/// A route of a matrix convolver: output `out` takes input `in` through a filter of its own.
+struct matrix_route {
+    int out;
+    int in;
+};
+
+/// Matrix (multi-input, multi-output) convolver over libneo_hip's neo_hip_matrix_* (include/neo_hip.h):
+/// output o = the sum over its routes (o, i) of what upols_convolver (M = method::upols) or
+/// upola_convolver (M = method::upola) gives for (input i, that route's filter). The reference has
+/// no such class; it is the routed form of its per-channel convolvers. One delay line per input,
+/// one inverse transform per output. Construction and filter() throw std::runtime_error; the call
+/// operator is noexcept like its neighbours.
+template<method M>
+struct hip_matrix_convolver {
+    static_assert(M == method::upols || M == method::upola, "matrix convolvers: upols or upola");
+
+    /// opts nullptr = all defaults (neo_hip_matrix_opts: fused, split_workgroups, out_tile)
+    hip_matrix_convolver(std::size_t inputs, std::size_t outputs, std::size_t block_size, std::size_t partitions,
+                         neo_hip_matrix_opts const* opts = nullptr, int device = neo::hip::detail::default_device())
+        : _I{inputs}, _O{outputs}, _B{block_size}, _P{partitions}
+    {
+        neo_hip_matrix* m = nullptr;
+        neo::hip::check(neo_hip_matrix_create(int(inputs), int(outputs), int(block_size), int(partitions), device,
+                                              M == method::upola ? 1 : 0, opts, &m));
+        _h.reset(m);
+    }
+
+    /// partitions [routes][P][B+1] in uniform_partition layout (host memory), one per route in the
+    /// list's order; resets all state like filter() everywhere else
+    auto filter(std::complex<float> const* partitions, std::vector<matrix_route> const& routes) -> void
+    {
+        std::vector<int> ro(routes.size()), ri(routes.size());
+        for (std::size_t r = 0; r < routes.size(); ++r) ro[r] = routes[r].out, ri[r] = routes[r].in;
+        neo::hip::check(neo_hip_matrix_set_filter(_h.get(), partitions, ro.data(), ri.data(), int(routes.size()), 0));
+    }
+
+    /// the dense matrix: partitions [O][I][P][B+1], every output fed by every input
+    auto filter(std::complex<float> const* partitions) -> void
+    {
+        std::vector<matrix_route> all;
+        for (std::size_t o = 0; o < _O; ++o)
+            for (std::size_t i = 0; i < _I; ++i) all.push_back({int(o), int(i)});
+        filter(partitions, all);
+    }
+
+    /// one block: in [I][B] -> out [O][B], host memory, complete on return; the two may be the same buffer
+    auto operator()(float const* in, float* out) noexcept -> void
+    {
+        neo::hip::check_or_abort(
+            neo_hip_matrix_process(_h.get(), in, std::int64_t(_B), out, std::int64_t(_B), 1, 0, nullptr));
+    }
+
+    /// num_blocks blocks: input i at in + i ld_in, output o at out + o ld_out (throws on bad strides)
+    auto process(float const* in, std::size_t ld_in, float* out, std::size_t ld_out, std::size_t num_blocks,
+                 bool device_memory = false, void* stream = nullptr) -> void
+    {
+        neo::hip::check(neo_hip_matrix_process(_h.get(), in, std::int64_t(ld_in), out, std::int64_t(ld_out),
+                                               std::int64_t(num_blocks), device_memory ? 1 : 0, stream));
+    }
+
+    auto reset() -> void { neo::hip::check(neo_hip_matrix_reset(_h.get())); }
+
+    [[nodiscard]] auto info() const -> neo_hip_matrix_desc
+    {
+        neo_hip_matrix_desc d{};
+        neo::hip::check(neo_hip_matrix_info(_h.get(), &d));
+        return d;
+    }
+    [[nodiscard]] auto inputs() const noexcept { return _I; }
+    [[nodiscard]] auto outputs() const noexcept { return _O; }
+    [[nodiscard]] auto block_size() const noexcept { return _B; }
+    [[nodiscard]] auto partitions() const noexcept { return _P; }
+
+private:
+    std::unique_ptr<neo_hip_matrix, detail::matrix_deleter> _h;
+    std::size_t _I, _O, _B, _P;
+};
+
+using upols_matrix_convolver = hip_matrix_convolver<method::upols>;
+using upola_matrix_convolver = hip_matrix_convolver<method::upola>;
+
+namespace detail {
 struct group_deleter {
     void operator()(neo_hip_upols_group* g) const noexcept { neo_hip_upols_group_destroy(g); }
 };

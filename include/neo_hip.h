@@ -78,8 +78,9 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.3.0: the sparse convolvers (neo_hip_upols_create_sparse and what goes with it).
  * 0.4.0: the perceptual sparsity predicate (neo_hip_perceptual_* and the two handle calls).
  * 0.5.0: batched passes on sparse handles (set_batch(1) accepted; neo_hip_upols_sparse_window_plan,
- *        neo_hip_upols_sparse_batch_info). */
-#define NEO_HIP_VERSION 500 /* 0.5.0 */
+ *        neo_hip_upols_sparse_batch_info).
+ * 0.6.0: the matrix convolver (neo_hip_matrix_*). */
+#define NEO_HIP_VERSION 600 /* 0.6.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -474,6 +475,87 @@ NEO_HIP_API int neo_hip_upols_group_unregister(neo_hip_upols_group* g, const voi
 /* coalesced now; one-launch frame steps, member calls, block re-runs, mode switches so far */
 NEO_HIP_API int neo_hip_upols_group_stats(neo_hip_upols_group* g, int* coalesced, int64_t* frame_steps, int64_t* calls,
                                           int64_t* redos, int64_t* switches);
+/* -- Matrix (multi-input, multi-output) convolver (upols_matrix.hip) ---------------------------
+ * I inputs, O outputs and a list of ROUTES: a route is a pair (out, in) with a filter [P][B+1]
+ * complex in uniform_partition layout. Output o is the sum over its routes of what the reference's
+ * upols_convolver (method 0) / upola_convolver (method 1) gives for (x_in, that route's filter);
+ * the reference itself has no such class (its plugin runs one convolver per channel,
+ * extra/plugin/src/dsp/DenseConvolution.hpp:35). The route list is unique pairs in any order (the
+ * results do not depend on the order); a dense matrix is the list of all O * I pairs. An output
+ * with no route produces zeros, and an input reaches only the outputs it has a route to (an Inf or
+ * NaN in it does not touch the others); an input with no route is accepted. Overlap-save keeps its window
+ * state per input, overlap-add its overlap tail per output. One delay line per input serves every
+ * output, the sum over the inputs is taken on spectra, and there is one inverse transform per
+ * output. A block step is two launches: the inputs' windows and transforms, then the plain step's
+ * MAC over (tiles of outputs) x (splits of the tile's rows), where a TILE is up to out_tile
+ * consecutive outputs that share each FDL row load. Equal calls with equal options give equal bits.
+ * Batching, streaming levels, offline windows, latency mode, sub-block input (method 2), groups and
+ * the multi-device convolver do not apply to this handle type; for very long filters (from 256
+ * partitions at 512 routes and more) O * I replicated channels on a neo_hip_upols handle
+ * with streaming levels remain the faster form. */
+typedef struct neo_hip_matrix neo_hip_matrix;
+typedef struct neo_hip_matrix_opts {
+    int fused;            /* -1 auto (one MAC launch with the last-arriver tail up to 64 workgroups, tiles x splits),
+                             0 MAC + finish, 1 the last split of a tile to arrive runs its tails */
+    int split_workgroups; /* 0 auto (about 1024 workgroups, >= 8 rows per split; 16 for the fused form up to
+                             B = 512), else the workgroup target for the splits, taken as given (up to 64 per tile) */
+    int out_tile;         /* outputs per workgroup: 0 auto (4 at B = 512 for 8 tiles or more whose outputs all take
+                             every input of their tile, from 2048 rows per tile: the measured range, DESIGN
+                             5.8; otherwise 1), else 1, 2 or 4; clamped to 4 for B <= 512, 2 for
+                             B = 1024 and 1 above (the accumulators of a tile stay in registers); info and plan
+                             report the value in use */
+} neo_hip_matrix_opts;
+/* method 0 = overlap-save, 1 = overlap-add (2 is EINVAL); opts NULL = all defaults. The shape, the
+ * method and the options are checked before a device is touched. */
+NEO_HIP_API int neo_hip_matrix_create(int inputs, int outputs, int block, int partitions, int device, int method,
+                                      const neo_hip_matrix_opts* opts, neo_hip_matrix** m);
+NEO_HIP_API int neo_hip_matrix_destroy(neo_hip_matrix* m);
+/* filter [nroutes][P][B+1] complex, host or device memory; route r = (route_out[r], route_in[r]),
+ * both arrays ALWAYS in host memory. A duplicate route, an index out of range or nroutes < 1 is
+ * EINVAL and leaves the handle as it was. Resets all state, like filter(). The call waits on the
+ * handle's stream only. */
+NEO_HIP_API int neo_hip_matrix_set_filter(neo_hip_matrix* m, const void* filter, const int* route_out,
+                                          const int* route_in, int nroutes, int is_device);
+/* ir [nroutes][length] float, host or device memory: normalize_impulse over all routes' rows (one
+ * factor, as neo_hip_upols_set_impulse takes it over channels) if `normalize`, then
+ * uniform_partition on the device; otherwise as set_filter. */
+NEO_HIP_API int neo_hip_matrix_set_impulse(neo_hip_matrix* m, const float* ir, int64_t length, const int* route_out,
+                                           const int* route_in, int nroutes, int normalize, int is_device);
+/* nblocks consecutive single-block steps: input i at in + i*ld_in, output o at out + o*ld_out, block
+ * t of either at + t*B. Device memory: asynchronous on `stream` (NULL = the HIP null stream), both
+ * pointers 16-byte aligned, ld_in and ld_out multiples of 4; host memory: staged, synchronous (the
+ * handle's stream if `stream` is NULL), any alignment. ld_in and ld_out >= nblocks * B. A refused
+ * call (EINVAL) leaves the state as it was. Every read of a block of `in` happens before the first
+ * write of that block of `out`, so in == out (same strides, I == O) is allowed, and for one block
+ * the two may overlap in any way. EINVAL before the first set_filter / set_impulse. */
+NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64_t ld_in, float* out, int64_t ld_out,
+                                       int64_t nblocks, int is_device, void* stream);
+NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m);
+/* what the handle runs; routes, tiles, out_tile, splits, fused and filter_bytes are 0 until a filter is set */
+typedef struct neo_hip_matrix_desc {
+    int inputs, outputs, block, partitions, method;
+    int routes, tiles, out_tile, splits, fused;
+    int64_t filter_bytes; /* [routes][P][B] packed */
+    int64_t fdl_bytes;    /* [inputs][P][B] */
+} neo_hip_matrix_desc;
+NEO_HIP_API int neo_hip_matrix_info(neo_hip_matrix* m, neo_hip_matrix_desc* desc);
+/* The plan for a route list and options, on the host (no device needed; the handle is built from
+ * the same function). Consecutive outputs form tiles of out_tile; a tile's row list is the union
+ * of its outputs' inputs (ascending) x partitions 0..P-1, flattened, and split s of the S splits
+ * walks rows [cuts[s], cuts[s + 1]) of it. Per step the MAC launch loads fdl_row_loads FDL rows
+ * (the sum of the tiles' row counts) and filter_row_loads filter rows (routes x P) of 8 B bytes
+ * each; the algorithmic bytes of a step are 8 B (fdl_row_loads + filter_row_loads) plus the block
+ * I/O. Arrays (each may be NULL): tile_first, tile_count, tile_rows [outputs]; union_off
+ * [outputs + 1] and union_in [outputs * inputs] (tile t's inputs are union_in[union_off[t] ..
+ * union_off[t + 1])); cuts [outputs][65] (row 65 t + s). Only the first `tiles` rows are written. */
+typedef struct neo_hip_matrix_plan_info {
+    int out_tile, fused, splits, tiles;
+    int64_t fdl_row_loads, filter_row_loads;
+} neo_hip_matrix_plan_info;
+NEO_HIP_API int neo_hip_matrix_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                    const int* route_in, int nroutes, const neo_hip_matrix_opts* opts,
+                                    neo_hip_matrix_plan_info* plan, int* tile_first, int* tile_count, int* tile_rows,
+                                    int* union_off, int* union_in, int* cuts);
 /* Kernel timing with HIP events recorded on the launch stream (for the roofline in
  * bench.py): enable = n > 0 brackets every n-th launch group with events (0 = off).
  * timing() returns the summed ms of the bracketed part and the count of timed groups:

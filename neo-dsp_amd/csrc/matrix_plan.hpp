@@ -1,0 +1,127 @@
+// matrix_plan.hpp — the host-side plan of a matrix convolver (upols_matrix.hip): which outputs
+// share a workgroup, which FDL rows each of those workgroups walks, and where its splits cut.
+// Plain C++, no device: neo_hip_matrix_plan returns it and the handle is built from the same call.
+#pragma once
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace neo_hip {
+
+// The most workgroups (tiles x splits) for which the MAC launch also runs the tails: each workgroup's
+// agent-scope release ahead of the arrival counter costs more than the second launch once there are
+// many (tools/matrix_sweep.py at B = 512: ahead at 2 .. 64 workgroups, level at 126 and
+// 128, behind from 256 on, up to 2.6 x). The dense step's rule, 64 MiB of filter + FDL, is too wide here.
+constexpr int kMatrixFusedMaxWgs = 64;
+constexpr int kMatrixMaxSplits = 64;
+
+// the most outputs one workgroup accumulates: OT VPT <= 4 float4 accumulator pairs per lane
+constexpr int matrix_max_tile(int B) { return B <= 512 ? 4 : B == 1024 ? 2 : 1; }
+
+// The automatic out_tile is 4 where the sweep has it ahead of 1 by more than the spread of the same
+// A/B (tools/matrix_sweep.py, B = 512): tiles whose outputs all take every input of the
+// tile's union (dense 8 x 32 and 32 x 32: 8 tiles) with at least 2048 rows in the longest tile,
+// -3 .. -10 %; below that many rows a tile of 1 is level or up to 13 % ahead, and so it is for the
+// banded matrix (8 of a tile's 11 inputs per output) up to 2816 rows and for 2 x 2 (one tile: too few
+// workgroups) at any length. Other block sizes are not measured: 1.
+constexpr int kMatrixAutoTileBlock = 512;
+constexpr int kMatrixAutoTileRows = 2048;
+constexpr int kMatrixAutoTileTiles = 8;
+
+struct matrix_plan {
+    int I = 0, O = 0, B = 0, P = 0, nroutes = 0;
+    int OT = 1, S = 1, ntiles = 0;
+    bool fused = true;
+    std::vector<int> rt;          // [O][I]: the route (index into the caller's list) or -1
+    std::vector<int> tile_first;  // [ntiles] first output
+    std::vector<int> tile_count;  // [ntiles] outputs (<= OT)
+    std::vector<int> uni_off;     // [ntiles + 1] into uni
+    std::vector<int> uni;         // the tiles' inputs, ascending per tile
+    int64_t fdl_loads = 0, filter_loads = 0;  // row loads per step
+    int rows(int t) const { return (uni_off[size_t(t) + 1] - uni_off[size_t(t)]) * P; }
+    // split s of tile t walks rows [cut(t, s), cut(t, s + 1)) of the tile's list
+    int cut(int t, int s) const
+    {
+        const int n = rows(t), per = (n + S - 1) / S;
+        return std::min<int64_t>(n, int64_t(s) * per);
+    }
+};
+
+// Checks the shape and the route list (why != nullptr: the reason) and fills the plan.
+// fused: -1 auto, 0, 1; split_wgs: 0 auto, else the workgroup target; out_tile: 0 auto, 1, 2, 4.
+inline const char* make_matrix_plan(int I, int O, int B, int P, const int* route_out, const int* route_in, int nroutes,
+                                    int fused, int split_wgs, int out_tile, matrix_plan& pl)
+{
+    if (I < 1 || O < 1) return "inputs and outputs must be >= 1";
+    if (B < 16 || B > 4096 || (B & (B - 1))) return "block must be a power of two in [16, 4096]";
+    if (P < 1) return "partitions must be >= 1";
+    if (int64_t(P) * B * 8 >= (int64_t(1) << 31)) return "a route's filter must span < 2 GiB";
+    if (nroutes < 1) return "nroutes must be >= 1";
+    if (!route_out || !route_in) return "null route list";
+    if (int64_t(I) * O > (int64_t(1) << 26)) return "inputs x outputs too large";
+    if (fused < -1 || fused > 1 || split_wgs < 0 || (out_tile != 0 && out_tile != 1 && out_tile != 2 && out_tile != 4))
+        return "invalid options (fused -1 / 0 / 1, split_workgroups >= 0, out_tile 0 / 1 / 2 / 4)";
+    pl = matrix_plan{};
+    pl.I = I, pl.O = O, pl.B = B, pl.P = P, pl.nroutes = nroutes;
+    pl.rt.assign(size_t(I) * size_t(O), -1);
+    for (int r = 0; r < nroutes; ++r) {
+        const int o = route_out[r], i = route_in[r];
+        if (o < 0 || o >= O || i < 0 || i >= I) return "route index out of range";
+        if (pl.rt[size_t(o) * I + i] >= 0) return "duplicate route";
+        pl.rt[size_t(o) * I + i] = r;
+    }
+    // consecutive outputs in tiles of ot; returns the (output, union input) pairs of all tiles, which
+    // equal the route count iff every output of a tile has a route from every input of its union
+    auto tiles = [&](int ot) {
+        pl.OT = ot;
+        pl.ntiles = (O + ot - 1) / ot;
+        pl.tile_first.clear(), pl.tile_count.clear(), pl.uni.clear();
+        pl.uni_off.assign(1, 0);
+        pl.fdl_loads = 0;
+        int64_t pairs = 0;
+        for (int t = 0; t < pl.ntiles; ++t) {
+            const int first = t * ot, count = std::min(ot, O - first);
+            pl.tile_first.push_back(first);
+            pl.tile_count.push_back(count);
+            for (int i = 0; i < I; ++i) {
+                bool any = false;
+                for (int o = first; o < first + count; ++o) any = any || pl.rt[size_t(o) * I + i] >= 0;
+                if (any) pl.uni.push_back(i);
+            }
+            pl.uni_off.push_back(int(pl.uni.size()));
+            const int nu = pl.uni_off[size_t(t) + 1] - pl.uni_off[size_t(t)];
+            pl.fdl_loads += int64_t(nu) * P;
+            pairs += int64_t(nu) * count;
+        }
+        return pairs;
+    };
+    auto longest = [&] {
+        int n = 1;
+        for (int t = 0; t < pl.ntiles; ++t) n = std::max(n, pl.rows(t));
+        return n;
+    };
+    if (out_tile) {
+        tiles(std::min(out_tile, matrix_max_tile(B)));
+    } else if (!(B == kMatrixAutoTileBlock && tiles(4) == nroutes && pl.ntiles >= kMatrixAutoTileTiles &&
+                 longest() >= kMatrixAutoTileRows)) {
+        tiles(1);
+    }
+    pl.filter_loads = int64_t(nroutes) * P;
+    // splits: the plain step's rule (about 1024 workgroups, >= 8 rows per split, 16 for the one-launch
+    // form up to B = 512; an explicit workgroup target is taken as given), on the longest tile
+    const int maxrows = longest();
+    auto splits = [&](bool fu) {
+        const int target = split_wgs ? split_wgs : 1024;
+        const int min_rows = split_wgs ? 1 : fu ? (B > 512 ? 8 : 16) : 8;
+        const int S = std::max(1, std::min({(target + pl.ntiles - 1) / pl.ntiles, (maxrows + min_rows - 1) / min_rows,
+                                            kMatrixMaxSplits}));
+        const int per = (maxrows + S - 1) / S;
+        return (maxrows + per - 1) / per;  // no empty split in the longest tile
+    };
+    pl.fused = fused >= 0 ? fused != 0 : int64_t(pl.ntiles) * splits(true) <= kMatrixFusedMaxWgs;
+    pl.S = splits(pl.fused);
+    return nullptr;
+}
+
+}  // namespace neo_hip

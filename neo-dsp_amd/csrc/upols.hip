@@ -378,12 +378,18 @@ int launch_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t 
 
 int neo_hip::launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s)
 {
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, true>), dim3(unsigned(h->C)), dim3(256), 0,
-                                                    s, h->part, out, ld_out, h->prev, h->tw, h->S))
+    return launch_finish_slabs(h->C, h->B, h->S, h->ola, h->part, out, ld_out, h->prev, h->tw, s);
+}
+
+int neo_hip::launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, float* out, int64_t ld_out, float* ovl,
+                                 const cf* tw, hipStream_t s)
+{
+    if (ola) {
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_upols_finish<BB, true>), dim3(unsigned(C)), dim3(256), 0, s, part,
+                                                 out, ld_out, ovl, tw, S))
     } else {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_finish<BB, false>), dim3(unsigned(h->C)), dim3(256),
-                                                    0, s, h->part, out, ld_out, h->prev, h->tw, h->S))
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_upols_finish<BB, false>), dim3(unsigned(C)), dim3(256), 0, s, part,
+                                                 out, ld_out, ovl, tw, S))
     }
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;

@@ -354,6 +354,10 @@ int perceptual_mask_device(const cf* filter, int C, int B, int P, const neo_hip_
                            uint8_t* mask, float** tmp, hipStream_t s);
 // upols.hip: the unfused step's second launch (k_upols_finish: slabs summed in order, c2r)
 int launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s);
+// the same launch on plain arguments (upols_matrix.hip: one "channel" per output): slabs part [C][S][B],
+// ovl [C][B] the overlap-add tails (not read by overlap-save)
+int launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, float* out, int64_t ld_out, float* ovl,
+                        const cf* tw, hipStream_t s);
 // upols_batch.hip: T whole blocks in one pass over the filter and the FDL
 int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch

@@ -1,0 +1,600 @@
+// upols_matrix.hip — matrix (multi-input, multi-output) partitioned convolver: output o is the sum
+// over its routes (o, i) of what upols_convolver / upola_convolver gives for (x_i, h[o][i])
+// (src/neo/convolution/uniform_partitioned_convolver.hpp:13-65 applied route by route). The
+// reference has no such class (its plugin runs one convolver per channel); the structure it saves
+// is the frequency-domain one: ONE delay line per input serves every output, the sum over the
+// inputs is taken on spectra, so there is ONE inverse transform per output.
+//
+// Device layout (HBM), packed rows of B complex with bin 0 = {DC, Nyquist} as in upols.hip:
+//   H    [nroutes][P][B]  the routes' filters, in the caller's route order
+//   FDL  [I][R][B]        one ring per input, R = P rows, write position w
+//   prev [I][B]           overlap-save: the input's previous block
+//   ovl  [O][B]           overlap-add: the output's overlap tail
+//   part [O][S][B]        per-split partial spectra; arrivals [tiles]
+//
+// A block step is two launches:
+//   k_matrix_window  one workgroup per input: window update, packed r2c, FDL row w. Every read of
+//                    the caller's input happens here, so `in` and `out` may overlap.
+//   k_matrix_step    grid tiles x S. A tile is up to OT consecutive outputs; its row list is the
+//                    union of their inputs (ascending) x partitions 0..P-1, cut into S splits at
+//                    equal row counts (matrix_plan.hpp). Per row (i, p) a lane loads the FDL row
+//                    (w - p) mod R of input i ONCE and one filter row per output of the tile. An
+//                    output without a route from i reads through a buffer descriptor of size zero:
+//                    the load moves no data, and a uniform branch leaves its accumulators alone.
+//                    Splits publish a slab per output; the tile's last split to arrive (FUSED) or
+//                    k_upols_finish sums them in the order s = 0..S-1 and runs the c2r tails.
+#include "matrix_plan.hpp"
+#include "upols_handle.hpp"
+#include "upols_step.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+struct neo_hip_matrix {
+    int device = 0, I = 0, O = 0, B = 0, P = 0, ring = 0;
+    bool ola = false;
+    int o_fused = -1, o_split = 0, o_tile = 0;  // the options as given (the plan follows the routes)
+    hipStream_t stream = nullptr;
+    neo_hip::cf* tw = nullptr;
+    neo_hip::cf* fdl = nullptr;  // [I][R][B]
+    float* prev = nullptr;       // [I][B]
+    float* ovl = nullptr;        // [O][B]
+    int wpos = 0;
+    // with the filter (set_filter / set_impulse)
+    bool ready = false;
+    neo_hip::matrix_plan plan;
+    neo_hip::cf* H = nullptr;     // [nroutes][P][B]
+    neo_hip::cf* part = nullptr;  // [O][S][B]
+    int* arrivals = nullptr;      // [tiles]
+    int* tab = nullptr;           // tiles [ntiles][4] {first, count, inputs, offset into uni}, uni, rt [O][I]
+    neo_hip::stream_set used;
+};
+
+namespace neo_hip {
+
+using matrix_t = neo_hip_matrix;
+
+// rows in flight per lane and workgroups per CU: one output per workgroup is the dense plain step
+// (U rows, 2 loads each = 8 loads in flight, 8 waves per SIMD up to B = 1024); more outputs keep
+// OT + 1 loads per row (9, 10 or 12 in flight) and OT accumulator sets. Those kernels are pinned to
+// 4 waves per SIMD (amdgpu_waves_per_eu(4, 4)): a launch bound alone is a lower bound on occupancy,
+// and left to itself the compiler took 62-68 registers for 7-8 waves and issued the loads of a
+// row group three at a time with a wait between them.
+template<int B, int OT>
+constexpr int matrix_unroll()
+{
+    using K = upols_cfg<B>;
+    if (OT == 1) return K::U;
+    return K::VPT >= 2 ? 2 : OT == 2 ? 3 : 2;
+}
+template<int B, int OT>
+constexpr int matrix_wgs() { return B > 1024 ? 2 : OT == 1 ? 8 : 4; }
+
+template<int B, bool OLA>
+__global__ __launch_bounds__(256) void k_matrix_window(const float* __restrict__ in, int64_t ld_in,
+                                                       float* __restrict__ prev, cf* __restrict__ fdl,
+                                                       const cf* __restrict__ twg, int ring, int w)
+{
+    using K = upols_cfg<B>;
+    __shared__ cf fft[K::LL];
+    __shared__ cf tw[K::TW1 + K::TW2];
+    const int tid = threadIdx.x, i = blockIdx.x;
+    const float* in_i = in + int64_t(i) * ld_in;
+    float* prev_i = prev + int64_t(i) * B;
+    window_fft<B, OLA>(prev_i, in_i, fft, tw, tid, twg);
+    cf* row = fdl + (int64_t(i) * ring + w) * B;
+    for (int k = tid; k < B; k += 256) row[k] = r2c_split<B>(fft, tw + K::TW1, k);
+    if constexpr (!OLA) {  // the window's second half becomes the next call's first half
+        for (int k = tid; k < B / 4; k += 256)
+            reinterpret_cast<float4*>(prev_i)[k] = reinterpret_cast<const float4*>(in_i)[k];
+    }
+}
+
+template<int B, int OT, bool FUSED, bool OLA>
+__global__ __launch_bounds__(256, (matrix_wgs<B, OT>()))
+__attribute__((amdgpu_waves_per_eu(matrix_wgs<B, OT>(), OT > 1 ? 4 : 8))) void k_matrix_step(
+    float* __restrict__ out, int64_t ld_out, float* __restrict__ ovl, const cf* __restrict__ H,
+    const cf* __restrict__ fdl, cf* __restrict__ part, int* __restrict__ arrivals, const cf* __restrict__ twg,
+    const int* __restrict__ tab, int ntiles, int I, int P, int ring, int S, int w)
+{
+    using K = upols_cfg<B>;
+    constexpr int UNROLL = matrix_unroll<B, OT>();
+    __shared__ step_lds<B> L;
+    const int tid = threadIdx.x;
+    const int t = blockIdx.x / S, s = blockIdx.x - t * S;
+    const int first = tab[4 * t], count = tab[4 * t + 1], nuni = tab[4 * t + 2];
+    const int* uni = tab + 4 * ntiles + tab[4 * t + 3];
+    const int* rt = tab + 4 * ntiles + tab[4 * (ntiles - 1) + 3] + tab[4 * (ntiles - 1) + 2];
+    const int n = nuni * P, per = (n + S - 1) / S;
+    const int r0 = min(n, s * per), r1 = min(n, r0 + per);
+
+    const int rs = tid / K::QT, q0 = tid - rs * K::QT;
+    acc4 a[OT][2 * K::VPT];
+#pragma unroll
+    for (int o = 0; o < OT; ++o)
+#pragma unroll
+        for (int v = 0; v < 2 * K::VPT; ++v) a[o][v] = {0.f, 0.f, 0.f, 0.f};
+
+    const int rowbytes = B * int(sizeof(cf));
+    // the rows of one input at a time: the input and the tile's routes from it are uniform
+    for (int seg = r1 > r0 ? r0 / P : nuni; seg < nuni && seg * P < r1; ++seg) {
+        const int i = uni[seg];
+        const int pbeg = max(r0, seg * P) - seg * P, pend = min(r1, (seg + 1) * P) - seg * P;
+        // a route's filter and an input's ring each span < 2 GiB (make_matrix_plan); no route: a
+        // descriptor of size zero, every load through it is out of range and moves no data, and the
+        // output's accumulators are left alone (a uniform branch after the loads: 0 * x would carry
+        // an Inf or NaN of input i into an output it does not feed)
+        __amdgpu_buffer_rsrc_t hd[OT];
+        bool has[OT];
+#pragma unroll
+        for (int o = 0; o < OT; ++o) {
+            const int r = o < count ? rt[int64_t(first + o) * I + i] : -1;
+            has[o] = r >= 0;
+            hd[o] = __builtin_amdgcn_make_buffer_rsrc(const_cast<cf*>(H + int64_t(r >= 0 ? r : 0) * P * B), 0,
+                                                      r >= 0 ? P * rowbytes : 0, 0x00020000);
+        }
+        const __amdgpu_buffer_rsrc_t fd = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<cf*>(fdl + int64_t(i) * ring * B), 0, ring * rowbytes, 0x00020000);
+        auto rows = [&]<int N>(int p) {
+            float4 xv[N][K::VPT], hv[OT][N][K::VPT];
+#pragma unroll
+            for (int u = 0; u < N; ++u) {
+                const int pp = p + u * K::RPI;
+                const int fr = w >= pp ? w - pp : w - pp + ring;  // fdl_index.hpp:28-31 ring
+#pragma unroll
+                for (int v = 0; v < K::VPT; ++v) {
+                    const int q = q0 + v * K::QT;
+                    xv[u][v] = buf_ld4<false>(fd, fr * rowbytes + q * 16);
+#pragma unroll
+                    for (int o = 0; o < OT; ++o) hv[o][u][v] = buf_ld4<true>(hd[o], pp * rowbytes + q * 16);
+                }
+            }
+#pragma unroll
+            for (int o = 0; o < OT; ++o) {
+                if (!has[o]) continue;  // uniform
+#pragma unroll
+                for (int u = 0; u < N; ++u)
+#pragma unroll
+                    for (int v = 0; v < K::VPT; ++v) mac2(a[o][2 * v], a[o][2 * v + 1], hv[o][u][v], xv[u][v]);
+            }
+        };
+        int p = pbeg + rs;
+        for (; p + (UNROLL - 1) * K::RPI < pend; p += UNROLL * K::RPI) rows.template operator()<UNROLL>(p);
+        for (; p < pend; p += K::RPI) rows.template operator()<1>(p);
+    }
+
+    // fold the row groups into group 0 (fixed order), one output at a time, and publish the slabs
+#pragma unroll
+    for (int o = 0; o < OT; ++o) {
+        if (o >= count) break;  // uniform
+        if constexpr (K::RPI > 1) {
+            if (o) __syncthreads();  // the fold of the output before has read red
+#pragma unroll
+            for (int v = 0; v < K::VPT; ++v) {
+                L.red[(tid * K::VPT + v) * 2 + 0] = make_float4(a[o][2 * v].rr, a[o][2 * v].ii, a[o][2 * v].ri, a[o][2 * v].ir);
+                L.red[(tid * K::VPT + v) * 2 + 1] =
+                    make_float4(a[o][2 * v + 1].rr, a[o][2 * v + 1].ii, a[o][2 * v + 1].ri, a[o][2 * v + 1].ir);
+            }
+            __syncthreads();
+            if (rs == 0) {
+#pragma unroll 4
+                for (int g = 1; g < K::RPI; ++g) {
+#pragma unroll
+                    for (int v = 0; v < K::VPT; ++v) {
+                        const int idx = ((g * K::QT + q0) * K::VPT + v) * 2;
+                        const float4 x0 = L.red[idx], x1 = L.red[idx + 1];
+                        a[o][2 * v].rr += x0.x; a[o][2 * v].ii += x0.y; a[o][2 * v].ri += x0.z; a[o][2 * v].ir += x0.w;
+                        a[o][2 * v + 1].rr += x1.x; a[o][2 * v + 1].ii += x1.y; a[o][2 * v + 1].ri += x1.z; a[o][2 * v + 1].ir += x1.w;
+                    }
+                }
+            }
+        }
+        float4* slab = reinterpret_cast<float4*>(part + (int64_t(first + o) * S + s) * B);
+        if (rs == 0) {
+#pragma unroll
+            for (int v = 0; v < K::VPT; ++v) {
+                const int q = q0 + v * K::QT;
+                const cf b0 = finish(a[o][2 * v], q == 0), b1 = finish(a[o][2 * v + 1], false);
+                slab[q] = make_float4(b0.x, b0.y, b1.x, b1.y);
+            }
+        }
+    }
+    if constexpr (!FUSED) return;  // k_upols_finish sums the slabs in the next launch
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores
+    __syncthreads();
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // keep the release's wait (upols_step.hpp)
+        const int before = __hip_atomic_fetch_add(arrivals + t, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        L.last = before == S - 1;
+    }
+    __syncthreads();
+    if (!L.last) return;  // uniform per workgroup
+    if (tid == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(arrivals + t, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next step
+    }
+    for (int k = tid; k < K::TW1 + K::TW2; k += 256) L.tw[k] = twg[k];
+    __syncthreads();
+    auto tail = [&](int o) {
+        // sum the S slabs of the output in order s = 0..S-1, 4 loads in flight
+        const float4* p4 = reinterpret_cast<const float4*>(part + int64_t(first + o) * S * B);
+        for (int q = tid; q < K::Q; q += 256) {
+            float4 sum = p4[q];
+            int u0 = 1;
+            for (; u0 + 3 < S; u0 += 4) {
+                float4 r[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) r[u] = p4[(u0 + u) * K::Q + q];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    sum.x += r[u].x; sum.y += r[u].y; sum.z += r[u].z; sum.w += r[u].w;
+                }
+            }
+            for (; u0 < S; ++u0) {
+                const float4 r = p4[u0 * K::Q + q];
+                sum.x += r.x; sum.y += r.y; sum.z += r.z; sum.w += r.w;
+            }
+            reinterpret_cast<float4*>(L.xnew)[q] = sum;
+        }
+        __syncthreads();
+        c2r_tail<B, OLA, (B / 4 <= 256 ? 4 : B / 256)>(L.xnew, L.fft, L.tw, out + int64_t(first + o) * ld_out,
+                                                       ovl + int64_t(first + o) * B, tid);
+        __syncthreads();  // the tail's reads of xnew and fft done before the next output's
+    };
+    // one output: no loop (the c2r's loop invariants, hoisted out of one, do not fit 64 registers)
+    if constexpr (OT == 1) {
+        tail(0);
+    } else {
+#pragma unroll 1
+        for (int o = 0; o < count; ++o) tail(o);
+    }
+}
+
+// filter [nroutes][P][B + 1] (reference layout) -> packed [nroutes][P][B]
+__global__ void k_matrix_pack(const cf* __restrict__ in, cf* __restrict__ out, int B, int64_t rows)
+{
+    const int64_t gid = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (gid >= rows * B) return;
+    const int64_t r = gid / B, k = gid - r * B;
+    const cf* src = in + r * (B + 1);
+    out[gid] = k == 0 ? cf{src[0].x, src[B].x} : src[k];
+}
+
+namespace {
+
+int matrix_reset_state(matrix_t* m, hipStream_t s)
+{
+    NEO_HIP_CHECK(hipMemsetAsync(m->fdl, 0, size_t(m->I) * m->ring * m->B * sizeof(cf), s));
+    NEO_HIP_CHECK(hipMemsetAsync(m->prev, 0, size_t(m->I) * m->B * sizeof(float), s));
+    NEO_HIP_CHECK(hipMemsetAsync(m->ovl, 0, size_t(m->O) * m->B * sizeof(float), s));
+    if (m->arrivals) NEO_HIP_CHECK(hipMemsetAsync(m->arrivals, 0, size_t(m->plan.ntiles) * sizeof(int), s));
+    m->wpos = 0;
+    return NEO_HIP_OK;
+}
+
+void matrix_free_filter(matrix_t* m)
+{
+    dfree(m->H);
+    dfree(m->part);
+    dfree(m->arrivals);
+    dfree(m->tab);
+    m->H = m->part = nullptr;
+    m->arrivals = m->tab = nullptr;
+    m->ready = false;
+}
+
+void matrix_destroy(matrix_t* m)
+{
+    if (!m) return;
+    matrix_free_filter(m);
+    dfree(m->fdl);
+    dfree(m->prev);
+    dfree(m->ovl);
+    delete m;  // the stream is one of the device's shared four (dmem.hip)
+}
+
+// a setup call runs after every step of this handle, on whatever stream it ran
+int matrix_join(matrix_t* m, bool device_input)
+{
+    if (int rc = m->used.join()) return rc;
+    if (device_input)
+        if (int rc = null_join()) return rc;
+    NEO_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return NEO_HIP_OK;
+}
+
+// the plan for a route list and the buffers that follow it; the filter rows are the caller's to fill
+int matrix_adopt(matrix_t* m, const int* route_out, const int* route_in, int nroutes)
+{
+    matrix_plan pl;
+    if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused, m->o_split,
+                                           m->o_tile, pl))
+        return fail(NEO_HIP_EINVAL, "matrix convolver: %s", why);
+    matrix_free_filter(m);  // the caller joined every stream that used them
+    m->plan = std::move(pl);
+    const matrix_plan& p = m->plan;
+    std::vector<int> tab;
+    tab.reserve(size_t(4) * p.ntiles + p.uni.size() + p.rt.size());
+    for (int t = 0; t < p.ntiles; ++t) {
+        tab.push_back(p.tile_first[size_t(t)]);
+        tab.push_back(p.tile_count[size_t(t)]);
+        tab.push_back(p.uni_off[size_t(t) + 1] - p.uni_off[size_t(t)]);
+        tab.push_back(p.uni_off[size_t(t)]);
+    }
+    tab.insert(tab.end(), p.uni.begin(), p.uni.end());
+    tab.insert(tab.end(), p.rt.begin(), p.rt.end());
+    const size_t rowbytes = size_t(m->B) * sizeof(cf);
+    if (dalloc(&m->H, size_t(nroutes) * m->P * rowbytes) || dalloc(&m->part, size_t(m->O) * p.S * rowbytes) ||
+        dalloc(&m->arrivals, size_t(p.ntiles) * sizeof(int)) || dalloc(&m->tab, tab.size() * sizeof(int))) {
+        matrix_free_filter(m);
+        return fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(nroutes) * m->P * rowbytes);
+    }
+    NEO_HIP_CHECK(hipMemcpyAsync(m->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
+    NEO_HIP_CHECK(hipStreamSynchronize(m->stream));  // tab is a local
+    return NEO_HIP_OK;
+}
+
+int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    const matrix_plan& p = m->plan;
+#define NEO_MATRIX_WINDOW(OL)                                                                                          \
+    NEO_UPOLS_DISPATCH(m->B, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s, in, \
+                                                ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
+    if (m->ola) NEO_MATRIX_WINDOW(true) else NEO_MATRIX_WINDOW(false)
+#undef NEO_MATRIX_WINDOW
+    NEO_HIP_LAUNCH_CHECK();
+    const unsigned grid = unsigned(p.ntiles) * unsigned(p.S);
+#define NEO_MATRIX_STEP(OT_, FU, OL)                                                                                   \
+    hipLaunchKernelGGL((k_matrix_step<BB, OT_, FU, OL>), dim3(grid), dim3(256), 0, s, out, ld_out, m->ovl, m->H,     \
+                       m->fdl, m->part, m->arrivals, m->tw, m->tab, p.ntiles, m->I, m->P, m->ring, p.S, m->wpos)
+#define NEO_MATRIX_STEP_T(FU, OL)                                                              \
+    NEO_UPOLS_DISPATCH(m->B, {                                                                 \
+        constexpr int CAP = matrix_max_tile(BB);                                               \
+        if (CAP >= 4 && p.OT == 4) NEO_MATRIX_STEP((CAP >= 4 ? 4 : 1), FU, OL);                \
+        else if (CAP >= 2 && p.OT == 2) NEO_MATRIX_STEP((CAP >= 2 ? 2 : 1), FU, OL);           \
+        else NEO_MATRIX_STEP(1, FU, OL);                                                       \
+    })
+    if (p.fused) {
+        if (m->ola) NEO_MATRIX_STEP_T(true, true) else NEO_MATRIX_STEP_T(true, false)
+    } else {
+        if (m->ola) NEO_MATRIX_STEP_T(false, true) else NEO_MATRIX_STEP_T(false, false)
+    }
+#undef NEO_MATRIX_STEP_T
+#undef NEO_MATRIX_STEP
+    NEO_HIP_LAUNCH_CHECK();
+    if (!p.fused) {
+        // k_upols_finish: one workgroup per output sums its slabs [S][B] in order and runs the c2r
+        // (overlap-add: the output's tail)
+        if (int rc = launch_finish_slabs(m->O, m->B, p.S, m->ola, m->part, out, ld_out, m->ovl, m->tw, s)) return rc;
+    }
+    m->wpos = m->wpos + 1 >= m->ring ? 0 : m->wpos + 1;  // fdl_index.hpp:35-37
+    return NEO_HIP_OK;
+}
+
+}  // namespace
+}  // namespace neo_hip
+
+using namespace neo_hip;
+
+extern "C" {
+
+NEO_HIP_API int neo_hip_matrix_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                    const int* route_in, int nroutes, const neo_hip_matrix_opts* opts,
+                                    neo_hip_matrix_plan_info* plan, int* tile_first, int* tile_count, int* tile_rows,
+                                    int* union_off, int* union_in, int* cuts)
+{
+    const neo_hip_matrix_opts o = opts ? *opts : neo_hip_matrix_opts{-1, 0, 0};
+    matrix_plan p;
+    if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, route_out, route_in, nroutes, o.fused,
+                                           o.split_workgroups, o.out_tile, p))
+        return fail(NEO_HIP_EINVAL, "matrix_plan: %s", why);
+    if (plan) {
+        plan->out_tile = p.OT;
+        plan->fused = p.fused ? 1 : 0;
+        plan->splits = p.S;
+        plan->tiles = p.ntiles;
+        plan->fdl_row_loads = p.fdl_loads;
+        plan->filter_row_loads = p.filter_loads;
+    }
+    for (int t = 0; t < p.ntiles; ++t) {
+        if (tile_first) tile_first[t] = p.tile_first[size_t(t)];
+        if (tile_count) tile_count[t] = p.tile_count[size_t(t)];
+        if (tile_rows) tile_rows[t] = p.rows(t);
+        if (union_off) union_off[t] = p.uni_off[size_t(t)];
+        if (cuts)
+            for (int s = 0; s <= p.S; ++s) cuts[int64_t(t) * (kMatrixMaxSplits + 1) + s] = p.cut(t, s);
+    }
+    if (union_off) union_off[p.ntiles] = p.uni_off[size_t(p.ntiles)];
+    if (union_in) std::copy(p.uni.begin(), p.uni.end(), union_in);
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_create(int inputs, int outputs, int block, int partitions, int device, int method,
+                                      const neo_hip_matrix_opts* opts, neo_hip_matrix** out)
+{
+    if (!out) return fail(NEO_HIP_EINVAL, "handle pointer is null");
+    *out = nullptr;
+    if (method < 0 || method > 1)
+        return fail(NEO_HIP_EINVAL, "matrix convolvers: method must be 0 (upols) or 1 (upola); whole blocks only");
+    const neo_hip_matrix_opts o = opts ? *opts : neo_hip_matrix_opts{-1, 0, 0};
+    {  // the shape and the options, before a device is touched (a one-route list stands in)
+        const int zero = 0;
+        matrix_plan p;
+        if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, &zero, &zero, 1, o.fused,
+                                               o.split_workgroups, o.out_tile, p))
+            return fail(NEO_HIP_EINVAL, "matrix convolver: %s", why);
+    }
+    device_guard g(device);
+    if (g.rc) return g.rc;
+    auto* m = new matrix_t{};
+    (void)hipGetDevice(&m->device);
+    m->I = inputs, m->O = outputs, m->B = block, m->P = partitions;
+    m->ring = partitions;  // one block per step: row w is written before the step's launch reads it
+    m->ola = method == 1;
+    m->o_fused = o.fused, m->o_split = o.split_workgroups, m->o_tile = o.out_tile;
+    auto bail = [&](int code) {
+        matrix_destroy(m);
+        return code;
+    };
+    if (int rc = shared_stream(&m->stream)) return bail(rc);
+    const size_t rowbytes = size_t(block) * sizeof(cf);
+    if (dalloc(&m->fdl, size_t(inputs) * m->ring * rowbytes) || dalloc(&m->prev, size_t(inputs) * block * sizeof(float)) ||
+        dalloc(&m->ovl, size_t(outputs) * block * sizeof(float)))
+        return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(inputs) * m->ring * rowbytes));
+    if (int rc = shared_tw(&m->tw, block)) return bail(rc);
+    if (int rc = matrix_reset_state(m, m->stream)) return bail(rc);
+    if (hipStreamSynchronize(m->stream) != hipSuccess) return bail(fail(NEO_HIP_ERUNTIME, "sync failed"));
+    *out = m;
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_destroy(neo_hip_matrix* m)
+{
+    if (!m) return NEO_HIP_OK;
+    device_guard g(m->device);
+    (void)matrix_join(m, false);
+    matrix_destroy(m);
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_set_filter(neo_hip_matrix* m, const void* filter, const int* route_out,
+                                          const int* route_in, int nroutes, int is_device)
+{
+    if (!m || !filter) return fail(NEO_HIP_EINVAL, "null handle or filter");
+    {  // a refused route list leaves the handle as it was
+        matrix_plan p;
+        if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused,
+                                               m->o_split, m->o_tile, p))
+            return fail(NEO_HIP_EINVAL, "matrix set_filter: %s", why);
+    }
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, is_device != 0)) return rc;
+    if (int rc = matrix_adopt(m, route_out, route_in, nroutes)) return rc;
+    const int64_t rows = int64_t(nroutes) * m->P;
+    const size_t bytes = size_t(rows) * size_t(m->B + 1) * sizeof(cf);
+    const cf* src = static_cast<const cf*>(filter);
+    cf* tmp = nullptr;
+    int rc = NEO_HIP_OK;
+    if (!is_device) {
+        if ((rc = dalloc(&tmp, bytes))) return rc;
+        if (hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
+        src = tmp;
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_matrix_pack, dim3(unsigned((rows * m->B + 255) / 256)), dim3(256), 0, m->stream, src, m->H,
+                           m->B, rows);
+        if (hipGetLastError() != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "pack launch failed");
+    }
+    if (!rc) rc = matrix_reset_state(m, m->stream);
+    if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(tmp);  // the stream was joined above
+    m->ready = !rc;
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_matrix_set_impulse(neo_hip_matrix* m, const float* ir, int64_t length, const int* route_out,
+                                           const int* route_in, int nroutes, int normalize, int is_device)
+{
+    if (!m || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
+    if (partitions_for(length, m->B) != m->P)
+        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
+                    (long long)partitions_for(length, m->B), m->P);
+    {
+        matrix_plan p;
+        if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused,
+                                               m->o_split, m->o_tile, p))
+            return fail(NEO_HIP_EINVAL, "matrix set_impulse: %s", why);
+    }
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, is_device != 0)) return rc;
+    if (int rc = matrix_adopt(m, route_out, route_in, nroutes)) return rc;
+    const size_t bytes = size_t(nroutes) * size_t(length) * sizeof(float);
+    float* d = nullptr;
+    if (int rc = dalloc(&d, bytes)) return rc;
+    int rc = NEO_HIP_OK;
+    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->stream) != hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
+    // one factor over all routes' rows, as the dense setup takes it over channels (normalize_impulse.hpp:21-30)
+    if (!rc && normalize) rc = normalize_device(d, nroutes, length, m->stream);
+    if (!rc) rc = partition_device(d, nroutes, length, m->B, true, m->H, m->tw, m->stream, int64_t(m->P) * m->B, m->B);
+    if (!rc) rc = matrix_reset_state(m, m->stream);
+    if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(d);
+    m->ready = !rc;
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64_t ld_in, float* out, int64_t ld_out,
+                                       int64_t nblocks, int is_device, void* stream)
+{
+    if (!m || !in || !out) return fail(NEO_HIP_EINVAL, "null handle or buffer");
+    if (!m->ready) return fail(NEO_HIP_EINVAL, "matrix process: no filter set (neo_hip_matrix_set_filter)");
+    if (nblocks < 0 || nblocks > (int64_t(1) << 40) / m->B) return fail(NEO_HIP_EINVAL, "bad block count");
+    const int64_t n = nblocks * m->B;
+    if (ld_in < n || ld_out < n) return fail(NEO_HIP_EINVAL, "leading dimension smaller than nblocks * block");
+    if (is_device && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15 || (ld_in | ld_out) & 3))
+        return fail(NEO_HIP_EINVAL, "device I/O must be 16-byte aligned (ld multiple of 4)");
+    if (!nblocks) return NEO_HIP_OK;
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;  // host I/O: own stream unless given
+    if (int rc = m->used.note(s)) return rc;
+    if (is_device) {
+        for (int64_t t = 0; t < nblocks; ++t)
+            if (int rc = matrix_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s)) return rc;
+        return NEO_HIP_OK;
+    }
+    // host memory: staged ([I][n] in, [O][n] out), synchronous
+    float* din = nullptr;
+    float* dout = nullptr;
+    if (dalloc(&din, size_t(m->I) * n * sizeof(float)) || dalloc(&dout, size_t(m->O) * n * sizeof(float))) {
+        dfree(din);
+        return fail(NEO_HIP_ENOMEM, "staging allocation failed");
+    }
+    int rc = NEO_HIP_OK;
+    if (hipMemcpy2DAsync(din, size_t(n) * sizeof(float), in, size_t(ld_in) * sizeof(float), size_t(n) * sizeof(float),
+                         size_t(m->I), hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "input copy failed");
+    for (int64_t t = 0; t < nblocks && !rc; ++t) rc = matrix_step(m, din + t * m->B, n, dout + t * m->B, n, s);
+    if (!rc && hipMemcpy2DAsync(out, size_t(ld_out) * sizeof(float), dout, size_t(n) * sizeof(float),
+                                size_t(n) * sizeof(float), size_t(m->O), hipMemcpyDeviceToHost, s) != hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "output copy failed");
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    dfree(din);
+    dfree(dout);
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, false)) return rc;
+    if (int rc = matrix_reset_state(m, m->stream)) return rc;
+    NEO_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_info(neo_hip_matrix* m, neo_hip_matrix_desc* d)
+{
+    if (!m || !d) return fail(NEO_HIP_EINVAL, "null handle or descriptor");
+    std::memset(d, 0, sizeof *d);
+    d->inputs = m->I, d->outputs = m->O, d->block = m->B, d->partitions = m->P;
+    d->method = m->ola ? 1 : 0;
+    d->fdl_bytes = int64_t(m->I) * m->ring * m->B * int64_t(sizeof(cf));
+    if (m->ready) {
+        d->routes = m->plan.nroutes, d->tiles = m->plan.ntiles, d->out_tile = m->plan.OT, d->splits = m->plan.S;
+        d->fused = m->plan.fused ? 1 : 0;
+        d->filter_bytes = int64_t(m->plan.nroutes) * m->P * m->B * int64_t(sizeof(cf));
+    }
+    return NEO_HIP_OK;
+}
+
+}  // extern "C"

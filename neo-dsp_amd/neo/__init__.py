@@ -15,7 +15,8 @@ from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_c
                           sparse_upola_convolver,
                           sparse_upols_convolver, PerceptualSparsity, a_weighting, amplitude_to_db, perceptual_histogram,
                           perceptual_histogram_host, perceptual_mask, perceptual_mask_host, perceptual_weights,
-                          threshold_for_tile_density, tile_density_curve)
+                          threshold_for_tile_density, tile_density_curve,
+                          MatrixConvolver, matrix_convolve, matrix_plan)
 
 __version__ = "0.1.0"
 
@@ -47,6 +48,9 @@ __all__ = [
     "sparse_plan",
     "sparse_window_plan",
     "sparse_convolve",
+    "MatrixConvolver",
+    "matrix_plan",
+    "matrix_convolve",
     "a_weighting",
     "amplitude_to_db",
     "PerceptualSparsity",

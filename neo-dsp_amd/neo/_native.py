@@ -30,6 +30,24 @@ class UpolsOpts(ctypes.Structure):
                 ("far_phase2", ctypes.c_int)]
 
 
+class MatrixOpts(ctypes.Structure):
+    """neo_hip_matrix_opts (include/neo_hip.h)."""
+    _fields_ = [("fused", ctypes.c_int), ("split_workgroups", ctypes.c_int), ("out_tile", ctypes.c_int)]
+
+
+class MatrixDesc(ctypes.Structure):
+    """neo_hip_matrix_desc (include/neo_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("inputs", "outputs", "block", "partitions", "method", "routes", "tiles",
+                                            "out_tile", "splits", "fused")] + \
+               [("filter_bytes", ctypes.c_int64), ("fdl_bytes", ctypes.c_int64)]
+
+
+class MatrixPlanInfo(ctypes.Structure):
+    """neo_hip_matrix_plan_info (include/neo_hip.h)."""
+    _fields_ = [("out_tile", ctypes.c_int), ("fused", ctypes.c_int), ("splits", ctypes.c_int), ("tiles", ctypes.c_int),
+                ("fdl_row_loads", ctypes.c_int64), ("filter_row_loads", ctypes.c_int64)]
+
+
 class Perceptual(ctypes.Structure):
     """neo_hip_perceptual (include/neo_hip.h)."""
     _fields_ = [("sample_rate", ctypes.c_double), ("threshold_db", ctypes.c_float),
@@ -106,6 +124,14 @@ SIGNATURES = {
     "neo_hip_upols_multi_set_impulse": (_i, [_vp, _vp, _i64, _i]),
     "neo_hip_upols_multi_process_samples": (_i, [_vp, _vp, _i64, _vp, _i64, _i64]),
     "neo_hip_upols_multi_reset": (_i, [_vp]),
+    "neo_hip_matrix_create": (_i, [_i, _i, _i, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
+    "neo_hip_matrix_destroy": (_i, [_vp]),
+    "neo_hip_matrix_set_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
+    "neo_hip_matrix_set_impulse": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _i, _i]),
+    "neo_hip_matrix_process": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _vp]),
+    "neo_hip_matrix_reset": (_i, [_vp]),
+    "neo_hip_matrix_info": (_i, [_vp, _vp]),
+    "neo_hip_matrix_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp] + [_vp] * 6),
     "neo_hip_overlap_create": (_i, [_i, _i, _i64, _i64, _i, ctypes.POINTER(_vp)]),
     "neo_hip_overlap_destroy": (_i, [_vp]),
     "neo_hip_overlap_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
@@ -135,7 +161,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 500  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 600  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

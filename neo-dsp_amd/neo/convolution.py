@@ -15,6 +15,8 @@ Python; extra/python/src/main.cpp:227-234 only lists the `upols` method enum):
   - sparse_upols_convolver / sparse_upola_convolver
                            src/neo/convolution/sparse_convolver.hpp:12-17 (sparse_filter.hpp:25-45;
                            kept in 128-byte tiles of 16 bins here, include/neo_hip.h)
+  - MatrixConvolver        no reference class: output o = the sum over its routes (o, i) of
+                           upols_convolver / upola_convolver on (x_i, h[o][i]) (include/neo_hip.h)
   - sparse_convolve        extra/plugin/src/dsp/DenseConvolution.cpp:124-186 (a mask of the caller's, or
                            the plugin's A-weighted threshold: PerceptualSparsity, perceptual_mask,
                            perceptual_histogram; a_weighting, amplitude_to_db as main.cpp:260-267)
@@ -51,6 +53,9 @@ __all__ = [
     "sparse_plan",
     "sparse_window_plan",
     "sparse_convolve",
+    "MatrixConvolver",
+    "matrix_plan",
+    "matrix_convolve",
     "a_weighting",
     "amplitude_to_db",
     "PerceptualSparsity",
@@ -1329,3 +1334,196 @@ def convolve(in1, in2, mode: str = "full", method: str = "auto", device: int = 0
     if method == "fft":
         return fft_convolve(in1, in2, device)
     return direct_convolve(in1, in2, device)
+
+
+# -- matrix (multi-input, multi-output) convolver ------------------------------------------------
+
+def _routes(routes, inputs: int, outputs: int):
+    """routes=None: the dense list of all (out, in) pairs, row-major. -> two int32 arrays."""
+    if routes is None:
+        ro, ri = np.divmod(np.arange(int(outputs) * int(inputs), dtype=np.int32), np.int32(inputs))
+    else:
+        r = np.asarray(list(routes), dtype=np.int64).reshape(-1, 2)
+        ro, ri = r[:, 0], r[:, 1]
+    return np.ascontiguousarray(ro, dtype=np.int32), np.ascontiguousarray(ri, dtype=np.int32)
+
+
+def _matrix_opts(options) -> "_native.MatrixOpts":
+    opts = dict(MatrixConvolver.OPTION_DEFAULTS)
+    for k, v in (options or {}).items():
+        if k not in opts:
+            raise ValueError(f"unknown matrix convolver option {k!r}")
+        opts[k] = int(v)
+    return _native.MatrixOpts(**opts)
+
+
+def matrix_plan(inputs: int, outputs: int, block_size: int, partitions: int, routes=None, options=None) -> dict:
+    """The plan of a matrix convolver for a route list and options (neo_hip_matrix_plan; no device
+    needed, the function the handle itself is built from): the out_tile in use, fused, splits, the
+    tiles (first output, count, row count, the union of their inputs, the split cuts into the row
+    list) and the step's totals of FDL-row and filter-row loads; `bytes` = 8 B (loads) plus the
+    block I/O, the algorithmic bytes of one step."""
+    ro, ri = _routes(routes, inputs, outputs)
+    o = _matrix_opts(options)
+    info = _native.MatrixPlanInfo()
+    O, I = max(1, int(outputs)), max(1, int(inputs))
+    first, count, rows = (np.zeros(O, np.int32) for _ in range(3))
+    uoff, uin, cuts = np.zeros(O + 1, np.int32), np.zeros(O * I, np.int32), np.zeros((O, 65), np.int32)
+    _native.check(_native.load().neo_hip_matrix_plan(int(inputs), int(outputs), int(block_size), int(partitions),
+                                                     _ptr(ro), _ptr(ri), len(ro), ctypes.byref(o), ctypes.byref(info),
+                                                     _ptr(first), _ptr(count), _ptr(rows), _ptr(uoff), _ptr(uin),
+                                                     _ptr(cuts)))
+    n, S = info.tiles, info.splits
+    tiles = [{"first": int(first[t]), "count": int(count[t]), "rows": int(rows[t]),
+              "inputs": [int(i) for i in uin[uoff[t]:uoff[t + 1]]], "cuts": [int(c) for c in cuts[t, :S + 1]]}
+             for t in range(n)]
+    loads = info.fdl_row_loads + info.filter_row_loads
+    return {"out_tile": info.out_tile, "fused": bool(info.fused), "splits": S, "tiles": tiles,
+            "fdl_row_loads": info.fdl_row_loads, "filter_row_loads": info.filter_row_loads,
+            "bytes": 8 * int(block_size) * loads + 4 * int(block_size) * (int(inputs) + int(outputs))}
+
+
+class MatrixConvolver:
+    """I inputs routed to O outputs: output o = the sum over its routes (o, i) of the UPOLS (or
+    UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
+    transform per output (neo_hip_matrix_*, include/neo_hip.h). Whole blocks, one block per step."""
+
+    OPTION_DEFAULTS = {"fused": -1, "split_workgroups": 0, "out_tile": 0}
+
+    def __init__(self, inputs: int, outputs: int, block_size: int, partitions: int, method: str = "upols",
+                 options: dict | None = None, device: int = 0):
+        methods = {"upols": 0, "upola": 1}
+        if method not in methods:
+            raise ValueError(f"method must be 'upols' or 'upola', got {method!r}")
+        o = _matrix_opts(options)
+        h = ctypes.c_void_p()
+        _native.check(_native.load().neo_hip_matrix_create(int(inputs), int(outputs), int(block_size), int(partitions),
+                                                           int(device), methods[method], ctypes.byref(o),
+                                                           ctypes.byref(h)))
+        self._h = h
+        self.inputs, self.outputs, self.block_size, self.partitions = int(inputs), int(outputs), int(block_size), int(partitions)
+        self.method, self.device = method, device
+
+    # -- setup ------------------------------------------------------------
+    def filter(self, partitions, routes=None) -> None:
+        """routes None: dense partitions [O][I][P][B+1]; else [nroutes][P][B+1] with routes a list
+        of (out, in). complex64 host array or CUDA tensor. Resets all state."""
+        ro, ri = _routes(routes, self.inputs, self.outputs)
+        shape = (len(ro), self.partitions, self.block_size + 1)
+        lib = _native.load()
+        if _is_torch(partitions) and partitions.is_cuda:
+            import torch
+
+            t = partitions
+            if t.dtype != torch.complex64 or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+                raise ValueError(f"filter must be a contiguous complex64 tensor of {shape} elements")
+            _producer_join(t)
+            _native.check(lib.neo_hip_matrix_set_filter(self._h, ctypes.c_void_p(t.data_ptr()), _ptr(ro), _ptr(ri),
+                                                        len(ro), 1))
+            return
+        H = np.ascontiguousarray(partitions, dtype=np.complex64)
+        if H.size != int(np.prod(shape)):
+            raise ValueError(f"filter of {H.shape} does not hold {shape}")
+        _native.check(lib.neo_hip_matrix_set_filter(self._h, _ptr(H), _ptr(ro), _ptr(ri), len(ro), 0))
+
+    def set_impulse(self, ir, routes=None, normalize: bool = True) -> None:
+        """ir [O][I][L] (routes None) or [nroutes][L] float32: normalize_impulse over all routes'
+        rows (optional), then uniform_partition on the device."""
+        ro, ri = _routes(routes, self.inputs, self.outputs)
+        lib = _native.load()
+        if _is_torch(ir) and ir.is_cuda:
+            import torch
+
+            t = ir
+            L = t.shape[-1]
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != len(ro) * L:
+                raise ValueError("impulse must be a contiguous float32 tensor of one row per route")
+            _producer_join(t)
+            _native.check(lib.neo_hip_matrix_set_impulse(self._h, ctypes.c_void_p(t.data_ptr()), L, _ptr(ro), _ptr(ri),
+                                                         len(ro), int(normalize), 1))
+            return
+        a = np.ascontiguousarray(ir, dtype=np.float32)
+        L = a.shape[-1]
+        if a.size != len(ro) * L:
+            raise ValueError("impulse must hold one row per route")
+        _native.check(lib.neo_hip_matrix_set_impulse(self._h, _ptr(a), L, _ptr(ro), _ptr(ri), len(ro), int(normalize), 0))
+
+    def reset(self) -> None:
+        _native.check(_native.load().neo_hip_matrix_reset(self._h))
+
+    # -- processing ---------------------------------------------------------
+    def process(self, x, stream: int = 0):
+        """x [I][n B] -> y [O][n B]: float32 ndarray (synchronous) or CUDA tensor (asynchronous on
+        `stream`, default torch's current stream)."""
+        lib = _native.load()
+        if _is_torch(x) and x.is_cuda:
+            import torch
+
+            if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 2 or x.shape[0] != self.inputs:
+                raise ValueError("x must be a contiguous float32 tensor [inputs][n * block_size]")
+            n = x.shape[1]
+            if n % self.block_size:
+                raise ValueError("matrix convolvers take whole blocks")
+            y = torch.empty((self.outputs, n), dtype=torch.float32, device=x.device)
+            s = stream or torch.cuda.current_stream(x.device).cuda_stream
+            _native.check(lib.neo_hip_matrix_process(self._h, ctypes.c_void_p(x.data_ptr()), n,
+                                                     ctypes.c_void_p(y.data_ptr()), n, n // self.block_size, 1,
+                                                     ctypes.c_void_p(s)))
+            return y
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(x, dtype=np.float32)))
+        if a.shape[0] != self.inputs or a.shape[1] % self.block_size:
+            raise ValueError("x must be [inputs][n * block_size]")
+        n = a.shape[1]
+        y = np.empty((self.outputs, n), dtype=np.float32)
+        _native.check(lib.neo_hip_matrix_process(self._h, _ptr(a), n, _ptr(y), n, n // self.block_size, 0, None))
+        return y
+
+    def process_device(self, in_ptr: int, ld_in: int, out_ptr: int, ld_out: int, nblocks: int = 1,
+                       stream: int = 0) -> None:
+        """nblocks steps on device pointers: input i at in_ptr + 4 i ld_in, output o at out_ptr + 4 o ld_out."""
+        _native.check(_native.load().neo_hip_matrix_process(self._h, ctypes.c_void_p(in_ptr), int(ld_in),
+                                                            ctypes.c_void_p(out_ptr), int(ld_out), int(nblocks), 1,
+                                                            ctypes.c_void_p(stream)))
+
+    def info(self) -> dict:
+        d = _native.MatrixDesc()
+        _native.check(_native.load().neo_hip_matrix_info(self._h, ctypes.byref(d)))
+        return {n: getattr(d, n) for n, _ in _native.MatrixDesc._fields_}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.load().neo_hip_matrix_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upols", device: int = 0) -> np.ndarray:
+    """One shot: signal [I][n], ir [O][I][L] (routes None) or [nroutes][L] with routes a list of
+    (out, in) and the output count max(out) + 1 -> [O][n padded to whole blocks]; the impulse is
+    normalized over all routes, as dense_convolve normalizes over channels."""
+    x = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
+    a = np.asarray(ir, dtype=np.float32)
+    I = x.shape[0]
+    if routes is None:
+        if a.ndim != 3 or a.shape[1] != I:
+            raise ValueError("ir must be [outputs][inputs][L] without a route list")
+        O = a.shape[0]
+    else:
+        routes = [(int(o), int(i)) for o, i in routes]
+        O = max(o for o, _ in routes) + 1
+    B = int(block_size)
+    n = x.shape[1]
+    pad = (-n) % B
+    if pad:
+        x = np.concatenate([x, np.zeros((I, pad), np.float32)], axis=1)
+    conv = MatrixConvolver(I, O, B, num_partitions(a.shape[-1], B), method=method, device=device)
+    try:
+        conv.set_impulse(a, routes)
+        return conv.process(x)
+    finally:
+        conv.close()
