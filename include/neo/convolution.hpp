@@ -614,6 +614,22 @@ struct hip_matrix_convolver {
 
     auto reset() -> void { neo::hip::check(neo_hip_matrix_reset(_h.get())); }
 
+    /// batched passes: process() runs up to 32 blocks of a call per pass over every route's filter
+    /// (neo_hip_matrix_set_batch); the stream continues across the call. split_workgroups 0 = automatic
+    auto batch(bool on, int split_workgroups = 0) -> void
+    {
+        neo::hip::check(neo_hip_matrix_set_batch(_h.get(), on ? 1 : 0, split_workgroups));
+    }
+    struct batch_desc {
+        int blocks_per_pass, splits, ring_rows;
+    };
+    [[nodiscard]] auto batch_info() const -> batch_desc
+    {
+        batch_desc d{};
+        neo::hip::check(neo_hip_matrix_batch_info(_h.get(), &d.blocks_per_pass, &d.splits, &d.ring_rows));
+        return d;
+    }
+
     [[nodiscard]] auto info() const -> neo_hip_matrix_desc
     {
         neo_hip_matrix_desc d{};

@@ -79,8 +79,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.4.0: the perceptual sparsity predicate (neo_hip_perceptual_* and the two handle calls).
  * 0.5.0: batched passes on sparse handles (set_batch(1) accepted; neo_hip_upols_sparse_window_plan,
  *        neo_hip_upols_sparse_batch_info).
- * 0.6.0: the matrix convolver (neo_hip_matrix_*). */
-#define NEO_HIP_VERSION 600 /* 0.6.0 */
+ * 0.6.0: the matrix convolver (neo_hip_matrix_*).
+ * 0.7.0: batched passes on matrix handles (neo_hip_matrix_set_batch, neo_hip_matrix_batch_info,
+ *        neo_hip_matrix_batch_plan). */
+#define NEO_HIP_VERSION 700 /* 0.7.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -489,10 +491,12 @@ NEO_HIP_API int neo_hip_upols_group_stats(neo_hip_upols_group* g, int* coalesced
  * output. A block step is two launches: the inputs' windows and transforms, then the plain step's
  * MAC over (tiles of outputs) x (splits of the tile's rows), where a TILE is up to out_tile
  * consecutive outputs that share each FDL row load. Equal calls with equal options give equal bits.
- * Batching, streaming levels, offline windows, latency mode, sub-block input (method 2), groups and
- * the multi-device convolver do not apply to this handle type; for very long filters (from 256
- * partitions at 512 routes and more) O * I replicated channels on a neo_hip_upols handle
- * with streaming levels remain the faster form. */
+ * Batched passes are the handle's second gear (neo_hip_matrix_set_batch below): with the blocks of a
+ * call known up front, up to 32 of them share one pass over every route's filter. Streaming levels,
+ * offline windows, latency mode, sub-block input (method 2), groups and the multi-device convolver
+ * do not apply to this handle type; for very long filters (from 256 partitions at 512 routes and
+ * more) O * I replicated channels on a neo_hip_upols handle with streaming levels (one
+ * block per call) or offline windows (many blocks per call) remain the faster form. */
 typedef struct neo_hip_matrix neo_hip_matrix;
 typedef struct neo_hip_matrix_opts {
     int fused;            /* -1 auto (one MAC launch with the last-arriver tail up to 64 workgroups, tiles x splits),
@@ -521,7 +525,7 @@ NEO_HIP_API int neo_hip_matrix_set_filter(neo_hip_matrix* m, const void* filter,
  * uniform_partition on the device; otherwise as set_filter. */
 NEO_HIP_API int neo_hip_matrix_set_impulse(neo_hip_matrix* m, const float* ir, int64_t length, const int* route_out,
                                            const int* route_in, int nroutes, int normalize, int is_device);
-/* nblocks consecutive single-block steps: input i at in + i*ld_in, output o at out + o*ld_out, block
+/* nblocks consecutive single-block steps (batched passes with neo_hip_matrix_set_batch): input i at in + i*ld_in, output o at out + o*ld_out, block
  * t of either at + t*B. Device memory: asynchronous on `stream` (NULL = the HIP null stream), both
  * pointers 16-byte aligned, ld_in and ld_out multiples of 4; host memory: staged, synchronous (the
  * handle's stream if `stream` is NULL), any alignment. ld_in and ld_out >= nblocks * B. A refused
@@ -536,9 +540,46 @@ typedef struct neo_hip_matrix_desc {
     int inputs, outputs, block, partitions, method;
     int routes, tiles, out_tile, splits, fused;
     int64_t filter_bytes; /* [routes][P][B] packed */
-    int64_t fdl_bytes;    /* [inputs][P][B] */
+    int64_t fdl_bytes;    /* [inputs][ring rows][B]: P rows, P + 31 once batching was turned on */
 } neo_hip_matrix_desc;
 NEO_HIP_API int neo_hip_matrix_info(neo_hip_matrix* m, neo_hip_matrix_desc* desc);
+/* Batched passes. enable = 1: neo_hip_matrix_process cuts a call into the largest power-of-two
+ * passes <= 32 of the blocks left (95 blocks: 32, 32, 16, 8, 4, 2 and one single step); a pass of T
+ * blocks is the inputs' T window transforms, ONE walk over every route's filter with T accumulators
+ * per bin (k_matrix_batch_mac: one output per workgroup, the sum over the inputs taken on spectra,
+ * fixed order, no atomics: equal calls give equal bits and the order of the route list plays no
+ * part), and T inverse transforms per output. Results equal those of single steps up to summation
+ * order; every read of the T blocks of `in` still happens before the first write of those blocks of
+ * `out`. Turning batching on grows every input's ring from P to P + 31 rows: the call joins the
+ * handle's streams and re-lays the live rows, so a stream continues across it; turning it off keeps
+ * the larger ring (single steps then give the bits they gave before). Batched passes and single
+ * steps mix freely at block boundaries. split_workgroups: 0 automatic (about 512 workgroups,
+ * outputs x splits x bin chunks, with at least 32 rows in every split of the longest output), else
+ * the workgroup target, taken as given (up to 64 splits per output). enable other than 0 / 1 or a
+ * negative target is EINVAL and leaves the state untouched. The slabs of the passes are allocated
+ * at the first batched pass and freed with the filter. Default: off. */
+NEO_HIP_API int neo_hip_matrix_set_batch(neo_hip_matrix* m, int enable, int split_workgroups);
+/* blocks_per_pass 32 (batching on) or 1; splits per output of a pass (0 until a filter is set or
+ * with batching off); the rows of every input's ring. Each pointer may be NULL. */
+NEO_HIP_API int neo_hip_matrix_batch_info(neo_hip_matrix* m, int* blocks_per_pass, int* splits, int* ring_rows);
+/* The plan of a batched pass of `blocks` (2, 4, 8, 16 or 32) blocks for a route list, on the host (no
+ * device needed; the handle is built from the same function). Output o's row list is its inputs
+ * (ascending) x partitions 0..P-1, flattened, out_rows[o] rows; split s of its `splits` walks rows
+ * [s rows / splits, (s + 1) rows / splits) as a list of RUNS: run k covers partitions [run_first[k],
+ * run_last[k]) of input run_in[k], and the runs of split s of output o are k in [run_off[65 o + s],
+ * run_off[65 o + s + 1]). A run of n rows loads n filter rows and n + blocks - 1 FDL rows (its window).
+ * Per pass: filter_row_loads (routes x P), fdl_row_loads, slab_rows (outputs x splits x blocks,
+ * written once and read once), and bytes = 8 B (filter + FDL rows + 2 slab rows) + 4 B blocks
+ * (inputs + outputs). Arrays (each may be NULL): out_rows [outputs], run_off [outputs][65], run_in,
+ * run_first, run_last [nroutes + 63 * outputs]. */
+typedef struct neo_hip_matrix_batch_plan_info {
+    int blocks, splits, chunks, runs; /* chunks: workgroups per row (B / 256 above 256 bins) */
+    int64_t filter_row_loads, fdl_row_loads, slab_rows, bytes;
+} neo_hip_matrix_batch_plan_info;
+NEO_HIP_API int neo_hip_matrix_batch_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                          const int* route_in, int nroutes, int blocks, int split_workgroups,
+                                          neo_hip_matrix_batch_plan_info* plan, int* out_rows, int* run_off, int* run_in,
+                                          int* run_first, int* run_last);
 /* The plan for a route list and options, on the host (no device needed; the handle is built from
  * the same function). Consecutive outputs form tiles of out_tile; a tile's row list is the union
  * of its outputs' inputs (ascending) x partitions 0..P-1, flattened, and split s of the S splits

@@ -124,4 +124,78 @@ inline const char* make_matrix_plan(int I, int O, int B, int P, const int* route
     return nullptr;
 }
 
+// -- batched passes (upols_matrix_batch.hip): T blocks share one pass over every route's filter ----
+//
+// One output per workgroup (the out_tile = 1 row list: the output's inputs ascending x partitions
+// 0..P-1). Split s of the Sb splits walks rows [cut(o, s), cut(o, s + 1)) of output o's list, a list
+// of RUNS (input, partitions [pa, pb)): at a run's start the kernel reloads its window of T - 1 FDL
+// rows, so a run of n rows loads n + T - 1 of them.
+constexpr int kMatrixBatch = 32;  // most blocks per pass; a batching handle's ring has P + 31 rows
+// the automatic split target, in workgroups (outputs x splits x bin chunks): the pass keeps 2
+// workgroups per CU resident (256 VGPRs), 256 CUs
+constexpr int kMatrixBatchAutoWgs = 512;
+
+// workgroups per row: rows wider than 256 bins take several
+constexpr int matrix_batch_chunks(int B) { return B > 256 ? B / 256 : 1; }
+
+struct matrix_batch_plan {
+    int T = 0, Sb = 1, G = 1, O = 0;
+    std::vector<int> rows;     // [O] the output's row count
+    std::vector<int> run_off;  // [O * Sb + 1] into the runs, split o * Sb + s
+    std::vector<int> runs;     // 4 ints per run: input, route, pa, pb
+    int64_t filter_rows = 0, fdl_rows = 0, slab_rows = 0, bytes = 0;  // per pass of T blocks
+    int nruns() const { return int(runs.size() / 4); }
+    // equal row counts (to one row): no split of an output with >= Sb rows is empty
+    int cut(int o, int s) const { return int(int64_t(s) * rows[size_t(o)] / Sb); }
+};
+
+// The batch plan of a checked plan's route table for passes of T blocks (2 .. 32, a power of two).
+// split_wgs: 0 auto (kMatrixBatchAutoWgs workgroups, at least kMatrixBatch rows in every split of the
+// longest output, so the rows a run reloads never exceed the rows it walks), else the workgroup
+// target, taken as given; at most kMatrixMaxSplits and never an empty split in the longest output.
+inline const char* make_matrix_batch_plan(const matrix_plan& pl, int T, int split_wgs, matrix_batch_plan& bp)
+{
+    if (T < 2 || T > kMatrixBatch || (T & (T - 1))) return "blocks per pass must be 2, 4, 8, 16 or 32";
+    if (split_wgs < 0) return "split_workgroups must be >= 0";
+    if (int64_t(pl.P + kMatrixBatch - 1) * pl.B * 8 >= (int64_t(1) << 31)) return "an input's ring of P + 31 rows must span < 2 GiB";
+    bp = matrix_batch_plan{};
+    const int I = pl.I, O = pl.O, P = pl.P;
+    bp.T = T, bp.O = O, bp.G = matrix_batch_chunks(pl.B);
+    bp.rows.assign(size_t(O), 0);
+    int maxrows = 1;
+    for (int o = 0; o < O; ++o) {
+        int n = 0;
+        for (int i = 0; i < I; ++i) n += pl.rt[size_t(o) * I + i] >= 0;
+        bp.rows[size_t(o)] = n * P;
+        maxrows = std::max(maxrows, n * P);
+    }
+    const int64_t per_split = int64_t(O) * bp.G;
+    const int64_t want = ((split_wgs ? split_wgs : kMatrixBatchAutoWgs) + per_split - 1) / per_split;
+    const int most = split_wgs ? maxrows : std::max(1, maxrows / kMatrixBatch);
+    bp.Sb = int(std::max<int64_t>(1, std::min<int64_t>({want, most, kMatrixMaxSplits})));
+    bp.run_off.assign(1, 0);
+    for (int o = 0; o < O; ++o) {
+        for (int s = 0; s < bp.Sb; ++s) {
+            const int r0 = bp.cut(o, s), r1 = bp.cut(o, s + 1);
+            int row = 0;  // where the next of the output's inputs starts in its row list
+            for (int i = 0; i < I && row < r1; ++i) {
+                const int r = pl.rt[size_t(o) * I + i];
+                if (r < 0) continue;
+                const int a = std::max(r0, row), b = std::min(r1, row + P);
+                if (a < b) {
+                    bp.runs.insert(bp.runs.end(), {i, r, a - row, b - row});
+                    bp.fdl_rows += b - a + T - 1;
+                }
+                row += P;
+            }
+            bp.run_off.push_back(bp.nruns());
+        }
+    }
+    bp.filter_rows = int64_t(pl.nroutes) * P;
+    bp.slab_rows = int64_t(O) * bp.Sb * T;
+    // filter and FDL row loads, the slabs written and read once, the block I/O
+    bp.bytes = 8 * int64_t(pl.B) * (bp.filter_rows + bp.fdl_rows + 2 * bp.slab_rows) + 4 * int64_t(pl.B) * T * (I + O);
+    return nullptr;
+}
+
 }  // namespace neo_hip

@@ -310,7 +310,9 @@ __global__ __launch_bounds__((batch_cfg<B, NB>::L), bmac_var<VAR>::W) void k_bat
 //   OLS: out_j = window samples [B, 2B); workgroup j = T-1 first saves x_{T-1} as the
 //        next batch's previous block (before out_j, which may alias it, is written).
 //   OLA: out_j = samples [0, B) (overlap added by k_batch_ola), tail_j = [B, 2B).
-template<int B, bool OLA>
+// SAVE = false (matrix handles: the previous block is per input, the finish per output) leaves
+// prev and the caller's input alone.
+template<int B, bool OLA, bool SAVE = true>
 __global__ __launch_bounds__(256) void k_batch_finish(const cf* __restrict__ part, int S, int T,
                                                       const float* __restrict__ in, int64_t ld_in,
                                                       float* __restrict__ out, int64_t ld_out, float* __restrict__ prev,
@@ -323,7 +325,7 @@ __global__ __launch_bounds__(256) void k_batch_finish(const cf* __restrict__ par
     __shared__ cf tw[K::TW1 + K::TW2];
     const int tid = threadIdx.x, c = blockIdx.x / T, j = blockIdx.x - c * T;
     for (int i = tid; i < K::TW1 + K::TW2; i += 256) tw[i] = twg[i];
-    if (!OLA && j == T - 1) {
+    if (SAVE && !OLA && j == T - 1) {
         const float4* x4 = reinterpret_cast<const float4*>(in + int64_t(c) * ld_in + int64_t(j) * B);
         float4* p4 = reinterpret_cast<float4*>(prev + int64_t(c) * B);
         for (int i = tid; i < B / 4; i += 256) p4[i] = x4[i];
@@ -479,6 +481,42 @@ int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t
     }
     NEO_HIP_LAUNCH_CHECK();
     h->wpos = (h->wpos + T) % h->ring;
+    return NEO_HIP_OK;
+}
+
+int launch_batch_window(int C, int B, int T, bool ola, const float* in, int64_t ld_in, const float* prev, cf* fdl,
+                        const cf* tw, int ring, int w, hipStream_t s)
+{
+    const unsigned grid = unsigned(C) * unsigned(T);
+    const int64_t cstride = int64_t(ring) * B, pstride = B;
+    if (ola) {
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, true>), dim3(grid), dim3(256), 0, s, in, ld_in, prev,
+                                                 fdl, tw, T, ring, w, cstride, pstride))
+    } else {
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, false>), dim3(grid), dim3(256), 0, s, in, ld_in, prev,
+                                                 fdl, tw, T, ring, w, cstride, pstride))
+    }
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+int launch_batch_finish_nosave(int C, int B, int S, int T, bool ola, const cf* part, float* out, int64_t ld_out,
+                               float* tail, float* ovl, const cf* tw, hipStream_t s)
+{
+    const unsigned grid = unsigned(C) * unsigned(T);
+    const float* no_in = nullptr;
+    float* no_prev = nullptr;
+    if (ola) {  // (overlap-add saves no previous block: the dense pass's own instantiation)
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, true>), dim3(grid), dim3(256), 0, s, part, S, T,
+                                                 no_in, int64_t(0), out, ld_out, no_prev, tail, tw))
+        NEO_HIP_LAUNCH_CHECK();
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_ola<BB>), dim3(unsigned(C)), dim3(256), 0, s, out, ld_out, tail,
+                                                 ovl, T))
+    } else {
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, false, false>), dim3(grid), dim3(256), 0, s, part, S,
+                                                 T, no_in, int64_t(0), out, ld_out, no_prev, tail, tw))
+    }
+    NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }
 

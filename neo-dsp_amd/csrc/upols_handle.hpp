@@ -360,6 +360,19 @@ int launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, float* ou
                         const cf* tw, hipStream_t s);
 // upols_batch.hip: T whole blocks in one pass over the filter and the FDL
 int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s);
+// the launches around a batched MAC on plain arguments (upols_matrix.hip: a matrix handle's window
+// transforms run per input, its finish per output). Window: blocks 0..T-1 of C inputs into FDL rows
+// (w + j) mod ring of [C][ring][B]; prev [C][B] is read (overlap-save), not written. Finish: slabs
+// part [C][S][T][B] summed in order, c2r; it never reads the caller's input and saves no previous
+// block. Overlap-add then chains tail [C][T][B] and ovl [C][B] into out.
+int launch_batch_window(int C, int B, int T, bool ola, const float* in, int64_t ld_in, const float* prev, cf* fdl,
+                        const cf* tw, int ring, int w, hipStream_t s);
+int launch_batch_finish_nosave(int C, int B, int S, int T, bool ola, const cf* part, float* out, int64_t ld_out,
+                               float* tail, float* ovl, const cf* tw, hipStream_t s);
+// upols_matrix_batch.hip: the MAC of a batched pass of a matrix handle: T blocks at write position w
+// into the slabs part [O][Sb][T][B]; tab is the batch plan's run_off and runs (matrix_plan.hpp)
+int launch_matrix_batch_mac(const cf* H, const cf* fdl, cf* part, const int* tab, int B, int P, int ring, int O, int Sb,
+                            int T, int w, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch
 // group is a timed one (every h->timing-th), else nullptr; mark(g, i, s) records event i.
 inline int timing_begin(upols_t* h, int nev, upols_t::ev_group** out)

@@ -23,6 +23,15 @@
 //                    the load moves no data, and a uniform branch leaves its accumulators alone.
 //                    Splits publish a slab per output; the tile's last split to arrive (FUSED) or
 //                    k_upols_finish sums them in the order s = 0..S-1 and runs the c2r tails.
+//
+// A batched pass (neo_hip_matrix_set_batch: T = 2 .. 32 blocks of a call share one pass over every
+// route's filter) needs R >= P + 31 rows, so turning batching on re-lays the ring. Its launches:
+//   k_batch_window      (upols_batch.hip) grid I x T: block j into FDL row (w + j) mod R. Every
+//                       read of the T blocks of `in` happens here and in
+//   k_matrix_save_prev  overlap-save: block T - 1 of every input becomes its previous block,
+//   k_matrix_batch_mac  (upols_matrix_batch.hip) slabs part_b [O][Sb][T][B],
+//   k_batch_finish      grid O x T, without its save of the previous block (that state is per
+//                       input here), and k_batch_ola for overlap-add: the first writes of `out`.
 #include "matrix_plan.hpp"
 #include "upols_handle.hpp"
 #include "upols_step.hpp"
@@ -48,6 +57,13 @@ struct neo_hip_matrix {
     neo_hip::cf* part = nullptr;  // [O][S][B]
     int* arrivals = nullptr;      // [tiles]
     int* tab = nullptr;           // tiles [ntiles][4] {first, count, inputs, offset into uni}, uni, rt [O][I]
+    // batched passes (neo_hip_matrix_set_batch; upols_matrix_batch.hip)
+    bool batch = false;
+    int b_split = 0;                   // the workgroup target as given (0 auto)
+    neo_hip::matrix_batch_plan bplan;  // with the filter, for passes of kMatrixBatch blocks
+    neo_hip::cf* part_b = nullptr;     // [O][Sb][32][B]; these three from the first batched pass on
+    float* tail = nullptr;             // [O][32][B] overlap-add tails of a pass
+    int* btab = nullptr;               // bplan's run_off, runs
     neo_hip::stream_set used;
 };
 
@@ -253,6 +269,16 @@ __attribute__((amdgpu_waves_per_eu(matrix_wgs<B, OT>(), OT > 1 ? 4 : 8))) void k
     }
 }
 
+// overlap-save after a batched pass's windows: block T - 1 of input i is the next call's previous
+// block (grid I; launched before the pass's first write of `out`, which may alias `in`)
+__global__ __launch_bounds__(256) void k_matrix_save_prev(const float* __restrict__ in, int64_t ld_in,
+                                                          float* __restrict__ prev, int B, int T)
+{
+    const float4* x4 = reinterpret_cast<const float4*>(in + int64_t(blockIdx.x) * ld_in + int64_t(T - 1) * B);
+    float4* p4 = reinterpret_cast<float4*>(prev + int64_t(blockIdx.x) * B);
+    for (int k = threadIdx.x; k < B / 4; k += 256) p4[k] = x4[k];
+}
+
 // filter [nroutes][P][B + 1] (reference layout) -> packed [nroutes][P][B]
 __global__ void k_matrix_pack(const cf* __restrict__ in, cf* __restrict__ out, int B, int64_t rows)
 {
@@ -275,8 +301,20 @@ int matrix_reset_state(matrix_t* m, hipStream_t s)
     return NEO_HIP_OK;
 }
 
+// the buffers of the batched passes follow the batch plan (the caller joined every stream that used them)
+void matrix_free_batch(matrix_t* m)
+{
+    dfree(m->part_b);
+    dfree(m->tail);
+    dfree(m->btab);
+    m->part_b = nullptr;
+    m->tail = nullptr;
+    m->btab = nullptr;
+}
+
 void matrix_free_filter(matrix_t* m)
 {
+    matrix_free_batch(m);
     dfree(m->H);
     dfree(m->part);
     dfree(m->arrivals);
@@ -315,6 +353,8 @@ int matrix_adopt(matrix_t* m, const int* route_out, const int* route_in, int nro
         return fail(NEO_HIP_EINVAL, "matrix convolver: %s", why);
     matrix_free_filter(m);  // the caller joined every stream that used them
     m->plan = std::move(pl);
+    // (refused only for a ring that set_batch refuses too: batching is off then)
+    if (make_matrix_batch_plan(m->plan, kMatrixBatch, m->b_split, m->bplan)) m->bplan = matrix_batch_plan{};
     const matrix_plan& p = m->plan;
     std::vector<int> tab;
     tab.reserve(size_t(4) * p.ntiles + p.uni.size() + p.rt.size());
@@ -371,6 +411,95 @@ int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t
         if (int rc = launch_finish_slabs(m->O, m->B, p.S, m->ola, m->part, out, ld_out, m->ovl, m->tw, s)) return rc;
     }
     m->wpos = m->wpos + 1 >= m->ring ? 0 : m->wpos + 1;  // fdl_index.hpp:35-37
+    return NEO_HIP_OK;
+}
+
+// the slabs, the overlap-add tails and the run table, at the first batched pass after a filter or
+// a set_batch (both joined the streams that used the old ones)
+int matrix_batch_buffers(matrix_t* m, hipStream_t s)
+{
+    if (m->part_b) return NEO_HIP_OK;
+    const matrix_batch_plan& bp = m->bplan;
+    const size_t ntab = bp.run_off.size() + bp.runs.size();
+    if (dalloc(&m->part_b, size_t(m->O) * bp.Sb * kMatrixBatch * m->B * sizeof(cf)) ||
+        (m->ola && dalloc(&m->tail, size_t(m->O) * kMatrixBatch * m->B * sizeof(float))) ||
+        dalloc(&m->btab, ntab * sizeof(int))) {
+        matrix_free_batch(m);
+        return fail(NEO_HIP_ENOMEM, "matrix batch buffers: device allocation failed");
+    }
+    std::vector<int> tab(bp.run_off);
+    tab.insert(tab.end(), bp.runs.begin(), bp.runs.end());
+    if (hipMemcpyAsync(m->btab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
+        matrix_free_batch(m);
+        return fail(NEO_HIP_ERUNTIME, "matrix batch buffers: table copy failed");
+    }
+    return NEO_HIP_OK;
+}
+
+// T = 2 .. 32 blocks in one pass over every route's filter (the ring has P + 31 rows: set_batch)
+int matrix_batch(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s)
+{
+    if (int rc = matrix_batch_buffers(m, s)) return rc;
+    if (int rc = launch_batch_window(m->I, m->B, T, m->ola, in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos, s)) return rc;
+    if (!m->ola) {
+        hipLaunchKernelGGL(k_matrix_save_prev, dim3(unsigned(m->I)), dim3(256), 0, s, in, ld_in, m->prev, m->B, T);
+        NEO_HIP_LAUNCH_CHECK();
+    }
+    if (int rc = launch_matrix_batch_mac(m->H, m->fdl, m->part_b, m->btab, m->B, m->P, m->ring, m->O, m->bplan.Sb, T,
+                                         m->wpos, s))
+        return rc;
+    if (int rc = launch_batch_finish_nosave(m->O, m->B, m->bplan.Sb, T, m->ola, m->part_b, out, ld_out, m->tail, m->ovl,
+                                            m->tw, s))
+        return rc;
+    m->wpos = (m->wpos + T) % m->ring;
+    return NEO_HIP_OK;
+}
+
+// the blocks of a call: with batching on the largest power-of-two passes <= 32 of the blocks left,
+// then single steps
+int matrix_blocks(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t nblocks, hipStream_t s)
+{
+    for (int64_t t = 0; t < nblocks;) {
+        int T = 1;
+        if (m->batch) {
+            T = kMatrixBatch;
+            while (T > nblocks - t) T >>= 1;
+        }
+        const int rc = T > 1 ? matrix_batch(m, in + t * m->B, ld_in, out + t * m->B, ld_out, T, s)
+                             : matrix_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s);
+        if (rc) return rc;
+        t += T;
+    }
+    return NEO_HIP_OK;
+}
+
+// the ring of R rows re-laid in one of `rows` > R: the R live rows in time order as rows 0 .. R - 1
+// (row w is the oldest), the write position R, the rest zero; partition p still pairs with row
+// (w - p) mod rows. The caller joined the handle's streams.
+int matrix_grow_ring(matrix_t* m, int rows)
+{
+    const size_t rowbytes = size_t(m->B) * sizeof(cf);
+    cf* fresh = nullptr;
+    if (dalloc(&fresh, size_t(m->I) * rows * rowbytes))
+        return fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(m->I) * rows * rowbytes);
+    const int R = m->ring, w = m->wpos;
+    hipError_t e = hipMemsetAsync(fresh, 0, size_t(m->I) * rows * rowbytes, m->stream);
+    if (e == hipSuccess)  // old rows w .. R - 1 -> 0 .. R - w - 1
+        e = hipMemcpy2DAsync(fresh, rows * rowbytes, m->fdl + size_t(w) * m->B, R * rowbytes, (R - w) * rowbytes,
+                             size_t(m->I), hipMemcpyDeviceToDevice, m->stream);
+    if (e == hipSuccess && w)  // old rows 0 .. w - 1 -> R - w .. R - 1
+        e = hipMemcpy2DAsync(fresh + size_t(R - w) * m->B, rows * rowbytes, m->fdl, R * rowbytes, w * rowbytes,
+                             size_t(m->I), hipMemcpyDeviceToDevice, m->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) {
+        dfree(fresh);
+        return fail(NEO_HIP_ERUNTIME, "matrix set_batch: re-laying the ring failed: %s", hipGetErrorString(e));
+    }
+    dfree(m->fdl);
+    m->fdl = fresh;
+    m->ring = rows;
+    m->wpos = R;
     return NEO_HIP_OK;
 }
 
@@ -545,11 +674,7 @@ NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64
     if (g.rc) return g.rc;
     hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;  // host I/O: own stream unless given
     if (int rc = m->used.note(s)) return rc;
-    if (is_device) {
-        for (int64_t t = 0; t < nblocks; ++t)
-            if (int rc = matrix_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s)) return rc;
-        return NEO_HIP_OK;
-    }
+    if (is_device) return matrix_blocks(m, in, ld_in, out, ld_out, nblocks, s);
     // host memory: staged ([I][n] in, [O][n] out), synchronous
     float* din = nullptr;
     float* dout = nullptr;
@@ -561,7 +686,7 @@ NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64
     if (hipMemcpy2DAsync(din, size_t(n) * sizeof(float), in, size_t(ld_in) * sizeof(float), size_t(n) * sizeof(float),
                          size_t(m->I), hipMemcpyHostToDevice, s) != hipSuccess)
         rc = fail(NEO_HIP_ERUNTIME, "input copy failed");
-    for (int64_t t = 0; t < nblocks && !rc; ++t) rc = matrix_step(m, din + t * m->B, n, dout + t * m->B, n, s);
+    if (!rc) rc = matrix_blocks(m, din, n, dout, n, nblocks, s);
     if (!rc && hipMemcpy2DAsync(out, size_t(ld_out) * sizeof(float), dout, size_t(n) * sizeof(float),
                                 size_t(n) * sizeof(float), size_t(m->O), hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(NEO_HIP_ERUNTIME, "output copy failed");
@@ -579,6 +704,74 @@ NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m)
     if (int rc = matrix_join(m, false)) return rc;
     if (int rc = matrix_reset_state(m, m->stream)) return rc;
     NEO_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_set_batch(neo_hip_matrix* m, int enable, int split_workgroups)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable < 0 || enable > 1 || split_workgroups < 0)
+        return fail(NEO_HIP_EINVAL, "matrix set_batch: enable must be 0 or 1, split_workgroups >= 0");
+    const int rows = m->P + kMatrixBatch - 1;
+    if (enable && int64_t(rows) * m->B * int64_t(sizeof(cf)) >= (int64_t(1) << 31))
+        return fail(NEO_HIP_EINVAL, "matrix set_batch: an input's ring of P + 31 rows must span < 2 GiB");
+    matrix_batch_plan bp;
+    if (m->ready)
+        if (const char* why = make_matrix_batch_plan(m->plan, kMatrixBatch, split_workgroups, bp))
+            return fail(NEO_HIP_EINVAL, "matrix set_batch: %s", why);
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, false)) return rc;
+    if (enable && m->ring < rows)
+        if (int rc = matrix_grow_ring(m, rows)) return rc;  // (the state is as it was)
+    m->batch = enable != 0;  // off: the larger ring stays, single steps read the same rows in the same order
+    m->b_split = split_workgroups;
+    if (m->ready) {
+        m->bplan = std::move(bp);
+        matrix_free_batch(m);  // sized by the plan; the next batched pass allocates them
+    }
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_batch_info(neo_hip_matrix* m, int* blocks_per_pass, int* splits, int* ring_rows)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (blocks_per_pass) *blocks_per_pass = m->batch ? kMatrixBatch : 1;
+    if (splits) *splits = m->batch && m->ready ? m->bplan.Sb : 0;
+    if (ring_rows) *ring_rows = m->ring;
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_batch_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                          const int* route_in, int nroutes, int blocks, int split_workgroups,
+                                          neo_hip_matrix_batch_plan_info* plan, int* out_rows, int* run_off, int* run_in,
+                                          int* run_first, int* run_last)
+{
+    matrix_plan p;
+    if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, route_out, route_in, nroutes, -1, 0, 1, p))
+        return fail(NEO_HIP_EINVAL, "matrix_batch_plan: %s", why);
+    matrix_batch_plan bp;
+    if (const char* why = make_matrix_batch_plan(p, blocks, split_workgroups, bp))
+        return fail(NEO_HIP_EINVAL, "matrix_batch_plan: %s", why);
+    if (plan) {
+        plan->blocks = bp.T;
+        plan->splits = bp.Sb;
+        plan->chunks = bp.G;
+        plan->runs = bp.nruns();
+        plan->filter_row_loads = bp.filter_rows;
+        plan->fdl_row_loads = bp.fdl_rows;
+        plan->slab_rows = bp.slab_rows;
+        plan->bytes = bp.bytes;
+    }
+    if (out_rows) std::copy(bp.rows.begin(), bp.rows.end(), out_rows);
+    if (run_off)  // row 65 o + s, as neo_hip_matrix_plan's cuts
+        for (int o = 0; o < outputs; ++o)
+            for (int s = 0; s <= bp.Sb; ++s) run_off[int64_t(o) * (kMatrixMaxSplits + 1) + s] = bp.run_off[size_t(o) * bp.Sb + s];
+    for (int k = 0; k < bp.nruns(); ++k) {
+        if (run_in) run_in[k] = bp.runs[size_t(4) * k];
+        if (run_first) run_first[k] = bp.runs[size_t(4) * k + 2];
+        if (run_last) run_last[k] = bp.runs[size_t(4) * k + 3];
+    }
     return NEO_HIP_OK;
 }
 

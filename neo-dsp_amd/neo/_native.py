@@ -48,6 +48,12 @@ class MatrixPlanInfo(ctypes.Structure):
                 ("fdl_row_loads", ctypes.c_int64), ("filter_row_loads", ctypes.c_int64)]
 
 
+class MatrixBatchPlanInfo(ctypes.Structure):
+    """neo_hip_matrix_batch_plan_info (include/neo_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("blocks", "splits", "chunks", "runs")] + \
+               [(n, ctypes.c_int64) for n in ("filter_row_loads", "fdl_row_loads", "slab_rows", "bytes")]
+
+
 class Perceptual(ctypes.Structure):
     """neo_hip_perceptual (include/neo_hip.h)."""
     _fields_ = [("sample_rate", ctypes.c_double), ("threshold_db", ctypes.c_float),
@@ -132,6 +138,9 @@ SIGNATURES = {
     "neo_hip_matrix_reset": (_i, [_vp]),
     "neo_hip_matrix_info": (_i, [_vp, _vp]),
     "neo_hip_matrix_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _vp] + [_vp] * 6),
+    "neo_hip_matrix_set_batch": (_i, [_vp, _i, _i]),
+    "neo_hip_matrix_batch_info": (_i, [_vp, _vp, _vp, _vp]),
+    "neo_hip_matrix_batch_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp] + [_vp] * 5),
     "neo_hip_overlap_create": (_i, [_i, _i, _i64, _i64, _i, ctypes.POINTER(_vp)]),
     "neo_hip_overlap_destroy": (_i, [_vp]),
     "neo_hip_overlap_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
@@ -161,7 +170,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 600  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 700  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

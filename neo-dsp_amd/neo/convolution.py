@@ -55,6 +55,7 @@ __all__ = [
     "sparse_convolve",
     "MatrixConvolver",
     "matrix_plan",
+    "matrix_batch_plan",
     "matrix_convolve",
     "a_weighting",
     "amplitude_to_db",
@@ -1383,10 +1384,37 @@ def matrix_plan(inputs: int, outputs: int, block_size: int, partitions: int, rou
             "bytes": 8 * int(block_size) * loads + 4 * int(block_size) * (int(inputs) + int(outputs))}
 
 
+def matrix_batch_plan(inputs: int, outputs: int, block_size: int, partitions: int, routes=None, blocks: int = 32,
+                      split_workgroups: int = 0) -> dict:
+    """The plan of a batched pass of `blocks` blocks of a matrix convolver (neo_hip_matrix_batch_plan;
+    no device needed, the function the handle itself is built from): the splits per output, the bin
+    chunks per row, per output its row count and per split its runs (input, first partition, one
+    past the last), and the pass's totals: filter_row_loads (routes x P), fdl_row_loads (per run its
+    length + blocks - 1), slab_rows and `bytes` = 8 B (filter + FDL rows + 2 slab rows) plus the
+    block I/O of all `blocks` blocks."""
+    ro, ri = _routes(routes, inputs, outputs)
+    info = _native.MatrixBatchPlanInfo()
+    O = max(1, int(outputs))
+    rows, off = np.zeros(O, np.int32), np.zeros((O, 65), np.int32)
+    rin, rfirst, rlast = (np.zeros(len(ro) + 63 * O, np.int32) for _ in range(3))
+    _native.check(_native.load().neo_hip_matrix_batch_plan(int(inputs), int(outputs), int(block_size), int(partitions),
+                                                           _ptr(ro), _ptr(ri), len(ro), int(blocks),
+                                                           int(split_workgroups), ctypes.byref(info), _ptr(rows),
+                                                           _ptr(off), _ptr(rin), _ptr(rfirst), _ptr(rlast)))
+    S = info.splits
+    outs = [{"rows": int(rows[o]),
+             "splits": [[(int(rin[k]), int(rfirst[k]), int(rlast[k])) for k in range(off[o, s], off[o, s + 1])]
+                        for s in range(S)]} for o in range(int(outputs))]
+    return {"blocks": info.blocks, "splits": S, "chunks": info.chunks, "runs": info.runs, "outputs": outs,
+            "filter_row_loads": info.filter_row_loads, "fdl_row_loads": info.fdl_row_loads,
+            "slab_rows": info.slab_rows, "bytes": info.bytes}
+
+
 class MatrixConvolver:
     """I inputs routed to O outputs: output o = the sum over its routes (o, i) of the UPOLS (or
     UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
-    transform per output (neo_hip_matrix_*, include/neo_hip.h). Whole blocks, one block per step."""
+    transform per output (neo_hip_matrix_*, include/neo_hip.h). Whole blocks: one block per step,
+    or with set_batch(True) up to 32 blocks of a call per pass over the filters."""
 
     OPTION_DEFAULTS = {"fused": -1, "split_workgroups": 0, "out_tile": 0}
 
@@ -1451,6 +1479,19 @@ class MatrixConvolver:
     def reset(self) -> None:
         _native.check(_native.load().neo_hip_matrix_reset(self._h))
 
+    def set_batch(self, enable: bool, split_workgroups: int = 0) -> None:
+        """Batched passes (neo_hip_matrix_set_batch): process() cuts a call into passes of up to 32
+        blocks that share one walk over every route's filter, then single steps. Turning it on grows
+        the inputs' rings to P + 31 rows and keeps the stream; split_workgroups 0 = automatic."""
+        _native.check(_native.load().neo_hip_matrix_set_batch(self._h, int(bool(enable)), int(split_workgroups)))
+
+    def batch_info(self) -> dict:
+        """blocks_per_pass (32 or 1), splits per output of a pass (0 without a filter or with
+        batching off) and the rows of every input's ring."""
+        b, s, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _native.check(_native.load().neo_hip_matrix_batch_info(self._h, ctypes.byref(b), ctypes.byref(s), ctypes.byref(r)))
+        return {"blocks_per_pass": b.value, "splits": s.value, "ring_rows": r.value}
+
     # -- processing ---------------------------------------------------------
     def process(self, x, stream: int = 0):
         """x [I][n B] -> y [O][n B]: float32 ndarray (synchronous) or CUDA tensor (asynchronous on
@@ -1502,12 +1543,26 @@ class MatrixConvolver:
             pass
 
 
-def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upols", device: int = 0) -> np.ndarray:
+def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upols", device: int = 0,
+                    batch: bool = False):
     """One shot: signal [I][n], ir [O][I][L] (routes None) or [nroutes][L] with routes a list of
     (out, in) and the output count max(out) + 1 -> [O][n padded to whole blocks]; the impulse is
-    normalized over all routes, as dense_convolve normalizes over channels."""
-    x = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
-    a = np.asarray(ir, dtype=np.float32)
+    normalized over all routes, as dense_convolve normalizes over channels. batch=True runs the
+    blocks in batched passes (MatrixConvolver.set_batch): the same results up to summation order.
+    A float32 CUDA tensor as signal (ir a tensor on the same device or an array) stays on the
+    device and gives a tensor."""
+    on_device = _is_torch(signal) and signal.is_cuda
+    if on_device:
+        import torch
+
+        if signal.dtype != torch.float32 or signal.dim() != 2:
+            raise ValueError("a device signal must be a float32 tensor [inputs][n]")
+        x = signal.contiguous()
+        a = ir if _is_torch(ir) and ir.is_cuda else np.asarray(ir, dtype=np.float32)
+        device = x.device.index or 0
+    else:
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
+        a = np.asarray(ir, dtype=np.float32)
     I = x.shape[0]
     if routes is None:
         if a.ndim != 3 or a.shape[1] != I:
@@ -1519,11 +1574,15 @@ def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upo
     B = int(block_size)
     n = x.shape[1]
     pad = (-n) % B
-    if pad:
+    if pad and on_device:
+        x = torch.nn.functional.pad(x, (0, pad)).contiguous()
+    elif pad:
         x = np.concatenate([x, np.zeros((I, pad), np.float32)], axis=1)
     conv = MatrixConvolver(I, O, B, num_partitions(a.shape[-1], B), method=method, device=device)
     try:
-        conv.set_impulse(a, routes)
+        conv.set_impulse(a.contiguous() if _is_torch(a) else a, routes)
+        if batch:
+            conv.set_batch(True)
         return conv.process(x)
     finally:
         conv.close()
