@@ -630,6 +630,24 @@ struct hip_matrix_convolver {
         return d;
     }
 
+    /// offline windows: process() runs passes of 256 (windows_per_pass 1: 128) blocks while that many
+    /// are left, by 256-point transforms along the block axis (neo_hip_matrix_set_offline: long
+    /// filters, every block of a call known up front); the stream continues across the call
+    auto offline(bool on, int windows_per_pass = 0) -> void
+    {
+        neo::hip::check(neo_hip_matrix_set_offline(_h.get(), on ? 1 : 0, windows_per_pass));
+    }
+    struct offline_desc {
+        int blocks_per_pass, segments, ring_rows;
+        std::int64_t spectra_bytes;
+    };
+    [[nodiscard]] auto offline_info() const -> offline_desc
+    {
+        offline_desc d{};
+        neo::hip::check(neo_hip_matrix_offline_info(_h.get(), &d.blocks_per_pass, &d.segments, &d.ring_rows, &d.spectra_bytes));
+        return d;
+    }
+
     [[nodiscard]] auto info() const -> neo_hip_matrix_desc
     {
         neo_hip_matrix_desc d{};

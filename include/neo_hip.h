@@ -81,8 +81,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  *        neo_hip_upols_sparse_batch_info).
  * 0.6.0: the matrix convolver (neo_hip_matrix_*).
  * 0.7.0: batched passes on matrix handles (neo_hip_matrix_set_batch, neo_hip_matrix_batch_info,
- *        neo_hip_matrix_batch_plan). */
-#define NEO_HIP_VERSION 700 /* 0.7.0 */
+ *        neo_hip_matrix_batch_plan).
+ * 0.8.0: offline windows on matrix handles (neo_hip_matrix_set_offline, neo_hip_matrix_offline_info,
+ *        neo_hip_matrix_offline_plan; neo_hip_matrix_desc gains offline_bytes at its end). */
+#define NEO_HIP_VERSION 800 /* 0.8.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -492,11 +494,13 @@ NEO_HIP_API int neo_hip_upols_group_stats(neo_hip_upols_group* g, int* coalesced
  * MAC over (tiles of outputs) x (splits of the tile's rows), where a TILE is up to out_tile
  * consecutive outputs that share each FDL row load. Equal calls with equal options give equal bits.
  * Batched passes are the handle's second gear (neo_hip_matrix_set_batch below): with the blocks of a
- * call known up front, up to 32 of them share one pass over every route's filter. Streaming levels,
- * offline windows, latency mode, sub-block input (method 2), groups and the multi-device convolver
- * do not apply to this handle type; for very long filters (from 256 partitions at 512 routes and
- * more) O * I replicated channels on a neo_hip_upols handle with streaming levels (one
- * block per call) or offline windows (many blocks per call) remain the faster form. */
+ * call known up front, up to 32 of them share one pass over every route's filter. Offline windows
+ * are the third (neo_hip_matrix_set_offline below): windows of 128 blocks by 256-point transforms
+ * along the block axis, for long filters with every block of a call known up front. Streaming levels,
+ * latency mode, sub-block input (method 2), groups and the multi-device convolver
+ * do not apply to this handle type; for very long filters with one block per call (from 256
+ * partitions at 512 routes and more) O * I replicated channels on a neo_hip_upols
+ * handle with streaming levels remain the faster form. */
 typedef struct neo_hip_matrix neo_hip_matrix;
 typedef struct neo_hip_matrix_opts {
     int fused;            /* -1 auto (one MAC launch with the last-arriver tail up to 64 workgroups, tiles x splits),
@@ -540,7 +544,10 @@ typedef struct neo_hip_matrix_desc {
     int inputs, outputs, block, partitions, method;
     int routes, tiles, out_tile, splits, fused;
     int64_t filter_bytes; /* [routes][P][B] packed */
-    int64_t fdl_bytes;    /* [inputs][ring rows][B]: P rows, P + 31 once batching was turned on */
+    int64_t fdl_bytes;    /* [inputs][ring rows][B]: P rows, P + 31 once batching was turned on, at least
+                             128 (ceil(P / 128) + 2) + 1 once offline windows were */
+    int64_t offline_bytes; /* the buffers of the offline windows (segment, pair and output spectra, overlap-add
+                              tails), 0 until the first offline pass after a filter allocates them */
 } neo_hip_matrix_desc;
 NEO_HIP_API int neo_hip_matrix_info(neo_hip_matrix* m, neo_hip_matrix_desc* desc);
 /* Batched passes. enable = 1: neo_hip_matrix_process cuts a call into the largest power-of-two
@@ -580,6 +587,61 @@ NEO_HIP_API int neo_hip_matrix_batch_plan(int inputs, int outputs, int block, in
                                           const int* route_in, int nroutes, int blocks, int split_workgroups,
                                           neo_hip_matrix_batch_plan_info* plan, int* out_rows, int* run_off, int* run_in,
                                           int* run_first, int* run_last);
+/* Offline windows, for long filters when every block of a call is known up front (a file render, a
+ * matrix over a dataset). enable = 1: while neo_hip_matrix_process has 256 blocks or more left it
+ * runs a pass of two windows of 128 blocks (windows_per_pass 0 = automatic = 2, or 2), else while 128
+ * or more are left a pass of one window (windows_per_pass 1: one-window passes only); the rest of
+ * the call goes as without it (batched passes if batching is on, else single steps). Per bin, the
+ * blocks t_W + j (j < 128) of a window are samples 128 + j of IDFT256 of the sum, over the output's
+ * routes (o, i) in ascending input order and the segments q < ceil(P / 128) of 128 partitions, of
+ * DFT256(ring rows t_W - 128 (q + 1) ... + 255 of input i) . DFT256(segment q of the route's
+ * filter, zero past P): forward transforms per input, inverse transforms per output, per route only
+ * the spectrum products; fixed order, no atomics, equal calls give equal bits and the order of the
+ * route list plays no part. Results equal those of single steps up to rounding. Every read of the
+ * pass's blocks of `in` happens before the first write of those blocks of `out`. Turning it on joins
+ * the handle's streams and re-lays every input's ring in at least 128 (ceil(P / 128) + 2) + 1 rows
+ * (the larger of this and P + 31 with batching), so a stream continues across it; a ring that would
+ * span 2 GiB or more per input is EINVAL. Turning it off keeps the larger ring (the other passes then
+ * give the bits they gave before). All kinds of pass mix freely at block boundaries, across calls
+ * and across toggling. enable other than 0 / 1 or windows_per_pass other than 0, 1, 2 is EINVAL and
+ * leaves the state untouched. The spectra ([routes][segments][256][B] of the filters: as large as
+ * the filters rounded up to 256 rows per 128 partitions, recomputed at the first offline pass after
+ * every set_filter / set_impulse) and the pass buffers are allocated at the first offline pass and
+ * freed with the filter; if that allocation fails the call returns ENOMEM and the handle goes on
+ * with batched passes and single steps. Default: off.
+ * Inf / NaN: the 256-point transforms mix the rows of a pair, and the zero-padded last segment
+ * meets rows older than the filter reaches. So a non-finite input block makes EVERY block of every
+ * window whose pairs hold it non-finite, on the outputs routed from that input: count on every
+ * block of every pass from the one containing the block up to the last pass with
+ * t_W - 128 ceil(P / 128) <= that block (as on a neo_hip_upols handle's offline windows), and with
+ * overlap-add on the first block after them, which takes the last one's overlap tail. Outputs with
+ * no route from that input are untouched, bit for bit. */
+NEO_HIP_API int neo_hip_matrix_set_offline(neo_hip_matrix* m, int enable, int windows_per_pass);
+/* blocks_per_pass 256 or 128 (offline windows on; 0 off); segments = ceil(P / 128); the rows of every
+ * input's ring; the payload bytes of the segment spectra (0 until allocated). Each pointer may be NULL. */
+NEO_HIP_API int neo_hip_matrix_offline_info(neo_hip_matrix* m, int* blocks_per_pass, int* segments, int* ring_rows,
+                                            int64_t* spectra_bytes);
+/* The plan of an offline pass, on the host (no device needed; the pass takes its rows from the same
+ * function): `windows` (0 = 2, 1, 2) windows at ring row write_pos of a ring of ring_rows rows (0 =
+ * min_ring_rows, the least a handle takes). A PAIR is 256 consecutive ring rows (mod ring_rows):
+ * pair_row[k], k < pairs = segments + windows - 1, is the first row of pair k (k = 0 the newest) and
+ * pair_of[window * segments + q] the pair that segment q of that window multiplies. hf_bytes and
+ * xf_bytes: the payloads of the segment spectra [routes][segments][256][B] and of the pass's pair
+ * spectra [inputs][pairs][256][B]. The model of a pass, in rows of 8 B bytes: spectrum_rows (routes x
+ * segments x 256, read once), pair_cache_rows (routes x pairs x 256: the pair spectra re-read by
+ * every route, expected from L2 / Infinity Cache), fdl_rows and pair_rows_written (inputs x pairs x
+ * 256 each), output_rows (outputs x 128 windows, written and read: x 2); bytes = 8 B times their sum
+ * + 4 B blocks_per_pass (inputs + outputs), of which cache_bytes = 8 B pair_cache_rows. Arrays (each
+ * may be NULL): pair_row [segments + 1], pair_of [2][segments] (only `windows` rows are written). */
+typedef struct neo_hip_matrix_offline_plan_info {
+    int segments, windows, blocks_per_pass, pairs, min_ring_rows, ring_rows;
+    int64_t hf_bytes, xf_bytes;
+    int64_t spectrum_rows, pair_cache_rows, fdl_rows, pair_rows_written, output_rows;
+    int64_t bytes, cache_bytes;
+} neo_hip_matrix_offline_plan_info;
+NEO_HIP_API int neo_hip_matrix_offline_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                            const int* route_in, int nroutes, int windows, int write_pos, int ring_rows,
+                                            neo_hip_matrix_offline_plan_info* plan, int* pair_row, int* pair_of);
 /* The plan for a route list and options, on the host (no device needed; the handle is built from
  * the same function). Consecutive outputs form tiles of out_tile; a tile's row list is the union
  * of its outputs' inputs (ascending) x partitions 0..P-1, flattened, and split s of the S splits

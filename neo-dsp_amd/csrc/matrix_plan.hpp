@@ -198,4 +198,72 @@ inline const char* make_matrix_batch_plan(const matrix_plan& pl, int T, int spli
     return nullptr;
 }
 
+// -- offline windows (upols_matrix_offline.hip): WP windows of 128 blocks per pass -----------------
+//
+// Per bin the blocks t_W + j (j < 128) of a window are samples 128 + j of the 256-point circular
+// convolutions of PAIRS (256 consecutive ring rows: t_W - 128 (q + 1) ... + 255) with the segments
+// h_q (partitions 128 q ... + 127, zero past P), summed over q < nseg = ceil(P / 128). A pass at
+// write position w writes rows w .. w + 128 WP - 1 and reads back to w - 128 nseg; window 1's pair
+// of segment q is window 0's pair of segment q - 1, so a pass has nseg + WP - 1 pairs.
+constexpr int kMatrixOffWindow = 128;  // blocks per window (kFarT)
+constexpr int kMatrixOffMaxWP = 2;     // windows per pass
+
+constexpr int matrix_offline_segments(int P) { return (P + kMatrixOffWindow - 1) / kMatrixOffWindow; }
+// the least ring: a two-window pass's span, and one row more to keep the per-input stride off a
+// large power of two ("Ring and channel strides")
+constexpr int matrix_offline_ring(int P) { return kMatrixOffWindow * (matrix_offline_segments(P) + kMatrixOffMaxWP) + 1; }
+// the first ring row of pair k (k = 0 the newest: the last window's own rows and the 128 before)
+constexpr int matrix_offline_pair_row(int w, int wp, int k, int ring)
+{
+    const int r = (w + kMatrixOffWindow * (wp - 2 - k)) % ring;
+    return r < 0 ? r + ring : r;
+}
+// the pair that segment q of window `window` multiplies
+constexpr int matrix_offline_pair_of(int wp, int window, int q) { return q + wp - 1 - window; }
+
+struct matrix_offline_plan {
+    int nseg = 0, WP = 0, T = 0, npairs = 0, min_ring = 0, ring = 0;
+    std::vector<int> pair_row;  // [npairs]
+    int64_t hf_bytes = 0, xf_bytes = 0;  // payloads of the segment and pair spectra
+    // rows of B complex per pass: segment spectra read, pair spectra re-read per route (cache), FDL
+    // rows read, pair spectra written, output spectra written and read
+    int64_t spec_rows = 0, cache_rows = 0, fdl_rows = 0, xf_rows = 0, y_rows = 0;
+    int64_t bytes = 0, cache_bytes = 0;  // the model of a pass (cache_bytes is part of bytes)
+};
+
+// windows: 0 automatic (2), 1 or 2; write_pos: the ring row of the pass's first block; ring_rows:
+// 0 = the least ring
+inline const char* make_matrix_offline_plan(int I, int O, int B, int P, int nroutes, int windows, int write_pos,
+                                            int ring_rows, matrix_offline_plan& op)
+{
+    if (I < 1 || O < 1) return "inputs and outputs must be >= 1";
+    if (B < 16 || B > 4096 || (B & (B - 1))) return "block must be a power of two in [16, 4096]";
+    if (P < 1 || int64_t(P) * B * 8 >= (int64_t(1) << 31)) return "partitions must be >= 1 and a route's filter span < 2 GiB";
+    if (nroutes < 1) return "nroutes must be >= 1";
+    if (windows < 0 || windows > kMatrixOffMaxWP) return "windows per pass must be 0 (automatic), 1 or 2";
+    op = matrix_offline_plan{};
+    op.nseg = matrix_offline_segments(P);
+    op.WP = windows ? windows : kMatrixOffMaxWP;
+    op.T = kMatrixOffWindow * op.WP;
+    op.npairs = op.nseg + op.WP - 1;
+    op.min_ring = matrix_offline_ring(P);
+    op.ring = ring_rows ? ring_rows : op.min_ring;
+    if (op.ring < op.min_ring) return "ring_rows below 128 (segments + 2) + 1";
+    if (int64_t(op.ring) * B * 8 >= (int64_t(1) << 31)) return "an input's ring must span < 2 GiB";
+    if (write_pos < 0 || write_pos >= op.ring) return "write_pos outside the ring";
+    for (int k = 0; k < op.npairs; ++k) op.pair_row.push_back(matrix_offline_pair_row(write_pos, op.WP, k, op.ring));
+    const int64_t spec = 2 * kMatrixOffWindow;  // rows of a 256-point spectrum
+    op.hf_bytes = int64_t(nroutes) * op.nseg * spec * B * 8;
+    op.xf_bytes = int64_t(I) * op.npairs * spec * B * 8;
+    op.spec_rows = int64_t(nroutes) * op.nseg * spec;
+    op.cache_rows = int64_t(nroutes) * op.npairs * spec;
+    op.fdl_rows = int64_t(I) * op.npairs * spec;
+    op.xf_rows = int64_t(I) * op.npairs * spec;
+    op.y_rows = int64_t(O) * op.T * 2;
+    op.cache_bytes = 8 * int64_t(B) * op.cache_rows;
+    op.bytes = 8 * int64_t(B) * (op.spec_rows + op.cache_rows + op.fdl_rows + op.xf_rows + op.y_rows) +
+               4 * int64_t(B) * op.T * (I + O);
+    return nullptr;
+}
+
 }  // namespace neo_hip

@@ -373,6 +373,21 @@ int launch_batch_finish_nosave(int C, int B, int S, int T, bool ola, const cf* p
 // into the slabs part [O][Sb][T][B]; tab is the batch plan's run_off and runs (matrix_plan.hpp)
 int launch_matrix_batch_mac(const cf* H, const cf* fdl, cf* part, const int* tab, int B, int P, int ring, int O, int Sb,
                             int T, int w, hipStream_t s);
+// upols_levels.hip: k_lvf_filter, the segment spectra hf [C][nseg][256][B] (channel stride
+// lvf_spec_stride(nseg, B): one row more than the data) of the filter rows H + c cstride + p pstride,
+// p = 128 (s + seg0) + r, zero past P
+int launch_lvf_filter(const cf* H, cf* hf, const cf* tw, int C, int B, int P, int nseg, int64_t cstride, int64_t pstride,
+                      int seg0, hipStream_t s);
+int64_t lvf_spec_stride(int nseg, int B);
+// upols_matrix_offline.hip: the transforms of an offline pass of a matrix handle, wp windows of 128
+// blocks at write position w. fwd: the npairs = nseg + wp - 1 pairs of ring rows of every input
+// (matrix_offline_pair_row, matrix_plan.hpp) -> xf [I][npairs][256][B]. mac: per output its routes
+// (tab: off [O + 1], then {input, route} per entry, inputs ascending) x segments against hf, the
+// inverse transforms -> y [O][128 wp][B], one slab of launch_batch_finish_nosave.
+int launch_matrix_off_fwd(const cf* fdl, cf* xf, const cf* twf, int I, int B, int ring, int npairs, int wp, int w,
+                          hipStream_t s);
+int launch_matrix_off_mac(const cf* xf, const cf* hf, cf* y, const cf* twf, const int* tab, int O, int B, int nseg,
+                          int wp, int64_t hcs, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch
 // group is a timed one (every h->timing-th), else nullptr; mark(g, i, s) records event i.
 inline int timing_begin(upols_t* h, int nev, upols_t::ev_group** out)

@@ -23,6 +23,7 @@
 // pair per bin (segment 2) and keeps the spectra in a ring of NSEG slots (XF); the rest is a
 // stream of XF . HF products (far1_role / far2_role).
 #include "upols_device.hpp"
+#include "upols_far.hpp"
 #include "upols_handle.hpp"
 
 #include <algorithm>
@@ -88,60 +89,8 @@ void plan_levels(int P, level_plan& lp, int far)
 // ---------------------------------------------------------------------------------------
 // device helpers
 
-constexpr int kFN = 2 * kFarT;  // far level: partition-axis transform length
-
-// Channel strides (complex units) of the level buffers: kPad rows more than the data, so that no
-// channel stride is a multiple of a large power of two -- every channel's row n of a slab, of the
-// far field or of a segment spectrum would otherwise sit at the same offset modulo 512 KB .. 8 MB
-// (an FDL ring of 1280 rows, 5 x 2^20 bytes per channel at B = 512, cost the c5full step 4 %)
-#ifndef NEO_PAD
-#define NEO_PAD 1  // diagnostic builds (A/B): 0 = unpadded strides
-#endif
-constexpr int kPad = NEO_PAD;
-__host__ __device__ constexpr int64_t slab_cs(int T, int B) { return int64_t(T + kPad) * B; }
-__host__ __device__ constexpr int64_t ff_cs(int B) { return int64_t(kFarT + kPad) * B; }
-__host__ __device__ constexpr int64_t spec_cs(int nseg, int B) { return (int64_t(nseg) * kFN + kPad) * B; }
-
-// 256-point transforms of NC columns held by lanes (a, cp), a < 16, cp < NC: on entry
-// v[n2] = x[a + 16 n2], on exit v[k1] = X[16 k1 + a] (16-point DFTs in registers, twiddle,
-// LDS transpose, 16-point DFTs). Every lane of the workgroup calls it (barriers inside);
-// lanes with active = false only take part in the barriers.
-template<int DIR, int NC>
-__device__ __forceinline__ void col_fft(cf (&v)[16], cf* lds, const cf* tw, int a, int cp, bool active)
-{
-    if (active) {
-        dft<16, DIR>(v);
-#pragma unroll
-        for (int k = 1; k < 16; ++k) v[k] = cmul(v[k], twiddle<kFN, DIR>(tw, a * k));
-#pragma unroll
-        for (int k = 0; k < 16; ++k) lds[(k * 16 + a) * NC + cp] = v[k];
-    }
-    __syncthreads();
-    if (active) {
-#pragma unroll
-        for (int n = 0; n < 16; ++n) v[n] = lds[(a * 16 + n) * NC + cp];
-    }
-    __syncthreads();
-    if (active) dft<16, DIR>(v);
-}
-
-// packed complex MAC: acc = (re, im) += h x as (hr, hr)(xr, xi) + (-hi, hi)(xi, xr), two
-// v_pk_fma_f32; the packed bin 0 (DC, Nyquist: two real products) takes (hr, hi)(xr, xi)
-struct pk_coef {
-    f2v h1, h2;
-    __device__ __forceinline__ pk_coef(cf h, bool bin0)
-    {
-        const float s = bin0 ? 0.f : h.y;
-        h1 = f2v{h.x, bin0 ? h.y : h.x};
-        h2 = f2v{-s, s};
-    }
-    __device__ __forceinline__ void mac(f2v& acc, cf x) const
-    {
-        const f2v xv = {x.x, x.y};
-        acc = __builtin_elementwise_fma(h1, xv, acc);
-        acc = __builtin_elementwise_fma(h2, xv.yx, acc);
-    }
-};
+// kFN, the padded strides, col_fft, pk_coef, the buffer loads and stores and the bin-0 packing:
+// upols_far.hpp (shared with upols_matrix_offline.hip)
 
 // ---------------------------------------------------------------------------------------
 // The per-step slices kernel: one launch after every block step, workgroups by role.
@@ -398,24 +347,6 @@ __device__ __forceinline__ void block_role(const slice_args& a, int c, char* sme
     NEO_PS_MARK(a, 4);  // joined spectrum in LDS
     if (tid < 64) c2r_tail<B, OLA, EW, true, true, WT>(X, fft, tw, a.out + int64_t(c) * a.ld_out, prev_c, tid);
     NEO_PS_MARK(a, 5);  // output stores issued
-}
-
-// buffer loads / stores: 32-bit lane offsets, uniform offsets in SGPRs (fewer VGPRs than
-// 64-bit addresses); offsets past the size read 0
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, int64_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, int(bytes), 0x00020000);
-}
-
-__device__ __forceinline__ cf buf_ld(__amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    return __builtin_bit_cast(cf, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 2 /* streaming */));
-}
-
-__device__ __forceinline__ void buf_st(cf v, __amdgpu_buffer_rsrc_t r, int voff, int soff)
-{
-    typedef unsigned u2v __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, v), r, voff, soff, 0);
 }
 
 // Toeplitz levels' filter rows: nontemporal (the default) or, NEO_H_POLICY 1, the default cache
@@ -897,46 +828,7 @@ __device__ __forceinline__ void toep_big_role(const slice_args& sa, const toep_a
 // (0 < f < 128), with W[0] = (X_dc[0], X_ny[0]) and W[128] = (X_dc[128], X_ny[128]) real pairs
 // (k_lvf_filter packs the segment spectra the same way): the MAC is the same complex product
 // except two real products at f = 0 and 128, and one unpack before the inverse transform
-// restores Y = Y_dc + i Y_ny.
-
-// Z = DFT(x_dc + i x_ny) -> packed W (real-FFT packing of X_dc, X_ny) at f, from Z[f], Z[-f]
-__device__ __forceinline__ cf pack_bin0(cf zf, cf zm, int f)
-{
-    if (f == 0 || f == kFN / 2) return zf;  // (Re, Im) = (X_dc, X_ny), both real here
-    if (f < kFN / 2) return cscale(cadd(zf, cconj(zm)), 0.5f);  // X_dc[f]
-    const cf d = csub(zm, cconj(zf));                            // f > 128: X_ny[256 - f] = (Z[-f] - conj Z[f]) / 2i
-    return cf{0.5f * d.y, -0.5f * d.x};
-}
-
-// packed W of bin 0 -> Y = Y_dc + i Y_ny at f, from W[f], W[-f]
-__device__ __forceinline__ cf unpack_bin0(cf wf, cf wm, int f)
-{
-    if (f == 0 || f == kFN / 2) return wf;
-    // f < 128: Y_dc[f] + i Y_ny[f] = W[f] + i W[256 - f]; f > 128: conj(W[256 - f]) + i conj(W[f])
-    const cf dc = f < kFN / 2 ? wf : cconj(wm);
-    const cf ny = f < kFN / 2 ? wm : cconj(wf);
-    return cf{dc.x - ny.y, dc.y + ny.x};
-}
-
-// bin 0 (column 0, lanes cp == 0) of a spectrum held with v[i] at f = a + 16 i: pack or unpack
-// through LDS z; every lane calls (barrier inside)
-template<bool PACK>
-__device__ __forceinline__ void bin0_exchange(cf (&v)[16], cf* z, int a, int cp)
-{
-    if (cp == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) z[a + 16 * i] = v[i];
-    }
-    __syncthreads();
-    if (cp == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int f = a + 16 * i;
-            const cf m = z[(kFN - f) & (kFN - 1)];
-            v[i] = PACK ? pack_bin0(v[i], m, f) : unpack_bin0(v[i], m, f);
-        }
-    }
-}
+// restores Y = Y_dc + i Y_ny (pack_bin0, unpack_bin0, bin0_exchange: upols_far.hpp).
 
 // phase 1, FPL f rows per lane: a workgroup takes kF1UG units side by side (64 columns:
 // every wave-load reads 512 contiguous bytes of one f row) and 4 FPL f rows of them, so
@@ -2654,6 +2546,18 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
     h->lv_n = n + 1;
     return NEO_HIP_OK;
 }
+
+int launch_lvf_filter(const cf* H, cf* hf, const cf* tw, int C, int B, int P, int nseg, int64_t cstride, int64_t pstride,
+                      int seg0, hipStream_t s)
+{
+    const unsigned grid = unsigned(C) * unsigned(nseg) * unsigned(B / 16);
+    hipLaunchKernelGGL(k_lvf_filter, dim3(grid), dim3(256), 0, s, H, hf, tw, B, P, nseg, cstride, pstride, seg0,
+                       spec_cs(nseg, B));
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+int64_t lvf_spec_stride(int nseg, int B) { return spec_cs(nseg, B); }
 
 size_t off_hf_bytes(const upols_t* h) { return size_t(h->C) * size_t(spec_cs(h->off_nseg, h->B)) * sizeof(cf); }
 

@@ -32,6 +32,12 @@
 //   k_matrix_batch_mac  (upols_matrix_batch.hip) slabs part_b [O][Sb][T][B],
 //   k_batch_finish      grid O x T, without its save of the previous block (that state is per
 //                       input here), and k_batch_ola for overlap-add: the first writes of `out`.
+//
+// An offline pass (neo_hip_matrix_set_offline: one or two windows of 128 blocks, 256-point transforms
+// along the block axis; upols_matrix_offline.hip) needs R >= 128 (ceil(P / 128) + 2) + 1 rows. Its
+// launches: k_batch_window and k_matrix_save_prev as above, k_lvf_filter (the routes' segment
+// spectra, after a filter change only), k_matrix_off_fwd (per input), k_matrix_off_mac (per
+// output), then k_batch_finish on its one slab and k_batch_ola.
 #include "matrix_plan.hpp"
 #include "upols_handle.hpp"
 #include "upols_step.hpp"
@@ -64,6 +70,16 @@ struct neo_hip_matrix {
     neo_hip::cf* part_b = nullptr;     // [O][Sb][32][B]; these three from the first batched pass on
     float* tail = nullptr;             // [O][32][B] overlap-add tails of a pass
     int* btab = nullptr;               // bplan's run_off, runs
+    // offline windows (neo_hip_matrix_set_offline; upols_matrix_offline.hip)
+    bool offline = false;
+    int off_wp = 0;                    // windows per pass as given (0 auto)
+    bool off_dirty = true;             // off_hf follows the filter: recomputed at the next offline pass
+    neo_hip::cf* off_tw = nullptr;     // the 256-point table (shared); the rest from the first offline pass on
+    neo_hip::cf* off_hf = nullptr;     // [routes][nseg][256][B] (+ one row per route) segment spectra
+    neo_hip::cf* off_xf = nullptr;     // [I][nseg + 1][256][B] a pass's pair spectra
+    neo_hip::cf* off_y = nullptr;      // [O][256][B] a pass's output spectra
+    float* off_tail = nullptr;         // [O][256][B] overlap-add tails of a pass
+    int* off_tab = nullptr;            // off [O + 1], then {input, route} per route, inputs ascending per output
     neo_hip::stream_set used;
 };
 
@@ -312,9 +328,34 @@ void matrix_free_batch(matrix_t* m)
     m->btab = nullptr;
 }
 
+// the buffers of the offline windows follow the filter (the caller joined every stream that used them)
+void matrix_free_offline(matrix_t* m)
+{
+    dfree(m->off_hf);
+    dfree(m->off_xf);
+    dfree(m->off_y);
+    dfree(m->off_tail);
+    dfree(m->off_tab);
+    m->off_hf = m->off_xf = m->off_y = nullptr;
+    m->off_tail = nullptr;
+    m->off_tab = nullptr;
+    m->off_dirty = true;
+}
+
+int64_t matrix_offline_bytes(const matrix_t* m)
+{
+    if (!m->off_hf) return 0;
+    const int nseg = matrix_offline_segments(m->P);
+    const int64_t spec = int64_t(2 * kMatrixOffWindow) * m->B;
+    return (int64_t(m->plan.nroutes) * lvf_spec_stride(nseg, m->B) + int64_t(m->I) * (nseg + kMatrixOffMaxWP - 1) * spec +
+            int64_t(m->O) * spec) * int64_t(sizeof(cf)) +
+           (m->ola ? int64_t(m->O) * spec * int64_t(sizeof(float)) : 0);
+}
+
 void matrix_free_filter(matrix_t* m)
 {
     matrix_free_batch(m);
+    matrix_free_offline(m);
     dfree(m->H);
     dfree(m->part);
     dfree(m->arrivals);
@@ -456,11 +497,81 @@ int matrix_batch(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_
     return NEO_HIP_OK;
 }
 
-// the blocks of a call: with batching on the largest power-of-two passes <= 32 of the blocks left,
-// then single steps
+// the spectra, the overlap-add tails and the route table of the offline windows, at the first
+// offline pass after a filter (which joined the streams that used the old ones); a failure frees
+// what was taken and leaves batched passes and single steps as they were
+int matrix_offline_buffers(matrix_t* m, hipStream_t s)
+{
+    if (m->off_hf) return NEO_HIP_OK;
+    if (!m->off_tw)
+        if (int rc = shared_far_tw(&m->off_tw)) return rc;
+    const int nseg = matrix_offline_segments(m->P), I = m->I, O = m->O;
+    const size_t spec = size_t(2 * kMatrixOffWindow) * m->B;
+    std::vector<int> tab(size_t(O) + 1, 0);
+    for (int o = 0; o < O; ++o) {
+        for (int i = 0; i < I; ++i)
+            if (const int r = m->plan.rt[size_t(o) * I + i]; r >= 0) tab.insert(tab.end(), {i, r});
+        tab[size_t(o) + 1] = int(tab.size() - size_t(O) - 1) / 2;
+    }
+    if (dalloc(&m->off_hf, size_t(m->plan.nroutes) * size_t(lvf_spec_stride(nseg, m->B)) * sizeof(cf)) ||
+        dalloc(&m->off_xf, size_t(I) * (nseg + kMatrixOffMaxWP - 1) * spec * sizeof(cf)) ||
+        dalloc(&m->off_y, size_t(O) * spec * sizeof(cf)) ||
+        (m->ola && dalloc(&m->off_tail, size_t(O) * spec * sizeof(float))) || dalloc(&m->off_tab, tab.size() * sizeof(int))) {
+        matrix_free_offline(m);
+        return fail(NEO_HIP_ENOMEM, "matrix offline buffers: device allocation failed");
+    }
+    if (hipMemcpyAsync(m->off_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
+        matrix_free_offline(m);
+        return fail(NEO_HIP_ERUNTIME, "matrix offline buffers: table copy failed");
+    }
+    m->off_dirty = true;
+    return NEO_HIP_OK;
+}
+
+// wp windows of 128 blocks in one pass (the ring has 128 (nseg + 2) + 1 rows or more: set_offline, so
+// the rows the pass writes are none it reads): every read of `in` is in the first two launches,
+// every write of `out` in the last two
+int matrix_offline(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int wp, hipStream_t s)
+{
+    if (int rc = matrix_offline_buffers(m, s)) return rc;
+    matrix_offline_plan op;
+    if (const char* why = make_matrix_offline_plan(m->I, m->O, m->B, m->P, m->plan.nroutes, wp, m->wpos, m->ring, op))
+        return fail(NEO_HIP_EINVAL, "matrix offline pass: %s", why);
+    if (int rc = launch_batch_window(m->I, m->B, op.T, m->ola, in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos, s)) return rc;
+    if (!m->ola) {
+        hipLaunchKernelGGL(k_matrix_save_prev, dim3(unsigned(m->I)), dim3(256), 0, s, in, ld_in, m->prev, m->B, op.T);
+        NEO_HIP_LAUNCH_CHECK();
+    }
+    if (m->off_dirty) {  // the routes stand in for channels: stride P B, one partition per row
+        if (int rc = launch_lvf_filter(m->H, m->off_hf, m->off_tw, m->plan.nroutes, m->B, m->P, op.nseg,
+                                       int64_t(m->P) * m->B, m->B, 0, s))
+            return rc;
+        m->off_dirty = false;
+    }
+    // (pair k's rows: matrix_offline_pair_row, the function op.pair_row was filled from)
+    if (int rc = launch_matrix_off_fwd(m->fdl, m->off_xf, m->off_tw, m->I, m->B, op.ring, op.npairs, op.WP, m->wpos, s)) return rc;
+    if (int rc = launch_matrix_off_mac(m->off_xf, m->off_hf, m->off_y, m->off_tw, m->off_tab, m->O, m->B, op.nseg, op.WP,
+                                       lvf_spec_stride(op.nseg, m->B), s))
+        return rc;
+    if (int rc = launch_batch_finish_nosave(m->O, m->B, 1, op.T, m->ola, m->off_y, out, ld_out, m->off_tail, m->ovl, m->tw, s))
+        return rc;
+    m->wpos = (m->wpos + op.T) % m->ring;
+    return NEO_HIP_OK;
+}
+
+// the blocks of a call: with offline windows on passes of 256 (two windows, if allowed) and 128
+// blocks while that many are left; then with batching on the largest power-of-two passes <= 32 of
+// the blocks left, then single steps
 int matrix_blocks(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t nblocks, hipStream_t s)
 {
     for (int64_t t = 0; t < nblocks;) {
+        if (m->offline && nblocks - t >= kMatrixOffWindow) {
+            const int wp = m->off_wp != 1 && nblocks - t >= 2 * kMatrixOffWindow ? 2 : 1;
+            if (int rc = matrix_offline(m, in + t * m->B, ld_in, out + t * m->B, ld_out, wp, s)) return rc;
+            t += wp * kMatrixOffWindow;
+            continue;
+        }
         int T = 1;
         if (m->batch) {
             T = kMatrixBatch;
@@ -494,7 +605,7 @@ int matrix_grow_ring(matrix_t* m, int rows)
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
     if (e != hipSuccess) {
         dfree(fresh);
-        return fail(NEO_HIP_ERUNTIME, "matrix set_batch: re-laying the ring failed: %s", hipGetErrorString(e));
+        return fail(NEO_HIP_ERUNTIME, "matrix convolver: re-laying the ring failed: %s", hipGetErrorString(e));
     }
     dfree(m->fdl);
     m->fdl = fresh;
@@ -742,6 +853,72 @@ NEO_HIP_API int neo_hip_matrix_batch_info(neo_hip_matrix* m, int* blocks_per_pas
     return NEO_HIP_OK;
 }
 
+NEO_HIP_API int neo_hip_matrix_set_offline(neo_hip_matrix* m, int enable, int windows_per_pass)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable < 0 || enable > 1 || windows_per_pass < 0 || windows_per_pass > kMatrixOffMaxWP)
+        return fail(NEO_HIP_EINVAL, "matrix set_offline: enable must be 0 or 1, windows_per_pass 0 (automatic), 1 or 2");
+    const int rows = matrix_offline_ring(m->P);
+    if (enable && int64_t(std::max(rows, m->ring)) * m->B * int64_t(sizeof(cf)) >= (int64_t(1) << 31))
+        return fail(NEO_HIP_EINVAL, "matrix set_offline: an input's ring of %d rows must span < 2 GiB", rows);
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, false)) return rc;
+    if (enable && m->ring < rows)
+        if (int rc = matrix_grow_ring(m, rows)) return rc;  // (the state is as it was)
+    m->offline = enable != 0;  // off: the larger ring stays, the other passes read the same rows in the same order
+    m->off_wp = windows_per_pass;
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_offline_info(neo_hip_matrix* m, int* blocks_per_pass, int* segments, int* ring_rows,
+                                            int64_t* spectra_bytes)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (blocks_per_pass) *blocks_per_pass = m->offline ? kMatrixOffWindow * (m->off_wp == 1 ? 1 : kMatrixOffMaxWP) : 0;
+    if (segments) *segments = matrix_offline_segments(m->P);
+    if (ring_rows) *ring_rows = m->ring;
+    if (spectra_bytes)
+        *spectra_bytes = m->off_hf ? int64_t(m->plan.nroutes) * matrix_offline_segments(m->P) * 2 * kMatrixOffWindow * m->B *
+                                         int64_t(sizeof(cf))
+                                   : 0;
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_offline_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                            const int* route_in, int nroutes, int windows, int write_pos, int ring_rows,
+                                            neo_hip_matrix_offline_plan_info* plan, int* pair_row, int* pair_of)
+{
+    matrix_plan p;
+    if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, route_out, route_in, nroutes, -1, 0, 1, p))
+        return fail(NEO_HIP_EINVAL, "matrix_offline_plan: %s", why);
+    matrix_offline_plan op;
+    if (const char* why = make_matrix_offline_plan(inputs, outputs, block, partitions, nroutes, windows, write_pos, ring_rows, op))
+        return fail(NEO_HIP_EINVAL, "matrix_offline_plan: %s", why);
+    if (plan) {
+        plan->segments = op.nseg;
+        plan->windows = op.WP;
+        plan->blocks_per_pass = op.T;
+        plan->pairs = op.npairs;
+        plan->min_ring_rows = op.min_ring;
+        plan->ring_rows = op.ring;
+        plan->hf_bytes = op.hf_bytes;
+        plan->xf_bytes = op.xf_bytes;
+        plan->spectrum_rows = op.spec_rows;
+        plan->pair_cache_rows = op.cache_rows;
+        plan->fdl_rows = op.fdl_rows;
+        plan->pair_rows_written = op.xf_rows;
+        plan->output_rows = op.y_rows;
+        plan->bytes = op.bytes;
+        plan->cache_bytes = op.cache_bytes;
+    }
+    if (pair_row) std::copy(op.pair_row.begin(), op.pair_row.end(), pair_row);
+    if (pair_of)  // row `window` of [2][segments]
+        for (int w = 0; w < op.WP; ++w)
+            for (int q = 0; q < op.nseg; ++q) pair_of[int64_t(w) * op.nseg + q] = matrix_offline_pair_of(op.WP, w, q);
+    return NEO_HIP_OK;
+}
+
 NEO_HIP_API int neo_hip_matrix_batch_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
                                           const int* route_in, int nroutes, int blocks, int split_workgroups,
                                           neo_hip_matrix_batch_plan_info* plan, int* out_rows, int* run_off, int* run_in,
@@ -786,6 +963,7 @@ NEO_HIP_API int neo_hip_matrix_info(neo_hip_matrix* m, neo_hip_matrix_desc* d)
         d->routes = m->plan.nroutes, d->tiles = m->plan.ntiles, d->out_tile = m->plan.OT, d->splits = m->plan.S;
         d->fused = m->plan.fused ? 1 : 0;
         d->filter_bytes = int64_t(m->plan.nroutes) * m->P * m->B * int64_t(sizeof(cf));
+        d->offline_bytes = matrix_offline_bytes(m);
     }
     return NEO_HIP_OK;
 }

@@ -39,7 +39,7 @@ class MatrixDesc(ctypes.Structure):
     """neo_hip_matrix_desc (include/neo_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("inputs", "outputs", "block", "partitions", "method", "routes", "tiles",
                                             "out_tile", "splits", "fused")] + \
-               [("filter_bytes", ctypes.c_int64), ("fdl_bytes", ctypes.c_int64)]
+               [("filter_bytes", ctypes.c_int64), ("fdl_bytes", ctypes.c_int64), ("offline_bytes", ctypes.c_int64)]
 
 
 class MatrixPlanInfo(ctypes.Structure):
@@ -52,6 +52,14 @@ class MatrixBatchPlanInfo(ctypes.Structure):
     """neo_hip_matrix_batch_plan_info (include/neo_hip.h)."""
     _fields_ = [(n, ctypes.c_int) for n in ("blocks", "splits", "chunks", "runs")] + \
                [(n, ctypes.c_int64) for n in ("filter_row_loads", "fdl_row_loads", "slab_rows", "bytes")]
+
+
+class MatrixOfflinePlanInfo(ctypes.Structure):
+    """neo_hip_matrix_offline_plan_info (include/neo_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("segments", "windows", "blocks_per_pass", "pairs", "min_ring_rows",
+                                            "ring_rows")] + \
+               [(n, ctypes.c_int64) for n in ("hf_bytes", "xf_bytes", "spectrum_rows", "pair_cache_rows", "fdl_rows",
+                                              "pair_rows_written", "output_rows", "bytes", "cache_bytes")]
 
 
 class Perceptual(ctypes.Structure):
@@ -141,6 +149,9 @@ SIGNATURES = {
     "neo_hip_matrix_set_batch": (_i, [_vp, _i, _i]),
     "neo_hip_matrix_batch_info": (_i, [_vp, _vp, _vp, _vp]),
     "neo_hip_matrix_batch_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp] + [_vp] * 5),
+    "neo_hip_matrix_set_offline": (_i, [_vp, _i, _i]),
+    "neo_hip_matrix_offline_info": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "neo_hip_matrix_offline_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "neo_hip_overlap_create": (_i, [_i, _i, _i64, _i64, _i, ctypes.POINTER(_vp)]),
     "neo_hip_overlap_destroy": (_i, [_vp]),
     "neo_hip_overlap_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
@@ -170,7 +181,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 700  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 800  # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

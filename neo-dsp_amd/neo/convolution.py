@@ -56,6 +56,7 @@ __all__ = [
     "MatrixConvolver",
     "matrix_plan",
     "matrix_batch_plan",
+    "matrix_offline_plan",
     "matrix_convolve",
     "a_weighting",
     "amplitude_to_db",
@@ -1410,11 +1411,37 @@ def matrix_batch_plan(inputs: int, outputs: int, block_size: int, partitions: in
             "slab_rows": info.slab_rows, "bytes": info.bytes}
 
 
+def matrix_offline_plan(inputs: int, outputs: int, block_size: int, partitions: int, routes=None, windows: int = 0,
+                        write_pos: int = 0, ring_rows: int = 0) -> dict:
+    """The plan of an offline pass of a matrix convolver (neo_hip_matrix_offline_plan; no device
+    needed, the function the launcher takes its rows from): `windows` (0 = automatic = 2, 1 or 2)
+    windows of 128 blocks at ring row `write_pos` of a ring of `ring_rows` rows (0 = the least a
+    handle takes, min_ring_rows). segments = ceil(P / 128); a PAIR is 256 consecutive ring rows
+    (mod ring_rows): pair_rows[k] is the first row of pair k and pair_of[window][segment] the pair
+    that window's segment multiplies. hf_bytes / xf_bytes are the payloads of the segment and pair
+    spectra; `bytes` is the pass's model: 8 B (spectrum_rows + pair_cache_rows + fdl_rows +
+    pair_rows_written + output_rows) plus the block I/O, of which cache_bytes (the pair spectra
+    re-read once per route, expected from L2 / Infinity Cache) are 8 B pair_cache_rows."""
+    ro, ri = _routes(routes, inputs, outputs)
+    info = _native.MatrixOfflinePlanInfo()
+    nseg = max(1, (max(1, int(partitions)) + 127) // 128)
+    rows, of = np.zeros(nseg + 1, np.int32), np.zeros((2, nseg), np.int32)
+    _native.check(_native.load().neo_hip_matrix_offline_plan(int(inputs), int(outputs), int(block_size),
+                                                             int(partitions), _ptr(ro), _ptr(ri), len(ro), int(windows),
+                                                             int(write_pos), int(ring_rows), ctypes.byref(info),
+                                                             _ptr(rows), _ptr(of)))
+    d = {n: int(getattr(info, n)) for n, _ in _native.MatrixOfflinePlanInfo._fields_}
+    d["pair_rows"] = [int(r) for r in rows[:info.pairs]]
+    d["pair_of"] = [[int(k) for k in of[w, :info.segments]] for w in range(info.windows)]
+    return d
+
+
 class MatrixConvolver:
     """I inputs routed to O outputs: output o = the sum over its routes (o, i) of the UPOLS (or
     UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
     transform per output (neo_hip_matrix_*, include/neo_hip.h). Whole blocks: one block per step,
-    or with set_batch(True) up to 32 blocks of a call per pass over the filters."""
+    with set_batch(True) up to 32 blocks of a call per pass over the filters, with set_offline(True)
+    windows of 128 blocks by 256-point transforms along the block axis (long filters)."""
 
     OPTION_DEFAULTS = {"fused": -1, "split_workgroups": 0, "out_tile": 0}
 
@@ -1492,6 +1519,22 @@ class MatrixConvolver:
         _native.check(_native.load().neo_hip_matrix_batch_info(self._h, ctypes.byref(b), ctypes.byref(s), ctypes.byref(r)))
         return {"blocks_per_pass": b.value, "splits": s.value, "ring_rows": r.value}
 
+    def set_offline(self, enable: bool, windows_per_pass: int = 0) -> None:
+        """Offline windows (neo_hip_matrix_set_offline): process() runs passes of 256 blocks (two
+        windows; windows_per_pass 1: 128) while that many are left, by 256-point transforms along the
+        block axis: per input the forward ones, per output the inverse ones, per route ceil(P / 128)
+        spectrum products. The rest of a call goes as without it. Turning it on grows the inputs'
+        rings to 128 (ceil(P / 128) + 2) + 1 rows and keeps the stream."""
+        _native.check(_native.load().neo_hip_matrix_set_offline(self._h, int(bool(enable)), int(windows_per_pass)))
+
+    def offline_info(self) -> dict:
+        """blocks_per_pass (256 or 128; 0 with offline windows off), segments = ceil(P / 128), the
+        rows of every input's ring and the bytes of the segment spectra (0 until they are allocated)."""
+        b, g, r, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_matrix_offline_info(self._h, ctypes.byref(b), ctypes.byref(g),
+                                                                 ctypes.byref(r), ctypes.byref(n)))
+        return {"blocks_per_pass": b.value, "segments": g.value, "ring_rows": r.value, "spectra_bytes": n.value}
+
     # -- processing ---------------------------------------------------------
     def process(self, x, stream: int = 0):
         """x [I][n B] -> y [O][n B]: float32 ndarray (synchronous) or CUDA tensor (asynchronous on
@@ -1544,11 +1587,13 @@ class MatrixConvolver:
 
 
 def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upols", device: int = 0,
-                    batch: bool = False):
+                    batch: bool = False, offline: bool = False):
     """One shot: signal [I][n], ir [O][I][L] (routes None) or [nroutes][L] with routes a list of
     (out, in) and the output count max(out) + 1 -> [O][n padded to whole blocks]; the impulse is
     normalized over all routes, as dense_convolve normalizes over channels. batch=True runs the
     blocks in batched passes (MatrixConvolver.set_batch): the same results up to summation order.
+    offline=True runs windows of 128 blocks as offline passes (MatrixConvolver.set_offline) and the
+    rest of the call in batched passes: the same results up to rounding.
     A float32 CUDA tensor as signal (ir a tensor on the same device or an array) stays on the
     device and gives a tensor."""
     on_device = _is_torch(signal) and signal.is_cuda
@@ -1581,8 +1626,10 @@ def matrix_convolve(signal, ir, block_size: int, routes=None, method: str = "upo
     conv = MatrixConvolver(I, O, B, num_partitions(a.shape[-1], B), method=method, device=device)
     try:
         conv.set_impulse(a.contiguous() if _is_torch(a) else a, routes)
-        if batch:
+        if batch or offline:
             conv.set_batch(True)
+        if offline:
+            conv.set_offline(True)
         return conv.process(x)
     finally:
         conv.close()
