@@ -558,6 +558,10 @@ struct matrix_route {
     int in;
 };
 
+/// The gain curve of a matrix convolver's live filter update: linear g = t, cosine
+/// g = 0.5 - 0.5 cos(pi t), t = n / (fade_blocks B) (neo_hip_matrix_fade_gains).
+enum class fade_curve : int { linear = 0, cosine = 1 };
+
 /// Matrix (multi-input, multi-output) convolver over libneo_hip's neo_hip_matrix_* (include/neo_hip.h):
 /// output o = the sum over its routes (o, i) of what upols_convolver (M = method::upols) or
 /// upola_convolver (M = method::upola) gives for (input i, that route's filter). The reference has
@@ -612,7 +616,38 @@ struct hip_matrix_convolver {
                                                std::int64_t(num_blocks), device_memory ? 1 : 0, stream));
     }
 
+    /// clears all state; a running fade (update_filter) completes: the new filter is the filter
     auto reset() -> void { neo::hip::check(neo_hip_matrix_reset(_h.get())); }
+
+    /// live update (neo_hip_matrix_update_filter): crossfade to `partitions` ([routes][P][B+1], host
+    /// memory, the route order of the last filter()) over the next fade_blocks blocks and KEEP ALL
+    /// STATE -- delay lines, windows, overlap tails; filter() remains the resetting call. The route
+    /// list does not change. Complete on return; throws while a fade still runs.
+    auto update_filter(std::complex<float> const* partitions, int fade_blocks = 1, fade_curve curve = fade_curve::linear)
+        -> void
+    {
+        neo::hip::check(neo_hip_matrix_update_filter(_h.get(), partitions, 0, fade_blocks, int(curve), nullptr));
+    }
+
+    /// the same from impulse responses ir [routes][length] (host memory): normalize_impulse over all
+    /// routes' rows if `normalize`, then uniform_partition on the device; keeps all state
+    auto update_impulse(float const* ir, std::size_t length, bool normalize = true, int fade_blocks = 1,
+                        fade_curve curve = fade_curve::linear) -> void
+    {
+        neo::hip::check(neo_hip_matrix_update_impulse(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, 0, fade_blocks,
+                                                      int(curve), nullptr));
+    }
+
+    struct fade_desc {
+        int remaining_blocks, fade_blocks;
+        std::int64_t bank_bytes;  ///< the second filter bank, 0 until the first update after a filter
+    };
+    [[nodiscard]] auto fade_info() const -> fade_desc
+    {
+        fade_desc d{};
+        neo::hip::check(neo_hip_matrix_fade_info(_h.get(), &d.remaining_blocks, &d.fade_blocks, &d.bank_bytes));
+        return d;
+    }
 
     /// batched passes: process() runs up to 32 blocks of a call per pass over every route's filter
     /// (neo_hip_matrix_set_batch); the stream continues across the call. split_workgroups 0 = automatic

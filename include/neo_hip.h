@@ -83,8 +83,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.7.0: batched passes on matrix handles (neo_hip_matrix_set_batch, neo_hip_matrix_batch_info,
  *        neo_hip_matrix_batch_plan).
  * 0.8.0: offline windows on matrix handles (neo_hip_matrix_set_offline, neo_hip_matrix_offline_info,
- *        neo_hip_matrix_offline_plan; neo_hip_matrix_desc gains offline_bytes at its end). */
-#define NEO_HIP_VERSION 800 /* 0.8.0 */
+ *        neo_hip_matrix_offline_plan; neo_hip_matrix_desc gains offline_bytes at its end).
+ * 0.9.0: crossfaded live filter updates on matrix handles (neo_hip_matrix_update_filter,
+ *        neo_hip_matrix_update_impulse, neo_hip_matrix_fade_info, neo_hip_matrix_fade_gains). */
+#define NEO_HIP_VERSION 900 /* 0.9.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -496,7 +498,10 @@ NEO_HIP_API int neo_hip_upols_group_stats(neo_hip_upols_group* g, int* coalesced
  * Batched passes are the handle's second gear (neo_hip_matrix_set_batch below): with the blocks of a
  * call known up front, up to 32 of them share one pass over every route's filter. Offline windows
  * are the third (neo_hip_matrix_set_offline below): windows of 128 blocks by 256-point transforms
- * along the block axis, for long filters with every block of a call known up front. Streaming levels,
+ * along the block axis, for long filters with every block of a call known up front. A filter
+ * changes in one of two ways: neo_hip_matrix_set_filter / _set_impulse take a new route list and
+ * RESET all state; neo_hip_matrix_update_filter / _update_impulse (below) keep the route list and
+ * ALL state and crossfade to the new filter while audio runs. Streaming levels,
  * latency mode, sub-block input (method 2), groups and the multi-device convolver
  * do not apply to this handle type; for very long filters with one block per call (from 256
  * partitions at 512 routes and more) O * I replicated channels on a neo_hip_upols
@@ -538,7 +543,46 @@ NEO_HIP_API int neo_hip_matrix_set_impulse(neo_hip_matrix* m, const float* ir, i
  * the two may overlap in any way. EINVAL before the first set_filter / set_impulse. */
 NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64_t ld_in, float* out, int64_t ld_out,
                                        int64_t nblocks, int is_device, void* stream);
+/* Clears all state. A running fade (below) completes: the new filter is the filter. */
 NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m);
+/* Live filter update: crossfade from the handle's filter A to `filter` (B) over the next fade_blocks
+ * blocks, keeping ALL state (delay lines, overlap-save windows, overlap-add tails); set_filter
+ * remains the resetting call. filter [nroutes][P][B+1] complex in the route order of the last
+ * set_filter / set_impulse; the route list does not change (a route that is to vanish gets zeros).
+ * With y_A, y_B the outputs of two convolvers with filters A and B fed the whole input from the
+ * start, sample n = 0 .. fade_blocks * B - 1 of the next fade_blocks blocks is
+ * y_A + g[n] (y_B - y_A) (the kernel's form of (1 - g) y_A + g y_B), g as neo_hip_matrix_fade_gains
+ * gives it; every block after them is y_B, bit for bit what a handle that had B from the start
+ * gives (overlap-add: from the second block after the fade on; the first takes a tail summed in the
+ * fade kernel's order). The new filter is packed into a second bank, allocated at the first update
+ * after a set_filter / set_impulse (neo_hip_matrix_fade_info reports it; beside it the fade's slabs
+ * [O][splits][2][B] and, overlap-add, a second set of tails [O][B]); no update re-plans or
+ * re-allocates after that. While a fade has blocks left, neo_hip_matrix_process runs them as single
+ * fade steps (three launches: the inputs' windows, both banks against the same delay-line rows, two
+ * inverse transforms and the mix per output) whatever set_batch / set_offline say, then swaps the
+ * banks and goes on in passes. Equal calls give equal bits.
+ * STREAM CONTRACT: `stream` must be the stream the caller's neo_hip_matrix_process calls run on, or
+ * be ordered with it (after every earlier process call, before every later one): the update reads
+ * the delay lines those calls write (overlap-add) and writes the bank the later ones read. Device
+ * pointer: asynchronous on `stream` (NULL = the HIP null stream). Host pointer: staged on `stream`
+ * (NULL = the handle's stream, as host process calls), returns when the bank is written.
+ * EINVAL, the handle unchanged: before a filter is set, fade_blocks < 1, curve not 0 (linear) or 1
+ * (raised cosine), or while a fade has blocks left. set_filter / set_impulse cancel a running fade
+ * (and free the second bank: the route list may change); set_batch / set_offline keep it. */
+NEO_HIP_API int neo_hip_matrix_update_filter(neo_hip_matrix* m, const void* filter, int is_device, int fade_blocks,
+                                             int curve, void* stream);
+/* The same from ir [nroutes][length] float (host or device): normalize_impulse over all routes' rows
+ * if `normalize`, then uniform_partition on the device into the second bank, as set_impulse does. */
+NEO_HIP_API int neo_hip_matrix_update_impulse(neo_hip_matrix* m, const float* ir, int64_t length, int normalize,
+                                              int is_device, int fade_blocks, int curve, void* stream);
+/* blocks left of the running fade (0: none), its length (0: none) and the bytes of the second filter
+ * bank (0 until the first update after a filter; then neo_hip_matrix_desc.filter_bytes) */
+NEO_HIP_API int neo_hip_matrix_fade_info(neo_hip_matrix* m, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes);
+/* Host only: the fade_blocks * block gains g[n] of a fade, t = n / (fade_blocks * block): curve 0
+ * g = t, curve 1 g = 0.5 - 0.5 cos(pi t), evaluated in float64 and rounded to float32; the kernel
+ * evaluates the same expression. EINVAL for a block that is no power of two in [16, 4096],
+ * fade_blocks < 1 (or > 2^20) and an unknown curve. */
+NEO_HIP_API int neo_hip_matrix_fade_gains(int block, int fade_blocks, int curve, float* g);
 /* what the handle runs; routes, tiles, out_tile, splits, fused and filter_bytes are 0 until a filter is set */
 typedef struct neo_hip_matrix_desc {
     int inputs, outputs, block, partitions, method;

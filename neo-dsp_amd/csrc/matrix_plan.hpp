@@ -124,6 +124,27 @@ inline const char* make_matrix_plan(int I, int O, int B, int P, const int* route
     return nullptr;
 }
 
+// -- live filter updates (upols_matrix_fade.hip): the fade step runs one output per workgroup -------
+//
+// The splits of the fade step for a checked plan: the plain step's rule for the MAC + finish form
+// (about 1024 workgroups, >= 8 rows per split; an explicit workgroup target is taken as given) on the
+// output with the most rows, `chunks` workgroups per row (matrix_fade_chunks); no empty split in it.
+inline int matrix_fade_splits(const matrix_plan& pl, int split_wgs, int chunks)
+{
+    int maxrows = 1;
+    for (int o = 0; o < pl.O; ++o) {
+        int n = 0;
+        for (int i = 0; i < pl.I; ++i) n += pl.rt[size_t(o) * pl.I + i] >= 0;
+        maxrows = std::max(maxrows, n * pl.P);
+    }
+    const int64_t per_split = int64_t(pl.O) * chunks;
+    const int64_t want = ((split_wgs ? split_wgs : 1024) + per_split - 1) / per_split;
+    const int min_rows = split_wgs ? 1 : 8;
+    const int S = int(std::max<int64_t>(1, std::min<int64_t>({want, (maxrows + min_rows - 1) / min_rows, kMatrixMaxSplits})));
+    const int per = (maxrows + S - 1) / S;
+    return (maxrows + per - 1) / per;
+}
+
 // -- batched passes (upols_matrix_batch.hip): T blocks share one pass over every route's filter ----
 //
 // One output per workgroup (the out_tile = 1 row list: the output's inputs ascending x partitions

@@ -388,6 +388,17 @@ int launch_matrix_off_fwd(const cf* fdl, cf* xf, const cf* twf, int I, int B, in
                           hipStream_t s);
 int launch_matrix_off_mac(const cf* xf, const cf* hf, cf* y, const cf* twf, const int* tab, int O, int B, int nseg,
                           int wp, int64_t hcs, hipStream_t s);
+// upols_matrix_fade.hip: the fade step of a live filter update of a matrix handle. mac: both banks
+// HA, HB [nroutes][P][B] against the FDL at write position w into the slabs part [O][S][2][B] (tab:
+// off [O + 1], then {input, route} per entry, inputs ascending; grid O x S x matrix_fade_chunks).
+// finish: per output both banks' slabs summed in order, two c2r, out = a + g (b - a) for the samples
+// n0 .. n0 + B - 1 of a fade of `total` samples; overlap-add keeps a tail per bank (ovl_a, ovl_b
+// [O][B]). prime (overlap-add): bank B's transform alone, its second half into ovl_b, no output.
+int matrix_fade_chunks(int B);
+int launch_matrix_fade_mac(const cf* HA, const cf* HB, const cf* fdl, cf* part, const int* tab, int B, int P, int ring,
+                           int O, int S, int w, hipStream_t s);
+int launch_matrix_fade_finish(const cf* part, float* out, int64_t ld_out, float* ovl_a, float* ovl_b, const cf* tw, int B,
+                              int O, int S, bool ola, bool prime, int64_t n0, int64_t total, int curve, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch
 // group is a timed one (every h->timing-th), else nullptr; mark(g, i, s) records event i.
 inline int timing_begin(upols_t* h, int nev, upols_t::ev_group** out)

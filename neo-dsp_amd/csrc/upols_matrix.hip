@@ -38,6 +38,15 @@
 // launches: k_batch_window and k_matrix_save_prev as above, k_lvf_filter (the routes' segment
 // spectra, after a filter change only), k_matrix_off_fwd (per input), k_matrix_off_mac (per
 // output), then k_batch_finish on its one slab and k_batch_ola.
+//
+// A live filter update (neo_hip_matrix_update_filter / _update_impulse; upols_matrix_fade.hip) packs
+// the new filter into a second bank H2 and crossfades to it over fade_blocks blocks without touching
+// any state: while the fade has blocks left a block is k_matrix_window, k_matrix_fade_step (both
+// banks against the same FDL rows) and k_matrix_fade_finish (two c2r, the time-domain mix), whatever
+// set_batch / set_offline say; after the last one the banks swap (pointers) and the call goes on in
+// passes as before. Overlap-add keeps a tail per bank; bank B's tail of the block before the update
+// is formed at the update call by one MAC at write position w - 1 (its rows are all intact).
+#include "matrix_fade.hpp"
 #include "matrix_plan.hpp"
 #include "upols_handle.hpp"
 #include "upols_step.hpp"
@@ -80,6 +89,13 @@ struct neo_hip_matrix {
     neo_hip::cf* off_y = nullptr;      // [O][256][B] a pass's output spectra
     float* off_tail = nullptr;         // [O][256][B] overlap-add tails of a pass
     int* off_tab = nullptr;            // off [O + 1], then {input, route} per route, inputs ascending per output
+    // live filter updates (neo_hip_matrix_update_filter; upols_matrix_fade.hip): from the first update after a filter on
+    neo_hip::cf* H2 = nullptr;     // the spare bank [nroutes][P][B]: bank B while a fade runs
+    neo_hip::cf* part2 = nullptr;  // [O][fade_S][2][B] the fade step's slabs
+    float* ovl2 = nullptr;         // [O][B] bank B's overlap-add tails
+    int* ftab = nullptr;           // off [O + 1], then {input, route} per route, inputs ascending per output
+    int fade_S = 1;
+    int fade_left = 0, fade_total = 0, fade_curve = 0;  // blocks left of the running fade (0: none)
     neo_hip::stream_set used;
 };
 
@@ -352,10 +368,25 @@ int64_t matrix_offline_bytes(const matrix_t* m)
            (m->ola ? int64_t(m->O) * spec * int64_t(sizeof(float)) : 0);
 }
 
+// the buffers of the live updates follow the route list; a running fade ends with them (the caller
+// joined every stream that used them)
+void matrix_free_fade(matrix_t* m)
+{
+    dfree(m->H2);
+    dfree(m->part2);
+    dfree(m->ovl2);
+    dfree(m->ftab);
+    m->H2 = m->part2 = nullptr;
+    m->ovl2 = nullptr;
+    m->ftab = nullptr;
+    m->fade_left = m->fade_total = 0;
+}
+
 void matrix_free_filter(matrix_t* m)
 {
     matrix_free_batch(m);
     matrix_free_offline(m);
+    matrix_free_fade(m);
     dfree(m->H);
     dfree(m->part);
     dfree(m->arrivals);
@@ -560,12 +591,102 @@ int matrix_offline(matrix_t* m, const float* in, int64_t ld_in, float* out, int6
     return NEO_HIP_OK;
 }
 
-// the blocks of a call: with offline windows on passes of 256 (two windows, if allowed) and 128
-// blocks while that many are left; then with batching on the largest power-of-two passes <= 32 of
-// the blocks left, then single steps
+// the spare bank, the fade step's slabs and table and bank B's overlap-add tails, at the first update
+// after a filter; a failure frees what was taken and leaves the handle as it was
+int matrix_fade_buffers(matrix_t* m, hipStream_t s)
+{
+    if (m->H2) return NEO_HIP_OK;
+    const int I = m->I, O = m->O;
+    std::vector<int> tab(size_t(O) + 1, 0);
+    for (int o = 0; o < O; ++o) {
+        for (int i = 0; i < I; ++i)
+            if (const int r = m->plan.rt[size_t(o) * I + i]; r >= 0) tab.insert(tab.end(), {i, r});
+        tab[size_t(o) + 1] = int(tab.size() - size_t(O) - 1) / 2;
+    }
+    m->fade_S = matrix_fade_splits(m->plan, m->o_split, matrix_fade_chunks(m->B));
+    const size_t rowbytes = size_t(m->B) * sizeof(cf);
+    if (dalloc(&m->H2, size_t(m->plan.nroutes) * m->P * rowbytes) || dalloc(&m->part2, size_t(O) * m->fade_S * 2 * rowbytes) ||
+        (m->ola && dalloc(&m->ovl2, size_t(O) * m->B * sizeof(float))) || dalloc(&m->ftab, tab.size() * sizeof(int))) {
+        matrix_free_fade(m);
+        return fail(NEO_HIP_ENOMEM, "matrix update: device allocation of the second filter bank failed");
+    }
+    if (hipMemcpyAsync(m->ftab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
+        matrix_free_fade(m);
+        return fail(NEO_HIP_ERUNTIME, "matrix update: table copy failed");
+    }
+    return NEO_HIP_OK;
+}
+
+// what every update checks before it touches anything
+int matrix_update_check(const matrix_t* m, int fade_blocks, int curve)
+{
+    if (!m->ready) return fail(NEO_HIP_EINVAL, "matrix update: no filter set (neo_hip_matrix_set_filter)");
+    if (fade_blocks < 1 || fade_blocks > kMatrixFadeMaxBlocks)
+        return fail(NEO_HIP_EINVAL, "matrix update: fade_blocks must be in [1, %d]", kMatrixFadeMaxBlocks);
+    if (curve < 0 || curve >= kMatrixFadeCurves)
+        return fail(NEO_HIP_EINVAL, "matrix update: curve must be 0 (linear) or 1 (raised cosine)");
+    if (m->fade_left > 0) return fail(NEO_HIP_EINVAL, "matrix update: a fade is still running (%d blocks left)", m->fade_left);
+    return NEO_HIP_OK;
+}
+
+// bank B (H2) is written on s: overlap-add's tail of the block before (the rows (w - 1 - p) mod
+// ring, p < P, are all intact: a step writes row w alone), then the fade is armed
+int matrix_fade_arm(matrix_t* m, int fade_blocks, int curve, hipStream_t s)
+{
+    if (m->ola) {
+        const int w1 = m->wpos ? m->wpos - 1 : m->ring - 1;
+        if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->ftab, m->B, m->P, m->ring, m->O, m->fade_S, w1, s))
+            return rc;
+        if (int rc = launch_matrix_fade_finish(m->part2, nullptr, 0, m->ovl, m->ovl2, m->tw, m->B, m->O, m->fade_S, true, true,
+                                               0, 1, 0, s))
+            return rc;
+    }
+    m->fade_left = m->fade_total = fade_blocks;
+    m->fade_curve = curve;
+    return NEO_HIP_OK;
+}
+
+// the end of a fade: bank B is the filter (pointers swap, no copy), the offline segment spectra follow it
+void matrix_fade_swap(matrix_t* m)
+{
+    std::swap(m->H, m->H2);
+    if (m->ola) std::swap(m->ovl, m->ovl2);
+    m->fade_left = m->fade_total = 0;
+    m->off_dirty = true;
+}
+
+// one block of a running fade: the window launch as ever, then both banks against the same FDL rows
+int matrix_fade_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+#define NEO_MATRIX_WINDOW(OL)                                                                                          \
+    NEO_UPOLS_DISPATCH(m->B, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s, in, \
+                                                ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
+    if (m->ola) NEO_MATRIX_WINDOW(true) else NEO_MATRIX_WINDOW(false)
+#undef NEO_MATRIX_WINDOW
+    NEO_HIP_LAUNCH_CHECK();
+    if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->ftab, m->B, m->P, m->ring, m->O, m->fade_S, m->wpos, s))
+        return rc;
+    const int64_t n0 = int64_t(m->fade_total - m->fade_left) * m->B;
+    if (int rc = launch_matrix_fade_finish(m->part2, out, ld_out, m->ovl, m->ovl2, m->tw, m->B, m->O, m->fade_S, m->ola, false,
+                                           n0, int64_t(m->fade_total) * m->B, m->fade_curve, s))
+        return rc;
+    m->wpos = m->wpos + 1 >= m->ring ? 0 : m->wpos + 1;
+    if (--m->fade_left == 0) matrix_fade_swap(m);
+    return NEO_HIP_OK;
+}
+
+// the blocks of a call: while a fade has blocks left single fade steps; with offline windows on
+// passes of 256 (two windows, if allowed) and 128 blocks while that many are left; then with batching
+// on the largest power-of-two passes <= 32 of the blocks left, then single steps
 int matrix_blocks(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t nblocks, hipStream_t s)
 {
     for (int64_t t = 0; t < nblocks;) {
+        if (m->fade_left > 0) {
+            if (int rc = matrix_fade_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s)) return rc;
+            ++t;
+            continue;
+        }
         if (m->offline && nblocks - t >= kMatrixOffWindow) {
             const int wp = m->off_wp != 1 && nblocks - t >= 2 * kMatrixOffWindow ? 2 : 1;
             if (int rc = matrix_offline(m, in + t * m->B, ld_in, out + t * m->B, ld_out, wp, s)) return rc;
@@ -813,8 +934,82 @@ NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m)
     device_guard g(m->device);
     if (g.rc) return g.rc;
     if (int rc = matrix_join(m, false)) return rc;
+    if (m->fade_left > 0) matrix_fade_swap(m);  // a running fade completes: the new filter is the filter
     if (int rc = matrix_reset_state(m, m->stream)) return rc;
     NEO_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_update_filter(neo_hip_matrix* m, const void* filter, int is_device, int fade_blocks,
+                                             int curve, void* stream)
+{
+    if (!m || !filter) return fail(NEO_HIP_EINVAL, "null handle or filter");
+    if (int rc = matrix_update_check(m, fade_blocks, curve)) return rc;
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;
+    if (int rc = m->used.note(s)) return rc;
+    if (int rc = matrix_fade_buffers(m, s)) return rc;
+    const int64_t rows = int64_t(m->plan.nroutes) * m->P;
+    const size_t bytes = size_t(rows) * size_t(m->B + 1) * sizeof(cf);
+    const cf* src = static_cast<const cf*>(filter);
+    cf* tmp = nullptr;
+    int rc = NEO_HIP_OK;
+    if (!is_device) {
+        if ((rc = dalloc(&tmp, bytes))) return rc;
+        if (hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
+        src = tmp;
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_matrix_pack, dim3(unsigned((rows * m->B + 255) / 256)), dim3(256), 0, s, src, m->H2, m->B, rows);
+        if (hipGetLastError() != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "pack launch failed");
+    }
+    if (!rc) rc = matrix_fade_arm(m, fade_blocks, curve, s);
+    if (!is_device) {  // staged: returns when the bank is written
+        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+        dfree(tmp);
+    }
+    if (rc) m->fade_left = m->fade_total = 0;
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_matrix_update_impulse(neo_hip_matrix* m, const float* ir, int64_t length, int normalize,
+                                              int is_device, int fade_blocks, int curve, void* stream)
+{
+    if (!m || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
+    if (partitions_for(length, m->B) != m->P)
+        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
+                    (long long)partitions_for(length, m->B), m->P);
+    if (int rc = matrix_update_check(m, fade_blocks, curve)) return rc;
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;
+    if (int rc = m->used.note(s)) return rc;
+    if (int rc = matrix_fade_buffers(m, s)) return rc;
+    const int nroutes = m->plan.nroutes;
+    const size_t bytes = size_t(nroutes) * size_t(length) * sizeof(float);
+    float* d = nullptr;  // stream-ordered: a device impulse leaves the call asynchronous
+    NEO_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, s));
+    int rc = NEO_HIP_OK;
+    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
+    if (!rc && normalize) rc = normalize_device(d, nroutes, length, s);
+    if (!rc) rc = partition_device(d, nroutes, length, m->B, true, m->H2, m->tw, s, int64_t(m->P) * m->B, m->B);
+    if (hipFreeAsync(d, s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "impulse scratch free failed");
+    if (!rc) rc = matrix_fade_arm(m, fade_blocks, curve, s);
+    if (!is_device)
+        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    if (rc) m->fade_left = m->fade_total = 0;
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_matrix_fade_info(neo_hip_matrix* m, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (remaining_blocks) *remaining_blocks = m->fade_left;
+    if (fade_blocks) *fade_blocks = m->fade_total;
+    if (bank_bytes) *bank_bytes = m->H2 ? int64_t(m->plan.nroutes) * m->P * m->B * int64_t(sizeof(cf)) : 0;
     return NEO_HIP_OK;
 }
 

@@ -152,6 +152,10 @@ SIGNATURES = {
     "neo_hip_matrix_set_offline": (_i, [_vp, _i, _i]),
     "neo_hip_matrix_offline_info": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "neo_hip_matrix_offline_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "neo_hip_matrix_update_filter": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "neo_hip_matrix_update_impulse": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "neo_hip_matrix_fade_info": (_i, [_vp, _vp, _vp, _vp]),
+    "neo_hip_matrix_fade_gains": (_i, [_i, _i, _i, _vp]),
     "neo_hip_overlap_create": (_i, [_i, _i, _i64, _i64, _i, ctypes.POINTER(_vp)]),
     "neo_hip_overlap_destroy": (_i, [_vp]),
     "neo_hip_overlap_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
@@ -181,7 +185,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 800  # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 900 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

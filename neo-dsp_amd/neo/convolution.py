@@ -58,6 +58,7 @@ __all__ = [
     "matrix_batch_plan",
     "matrix_offline_plan",
     "matrix_convolve",
+    "matrix_fade_gains",
     "a_weighting",
     "amplitude_to_db",
     "PerceptualSparsity",
@@ -1436,6 +1437,25 @@ def matrix_offline_plan(inputs: int, outputs: int, block_size: int, partitions: 
     return d
 
 
+def _fade_curve(curve) -> int:
+    if isinstance(curve, str):
+        if curve not in MatrixConvolver.FADE_CURVES:
+            raise ValueError(f"curve must be one of {sorted(MatrixConvolver.FADE_CURVES)}, got {curve!r}")
+        return MatrixConvolver.FADE_CURVES[curve]
+    return int(curve)  # the library's number (an unknown one is its EINVAL)
+
+
+def matrix_fade_gains(block: int, fade_blocks: int, curve="linear") -> np.ndarray:
+    """The fade_blocks * block float32 gains g[n] of a live filter update (neo_hip_matrix_fade_gains;
+    no device needed, the expression the kernel evaluates): t = n / (fade_blocks * block), "linear"
+    (0) g = t, "cosine" (1) g = 0.5 - 0.5 cos(pi t). Sample n of the fade is y_A + g[n] (y_B - y_A)."""
+    c = _fade_curve(curve)
+    ok = 1 <= int(fade_blocks) <= 1 << 20 and 16 <= int(block) <= 4096  # else the library's EINVAL, nothing written
+    g = np.zeros(int(fade_blocks) * int(block) if ok else 1, np.float32)
+    _native.check(_native.load().neo_hip_matrix_fade_gains(int(block), int(fade_blocks), c, _ptr(g)))
+    return g
+
+
 class MatrixConvolver:
     """I inputs routed to O outputs: output o = the sum over its routes (o, i) of the UPOLS (or
     UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
@@ -1504,7 +1524,77 @@ class MatrixConvolver:
         _native.check(lib.neo_hip_matrix_set_impulse(self._h, _ptr(a), L, _ptr(ro), _ptr(ri), len(ro), int(normalize), 0))
 
     def reset(self) -> None:
+        """Clears all state; a running fade (update_filter) completes: the new filter is the filter."""
         _native.check(_native.load().neo_hip_matrix_reset(self._h))
+
+    # -- live updates -------------------------------------------------------
+    FADE_CURVES = {"linear": 0, "cosine": 1}
+
+    def update_filter(self, partitions, fade_blocks: int = 1, curve: str = "linear", stream: int = 0) -> None:
+        """Live update (neo_hip_matrix_update_filter): crossfade to `partitions` over the next
+        fade_blocks blocks and KEEP ALL STATE; filter() remains the resetting call. partitions
+        [nroutes][P][B+1] (dense: [O][I][P][B+1]) in the route order of the last filter() /
+        set_impulse(): the route list does not change. Sample n of the fade is
+        y_A + g[n] (y_B - y_A) with g = matrix_fade_gains(block_size, fade_blocks, curve); curve
+        "linear" or "cosine". A CUDA tensor: asynchronous on torch's current stream (or `stream`),
+        which must be the stream process() runs on; an ndarray: complete on return."""
+        shape = (self.info()["routes"], self.partitions, self.block_size + 1)
+        c = _fade_curve(curve)
+        lib = _native.load()
+        if not shape[0]:  # no filter set: the library's refusal
+            _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(np.zeros(1, np.complex64)), 0, int(fade_blocks), c, None))
+        if _is_torch(partitions) and partitions.is_cuda:
+            import torch
+
+            t = partitions
+            if t.dtype != torch.complex64 or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+                raise ValueError(f"filter must be a contiguous complex64 tensor of {shape} elements")
+            _producer_join(t)
+            s = stream or torch.cuda.current_stream(t.device).cuda_stream
+            _native.check(lib.neo_hip_matrix_update_filter(self._h, ctypes.c_void_p(t.data_ptr()), 1, int(fade_blocks), c,
+                                                           ctypes.c_void_p(s)))
+            return
+        H = np.ascontiguousarray(partitions, dtype=np.complex64)
+        if H.size != int(np.prod(shape)):
+            raise ValueError(f"filter of {H.shape} does not hold {shape}")
+        _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(H), 0, int(fade_blocks), c,
+                                                       ctypes.c_void_p(stream) if stream else None))
+
+    def update_impulse(self, ir, normalize: bool = True, fade_blocks: int = 1, curve: str = "linear",
+                       stream: int = 0) -> None:
+        """update_filter from impulse responses [nroutes][L] (dense: [O][I][L]) float32:
+        normalize_impulse over all routes' rows (optional), then uniform_partition on the device
+        into the second bank (neo_hip_matrix_update_impulse). Keeps all state."""
+        nroutes = self.info()["routes"]
+        c = _fade_curve(curve)
+        lib = _native.load()
+        if not nroutes:  # no filter set: the library's refusal
+            _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(np.zeros(1, np.complex64)), 0, int(fade_blocks), c, None))
+        if _is_torch(ir) and ir.is_cuda:
+            import torch
+
+            t = ir
+            L = t.shape[-1]
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != nroutes * L:
+                raise ValueError("impulse must be a contiguous float32 tensor of one row per route")
+            _producer_join(t)
+            s = stream or torch.cuda.current_stream(t.device).cuda_stream
+            _native.check(lib.neo_hip_matrix_update_impulse(self._h, ctypes.c_void_p(t.data_ptr()), L, int(normalize), 1,
+                                                            int(fade_blocks), c, ctypes.c_void_p(s)))
+            return
+        a = np.ascontiguousarray(ir, dtype=np.float32)
+        L = a.shape[-1]
+        if a.size != nroutes * L:
+            raise ValueError("impulse must hold one row per route")
+        _native.check(lib.neo_hip_matrix_update_impulse(self._h, _ptr(a), L, int(normalize), 0, int(fade_blocks), c,
+                                                        ctypes.c_void_p(stream) if stream else None))
+
+    def fade_info(self) -> dict:
+        """remaining_blocks of the running fade (0: none), its fade_blocks (0: none) and bank_bytes,
+        the second filter bank (0 until the first update after a filter; then info()["filter_bytes"])."""
+        r, f, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_matrix_fade_info(self._h, ctypes.byref(r), ctypes.byref(f), ctypes.byref(n)))
+        return {"remaining_blocks": r.value, "fade_blocks": f.value, "bank_bytes": n.value}
 
     def set_batch(self, enable: bool, split_workgroups: int = 0) -> None:
         """Batched passes (neo_hip_matrix_set_batch): process() cuts a call into passes of up to 32
