@@ -124,6 +124,38 @@ inline const char* make_matrix_plan(int I, int O, int B, int P, const int* route
     return nullptr;
 }
 
+// -- the device tables of a checked plan (the handle uploads both with the filter) -----------------
+//
+// What k_matrix_step reads: tiles [ntiles][4] {first output, outputs, inputs, offset into the
+// unions}, the tiles' unions, the route matrix rt [O][I].
+inline std::vector<int> matrix_tile_table(const matrix_plan& p)
+{
+    std::vector<int> tab;
+    tab.reserve(size_t(4) * p.ntiles + p.uni.size() + p.rt.size());
+    for (int t = 0; t < p.ntiles; ++t) {
+        tab.push_back(p.tile_first[size_t(t)]);
+        tab.push_back(p.tile_count[size_t(t)]);
+        tab.push_back(p.uni_off[size_t(t) + 1] - p.uni_off[size_t(t)]);
+        tab.push_back(p.uni_off[size_t(t)]);
+    }
+    tab.insert(tab.end(), p.uni.begin(), p.uni.end());
+    tab.insert(tab.end(), p.rt.begin(), p.rt.end());
+    return tab;
+}
+
+// What the kernels with one output per workgroup read (k_matrix_off_mac, k_matrix_fade_step): off
+// [O + 1], then {input, route} per route, inputs ascending per output.
+inline std::vector<int> matrix_route_table(const matrix_plan& p)
+{
+    std::vector<int> tab(size_t(p.O) + 1, 0);
+    for (int o = 0; o < p.O; ++o) {
+        for (int i = 0; i < p.I; ++i)
+            if (const int r = p.rt[size_t(o) * p.I + i]; r >= 0) tab.insert(tab.end(), {i, r});
+        tab[size_t(o) + 1] = int(tab.size() - size_t(p.O) - 1) / 2;
+    }
+    return tab;
+}
+
 // -- live filter updates (upols_matrix_fade.hip): the fade step runs one output per workgroup -------
 //
 // The splits of the fade step for a checked plan: the plain step's rule for the MAC + finish form

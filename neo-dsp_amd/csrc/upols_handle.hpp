@@ -382,15 +382,16 @@ int64_t lvf_spec_stride(int nseg, int B);
 // upols_matrix_offline.hip: the transforms of an offline pass of a matrix handle, wp windows of 128
 // blocks at write position w. fwd: the npairs = nseg + wp - 1 pairs of ring rows of every input
 // (matrix_offline_pair_row, matrix_plan.hpp) -> xf [I][npairs][256][B]. mac: per output its routes
-// (tab: off [O + 1], then {input, route} per entry, inputs ascending) x segments against hf, the
-// inverse transforms -> y [O][128 wp][B], one slab of launch_batch_finish_nosave.
+// (tab: the handle's route table, matrix_route_table in matrix_plan.hpp, uploaded once with the
+// filter) x segments against hf, the inverse transforms -> y [O][128 wp][B], one slab of
+// launch_batch_finish_nosave.
 int launch_matrix_off_fwd(const cf* fdl, cf* xf, const cf* twf, int I, int B, int ring, int npairs, int wp, int w,
                           hipStream_t s);
 int launch_matrix_off_mac(const cf* xf, const cf* hf, cf* y, const cf* twf, const int* tab, int O, int B, int nseg,
                           int wp, int64_t hcs, hipStream_t s);
 // upols_matrix_fade.hip: the fade step of a live filter update of a matrix handle. mac: both banks
 // HA, HB [nroutes][P][B] against the FDL at write position w into the slabs part [O][S][2][B] (tab:
-// off [O + 1], then {input, route} per entry, inputs ascending; grid O x S x matrix_fade_chunks).
+// the same route table as launch_matrix_off_mac's; grid O x S x matrix_fade_chunks).
 // finish: per output both banks' slabs summed in order, two c2r, out = a + g (b - a) for the samples
 // n0 .. n0 + B - 1 of a fade of `total` samples; overlap-add keeps a tail per bank (ovl_a, ovl_b
 // [O][B]). prime (overlap-add): bank B's transform alone, its second half into ovl_b, no output.

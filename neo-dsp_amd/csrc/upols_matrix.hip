@@ -11,6 +11,8 @@
 //   prev [I][B]           overlap-save: the input's previous block
 //   ovl  [O][B]           overlap-add: the output's overlap tail
 //   part [O][S][B]        per-split partial spectra; arrivals [tiles]
+//   tab                   k_matrix_step's tile table, behind it the per-output route table of the
+//                         offline MAC and the fade step (matrix_plan.hpp): one upload with the filter
 //
 // A block step is two launches:
 //   k_matrix_window  one workgroup per input: window update, packed r2c, FDL row w. Every read of
@@ -46,6 +48,11 @@
 // set_batch / set_offline say; after the last one the banks swap (pointers) and the call goes on in
 // passes as before. Overlap-add keeps a tail per bank; bank B's tail of the block before the update
 // is formed at the update call by one MAC at write position w - 1 (its rows are all intact).
+//
+// Host side: the buffers of batching, offline windows and updates are three groups of one shape
+// (matrix_group), each taken whole at its first use after a filter and freed with it; the four
+// filter calls are two loaders (matrix_load_filter, matrix_load_impulse: a bank, a stream, no wait)
+// followed by matrix_set_end (reset, complete on return) or matrix_update_end (the fade armed).
 #include "matrix_fade.hpp"
 #include "matrix_plan.hpp"
 #include "upols_handle.hpp"
@@ -72,6 +79,7 @@ struct neo_hip_matrix {
     neo_hip::cf* part = nullptr;  // [O][S][B]
     int* arrivals = nullptr;      // [tiles]
     int* tab = nullptr;           // tiles [ntiles][4] {first, count, inputs, offset into uni}, uni, rt [O][I]
+    const int* rtab = nullptr;    // behind them in tab: off [O + 1], then {input, route} per route, inputs ascending per output
     // batched passes (neo_hip_matrix_set_batch; upols_matrix_batch.hip)
     bool batch = false;
     int b_split = 0;                   // the workgroup target as given (0 auto)
@@ -88,12 +96,10 @@ struct neo_hip_matrix {
     neo_hip::cf* off_xf = nullptr;     // [I][nseg + 1][256][B] a pass's pair spectra
     neo_hip::cf* off_y = nullptr;      // [O][256][B] a pass's output spectra
     float* off_tail = nullptr;         // [O][256][B] overlap-add tails of a pass
-    int* off_tab = nullptr;            // off [O + 1], then {input, route} per route, inputs ascending per output
     // live filter updates (neo_hip_matrix_update_filter; upols_matrix_fade.hip): from the first update after a filter on
     neo_hip::cf* H2 = nullptr;     // the spare bank [nroutes][P][B]: bank B while a fade runs
     neo_hip::cf* part2 = nullptr;  // [O][fade_S][2][B] the fade step's slabs
     float* ovl2 = nullptr;         // [O][B] bank B's overlap-add tails
-    int* ftab = nullptr;           // off [O + 1], then {input, route} per route, inputs ascending per output
     int fade_S = 1;
     int fade_left = 0, fade_total = 0, fade_curve = 0;  // blocks left of the running fade (0: none)
     neo_hip::stream_set used;
@@ -333,29 +339,34 @@ int matrix_reset_state(matrix_t* m, hipStream_t s)
     return NEO_HIP_OK;
 }
 
-// the buffers of the batched passes follow the batch plan (the caller joined every stream that used them)
-void matrix_free_batch(matrix_t* m)
+template<class... T>
+void drop(T*&... p)  // dfree, and the pointers are null again
 {
-    dfree(m->part_b);
-    dfree(m->tail);
-    dfree(m->btab);
-    m->part_b = nullptr;
-    m->tail = nullptr;
-    m->btab = nullptr;
+    ((dfree(p), p = nullptr), ...);
 }
 
-// the buffers of the offline windows follow the filter (the caller joined every stream that used them)
-void matrix_free_offline(matrix_t* m)
+// The lazily allocated groups (batch, offline, fade) have one shape: matrix_*_buffers takes the whole
+// group at its first use after a filter, or through matrix_group none of it; matrix_free_* gives it
+// back (the caller joined every stream that used it).
+int matrix_group(matrix_t* m, int rc, void (*release)(matrix_t*), const char* what)
 {
-    dfree(m->off_hf);
-    dfree(m->off_xf);
-    dfree(m->off_y);
-    dfree(m->off_tail);
-    dfree(m->off_tab);
-    m->off_hf = m->off_xf = m->off_y = nullptr;
-    m->off_tail = nullptr;
-    m->off_tab = nullptr;
+    if (!rc) return NEO_HIP_OK;
+    release(m);
+    return fail(rc, "matrix %s buffers: device allocation or table copy failed", what);
+}
+
+void matrix_free_batch(matrix_t* m) { drop(m->part_b, m->tail, m->btab); }  // they follow the batch plan
+
+void matrix_free_offline(matrix_t* m)  // they follow the filter
+{
+    drop(m->off_hf, m->off_xf, m->off_y, m->off_tail);
     m->off_dirty = true;
+}
+
+void matrix_free_fade(matrix_t* m)  // they follow the route list; a running fade ends with them
+{
+    drop(m->H2, m->part2, m->ovl2);
+    m->fade_left = m->fade_total = 0;
 }
 
 int64_t matrix_offline_bytes(const matrix_t* m)
@@ -368,31 +379,13 @@ int64_t matrix_offline_bytes(const matrix_t* m)
            (m->ola ? int64_t(m->O) * spec * int64_t(sizeof(float)) : 0);
 }
 
-// the buffers of the live updates follow the route list; a running fade ends with them (the caller
-// joined every stream that used them)
-void matrix_free_fade(matrix_t* m)
-{
-    dfree(m->H2);
-    dfree(m->part2);
-    dfree(m->ovl2);
-    dfree(m->ftab);
-    m->H2 = m->part2 = nullptr;
-    m->ovl2 = nullptr;
-    m->ftab = nullptr;
-    m->fade_left = m->fade_total = 0;
-}
-
 void matrix_free_filter(matrix_t* m)
 {
     matrix_free_batch(m);
     matrix_free_offline(m);
     matrix_free_fade(m);
-    dfree(m->H);
-    dfree(m->part);
-    dfree(m->arrivals);
-    dfree(m->tab);
-    m->H = m->part = nullptr;
-    m->arrivals = m->tab = nullptr;
+    drop(m->H, m->part, m->arrivals, m->tab);
+    m->rtab = nullptr;
     m->ready = false;
 }
 
@@ -400,10 +393,18 @@ void matrix_destroy(matrix_t* m)
 {
     if (!m) return;
     matrix_free_filter(m);
-    dfree(m->fdl);
-    dfree(m->prev);
-    dfree(m->ovl);
+    drop(m->fdl, m->prev, m->ovl);
     delete m;  // the stream is one of the device's shared four (dmem.hip)
+}
+
+// a host table in device memory, complete on return: the vector may be a local
+int matrix_upload(int** out, const std::vector<int>& tab, hipStream_t s)
+{
+    if (int rc = dalloc(out, tab.size() * sizeof(int))) return rc;
+    if (hipMemcpyAsync(*out, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess)
+        return fail(NEO_HIP_ERUNTIME, "matrix convolver: table copy failed");
+    return NEO_HIP_OK;
 }
 
 // a setup call runs after every step of this handle, on whatever stream it ran
@@ -416,48 +417,63 @@ int matrix_join(matrix_t* m, bool device_input)
     return NEO_HIP_OK;
 }
 
-// the plan for a route list and the buffers that follow it; the filter rows are the caller's to fill
-int matrix_adopt(matrix_t* m, const int* route_out, const int* route_in, int nroutes)
+// a checked plan (make_matrix_plan with the handle's shape and options) and the buffers that follow
+// it, both device tables in one upload; the filter rows are the caller's to fill
+int matrix_adopt(matrix_t* m, matrix_plan&& pl)
 {
-    matrix_plan pl;
-    if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused, m->o_split,
-                                           m->o_tile, pl))
-        return fail(NEO_HIP_EINVAL, "matrix convolver: %s", why);
     matrix_free_filter(m);  // the caller joined every stream that used them
     m->plan = std::move(pl);
     // (refused only for a ring that set_batch refuses too: batching is off then)
     if (make_matrix_batch_plan(m->plan, kMatrixBatch, m->b_split, m->bplan)) m->bplan = matrix_batch_plan{};
     const matrix_plan& p = m->plan;
-    std::vector<int> tab;
-    tab.reserve(size_t(4) * p.ntiles + p.uni.size() + p.rt.size());
-    for (int t = 0; t < p.ntiles; ++t) {
-        tab.push_back(p.tile_first[size_t(t)]);
-        tab.push_back(p.tile_count[size_t(t)]);
-        tab.push_back(p.uni_off[size_t(t) + 1] - p.uni_off[size_t(t)]);
-        tab.push_back(p.uni_off[size_t(t)]);
-    }
-    tab.insert(tab.end(), p.uni.begin(), p.uni.end());
-    tab.insert(tab.end(), p.rt.begin(), p.rt.end());
+    std::vector<int> tab = matrix_tile_table(p);
+    const size_t ntile = tab.size();
+    const std::vector<int> routes = matrix_route_table(p);
+    tab.insert(tab.end(), routes.begin(), routes.end());
     const size_t rowbytes = size_t(m->B) * sizeof(cf);
-    if (dalloc(&m->H, size_t(nroutes) * m->P * rowbytes) || dalloc(&m->part, size_t(m->O) * p.S * rowbytes) ||
-        dalloc(&m->arrivals, size_t(p.ntiles) * sizeof(int)) || dalloc(&m->tab, tab.size() * sizeof(int))) {
+    int rc = dalloc(&m->H, size_t(p.nroutes) * m->P * rowbytes);
+    if (!rc) rc = dalloc(&m->part, size_t(m->O) * p.S * rowbytes);
+    if (!rc) rc = dalloc(&m->arrivals, size_t(p.ntiles) * sizeof(int));
+    if (!rc) rc = matrix_upload(&m->tab, tab, m->stream);
+    if (rc) {
         matrix_free_filter(m);
-        return fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(nroutes) * m->P * rowbytes);
+        return rc;
     }
-    NEO_HIP_CHECK(hipMemcpyAsync(m->tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    NEO_HIP_CHECK(hipStreamSynchronize(m->stream));  // tab is a local
+    m->rtab = m->tab + ntile;
     return NEO_HIP_OK;
 }
 
-int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+// the ring row d rows after the write position (d < 0: before it; |d| <= ring)
+int matrix_row(const matrix_t* m, int d) { return (m->wpos + d + m->ring) % m->ring; }  // fdl_index.hpp:28-37
+
+// the window launch of one block: every read of `in` (k_matrix_window)
+int matrix_window(matrix_t* m, const float* in, int64_t ld_in, hipStream_t s)
 {
-    const matrix_plan& p = m->plan;
 #define NEO_MATRIX_WINDOW(OL)                                                                                          \
     NEO_UPOLS_DISPATCH(m->B, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s, in, \
                                                 ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
     if (m->ola) NEO_MATRIX_WINDOW(true) else NEO_MATRIX_WINDOW(false)
 #undef NEO_MATRIX_WINDOW
     NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+// the windows of a pass of T blocks (k_batch_window: block j into row (w + j) mod R) and, for
+// overlap-save, its last block as every input's previous block: every read of `in`
+int matrix_pass_windows(matrix_t* m, const float* in, int64_t ld_in, int T, hipStream_t s)
+{
+    if (int rc = launch_batch_window(m->I, m->B, T, m->ola, in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos, s)) return rc;
+    if (!m->ola) {
+        hipLaunchKernelGGL(k_matrix_save_prev, dim3(unsigned(m->I)), dim3(256), 0, s, in, ld_in, m->prev, m->B, T);
+        NEO_HIP_LAUNCH_CHECK();
+    }
+    return NEO_HIP_OK;
+}
+
+int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    const matrix_plan& p = m->plan;
+    if (int rc = matrix_window(m, in, ld_in, s)) return rc;
     const unsigned grid = unsigned(p.ntiles) * unsigned(p.S);
 #define NEO_MATRIX_STEP(OT_, FU, OL)                                                                                   \
     hipLaunchKernelGGL((k_matrix_step<BB, OT_, FU, OL>), dim3(grid), dim3(256), 0, s, out, ld_out, m->ovl, m->H,     \
@@ -482,82 +498,53 @@ int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t
         // (overlap-add: the output's tail)
         if (int rc = launch_finish_slabs(m->O, m->B, p.S, m->ola, m->part, out, ld_out, m->ovl, m->tw, s)) return rc;
     }
-    m->wpos = m->wpos + 1 >= m->ring ? 0 : m->wpos + 1;  // fdl_index.hpp:35-37
+    m->wpos = matrix_row(m, 1);
     return NEO_HIP_OK;
 }
 
 // the slabs, the overlap-add tails and the run table, at the first batched pass after a filter or
-// a set_batch (both joined the streams that used the old ones)
+// a set_batch
 int matrix_batch_buffers(matrix_t* m, hipStream_t s)
 {
     if (m->part_b) return NEO_HIP_OK;
     const matrix_batch_plan& bp = m->bplan;
-    const size_t ntab = bp.run_off.size() + bp.runs.size();
-    if (dalloc(&m->part_b, size_t(m->O) * bp.Sb * kMatrixBatch * m->B * sizeof(cf)) ||
-        (m->ola && dalloc(&m->tail, size_t(m->O) * kMatrixBatch * m->B * sizeof(float))) ||
-        dalloc(&m->btab, ntab * sizeof(int))) {
-        matrix_free_batch(m);
-        return fail(NEO_HIP_ENOMEM, "matrix batch buffers: device allocation failed");
-    }
     std::vector<int> tab(bp.run_off);
     tab.insert(tab.end(), bp.runs.begin(), bp.runs.end());
-    if (hipMemcpyAsync(m->btab, tab.data(), ntab * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
-        matrix_free_batch(m);
-        return fail(NEO_HIP_ERUNTIME, "matrix batch buffers: table copy failed");
-    }
-    return NEO_HIP_OK;
+    int rc = dalloc(&m->part_b, size_t(m->O) * bp.Sb * kMatrixBatch * m->B * sizeof(cf));
+    if (!rc && m->ola) rc = dalloc(&m->tail, size_t(m->O) * kMatrixBatch * m->B * sizeof(float));
+    if (!rc) rc = matrix_upload(&m->btab, tab, s);
+    return matrix_group(m, rc, matrix_free_batch, "batch");
 }
 
 // T = 2 .. 32 blocks in one pass over every route's filter (the ring has P + 31 rows: set_batch)
 int matrix_batch(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s)
 {
     if (int rc = matrix_batch_buffers(m, s)) return rc;
-    if (int rc = launch_batch_window(m->I, m->B, T, m->ola, in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos, s)) return rc;
-    if (!m->ola) {
-        hipLaunchKernelGGL(k_matrix_save_prev, dim3(unsigned(m->I)), dim3(256), 0, s, in, ld_in, m->prev, m->B, T);
-        NEO_HIP_LAUNCH_CHECK();
-    }
+    if (int rc = matrix_pass_windows(m, in, ld_in, T, s)) return rc;
     if (int rc = launch_matrix_batch_mac(m->H, m->fdl, m->part_b, m->btab, m->B, m->P, m->ring, m->O, m->bplan.Sb, T,
                                          m->wpos, s))
         return rc;
     if (int rc = launch_batch_finish_nosave(m->O, m->B, m->bplan.Sb, T, m->ola, m->part_b, out, ld_out, m->tail, m->ovl,
                                             m->tw, s))
         return rc;
-    m->wpos = (m->wpos + T) % m->ring;
+    m->wpos = matrix_row(m, T);
     return NEO_HIP_OK;
 }
 
-// the spectra, the overlap-add tails and the route table of the offline windows, at the first
-// offline pass after a filter (which joined the streams that used the old ones); a failure frees
-// what was taken and leaves batched passes and single steps as they were
-int matrix_offline_buffers(matrix_t* m, hipStream_t s)
+// the spectra and the overlap-add tails of the offline windows, at the first offline pass after a
+// filter; a failure leaves batched passes and single steps as they were
+int matrix_offline_buffers(matrix_t* m)
 {
     if (m->off_hf) return NEO_HIP_OK;
     if (!m->off_tw)
         if (int rc = shared_far_tw(&m->off_tw)) return rc;
-    const int nseg = matrix_offline_segments(m->P), I = m->I, O = m->O;
+    const int nseg = matrix_offline_segments(m->P);
     const size_t spec = size_t(2 * kMatrixOffWindow) * m->B;
-    std::vector<int> tab(size_t(O) + 1, 0);
-    for (int o = 0; o < O; ++o) {
-        for (int i = 0; i < I; ++i)
-            if (const int r = m->plan.rt[size_t(o) * I + i]; r >= 0) tab.insert(tab.end(), {i, r});
-        tab[size_t(o) + 1] = int(tab.size() - size_t(O) - 1) / 2;
-    }
-    if (dalloc(&m->off_hf, size_t(m->plan.nroutes) * size_t(lvf_spec_stride(nseg, m->B)) * sizeof(cf)) ||
-        dalloc(&m->off_xf, size_t(I) * (nseg + kMatrixOffMaxWP - 1) * spec * sizeof(cf)) ||
-        dalloc(&m->off_y, size_t(O) * spec * sizeof(cf)) ||
-        (m->ola && dalloc(&m->off_tail, size_t(O) * spec * sizeof(float))) || dalloc(&m->off_tab, tab.size() * sizeof(int))) {
-        matrix_free_offline(m);
-        return fail(NEO_HIP_ENOMEM, "matrix offline buffers: device allocation failed");
-    }
-    if (hipMemcpyAsync(m->off_tab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
-        matrix_free_offline(m);
-        return fail(NEO_HIP_ERUNTIME, "matrix offline buffers: table copy failed");
-    }
-    m->off_dirty = true;
-    return NEO_HIP_OK;
+    int rc = dalloc(&m->off_hf, size_t(m->plan.nroutes) * size_t(lvf_spec_stride(nseg, m->B)) * sizeof(cf));
+    if (!rc) rc = dalloc(&m->off_xf, size_t(m->I) * (nseg + kMatrixOffMaxWP - 1) * spec * sizeof(cf));
+    if (!rc) rc = dalloc(&m->off_y, size_t(m->O) * spec * sizeof(cf));
+    if (!rc && m->ola) rc = dalloc(&m->off_tail, size_t(m->O) * spec * sizeof(float));
+    return matrix_group(m, rc, matrix_free_offline, "offline");  // (off_dirty is set: matrix_free_offline)
 }
 
 // wp windows of 128 blocks in one pass (the ring has 128 (nseg + 2) + 1 rows or more: set_offline, so
@@ -565,15 +552,11 @@ int matrix_offline_buffers(matrix_t* m, hipStream_t s)
 // every write of `out` in the last two
 int matrix_offline(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int wp, hipStream_t s)
 {
-    if (int rc = matrix_offline_buffers(m, s)) return rc;
+    if (int rc = matrix_offline_buffers(m)) return rc;
     matrix_offline_plan op;
     if (const char* why = make_matrix_offline_plan(m->I, m->O, m->B, m->P, m->plan.nroutes, wp, m->wpos, m->ring, op))
         return fail(NEO_HIP_EINVAL, "matrix offline pass: %s", why);
-    if (int rc = launch_batch_window(m->I, m->B, op.T, m->ola, in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos, s)) return rc;
-    if (!m->ola) {
-        hipLaunchKernelGGL(k_matrix_save_prev, dim3(unsigned(m->I)), dim3(256), 0, s, in, ld_in, m->prev, m->B, op.T);
-        NEO_HIP_LAUNCH_CHECK();
-    }
+    if (int rc = matrix_pass_windows(m, in, ld_in, op.T, s)) return rc;
     if (m->off_dirty) {  // the routes stand in for channels: stride P B, one partition per row
         if (int rc = launch_lvf_filter(m->H, m->off_hf, m->off_tw, m->plan.nroutes, m->B, m->P, op.nseg,
                                        int64_t(m->P) * m->B, m->B, 0, s))
@@ -582,40 +565,26 @@ int matrix_offline(matrix_t* m, const float* in, int64_t ld_in, float* out, int6
     }
     // (pair k's rows: matrix_offline_pair_row, the function op.pair_row was filled from)
     if (int rc = launch_matrix_off_fwd(m->fdl, m->off_xf, m->off_tw, m->I, m->B, op.ring, op.npairs, op.WP, m->wpos, s)) return rc;
-    if (int rc = launch_matrix_off_mac(m->off_xf, m->off_hf, m->off_y, m->off_tw, m->off_tab, m->O, m->B, op.nseg, op.WP,
+    if (int rc = launch_matrix_off_mac(m->off_xf, m->off_hf, m->off_y, m->off_tw, m->rtab, m->O, m->B, op.nseg, op.WP,
                                        lvf_spec_stride(op.nseg, m->B), s))
         return rc;
     if (int rc = launch_batch_finish_nosave(m->O, m->B, 1, op.T, m->ola, m->off_y, out, ld_out, m->off_tail, m->ovl, m->tw, s))
         return rc;
-    m->wpos = (m->wpos + op.T) % m->ring;
+    m->wpos = matrix_row(m, op.T);
     return NEO_HIP_OK;
 }
 
-// the spare bank, the fade step's slabs and table and bank B's overlap-add tails, at the first update
-// after a filter; a failure frees what was taken and leaves the handle as it was
-int matrix_fade_buffers(matrix_t* m, hipStream_t s)
+// the spare bank, the fade step's slabs and bank B's overlap-add tails, at the first update after a
+// filter (no host-side wait); a failure leaves the handle as it was
+int matrix_fade_buffers(matrix_t* m)
 {
     if (m->H2) return NEO_HIP_OK;
-    const int I = m->I, O = m->O;
-    std::vector<int> tab(size_t(O) + 1, 0);
-    for (int o = 0; o < O; ++o) {
-        for (int i = 0; i < I; ++i)
-            if (const int r = m->plan.rt[size_t(o) * I + i]; r >= 0) tab.insert(tab.end(), {i, r});
-        tab[size_t(o) + 1] = int(tab.size() - size_t(O) - 1) / 2;
-    }
     m->fade_S = matrix_fade_splits(m->plan, m->o_split, matrix_fade_chunks(m->B));
     const size_t rowbytes = size_t(m->B) * sizeof(cf);
-    if (dalloc(&m->H2, size_t(m->plan.nroutes) * m->P * rowbytes) || dalloc(&m->part2, size_t(O) * m->fade_S * 2 * rowbytes) ||
-        (m->ola && dalloc(&m->ovl2, size_t(O) * m->B * sizeof(float))) || dalloc(&m->ftab, tab.size() * sizeof(int))) {
-        matrix_free_fade(m);
-        return fail(NEO_HIP_ENOMEM, "matrix update: device allocation of the second filter bank failed");
-    }
-    if (hipMemcpyAsync(m->ftab, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {  // tab is a local
-        matrix_free_fade(m);
-        return fail(NEO_HIP_ERUNTIME, "matrix update: table copy failed");
-    }
-    return NEO_HIP_OK;
+    int rc = dalloc(&m->H2, size_t(m->plan.nroutes) * m->P * rowbytes);
+    if (!rc) rc = dalloc(&m->part2, size_t(m->O) * m->fade_S * 2 * rowbytes);
+    if (!rc && m->ola) rc = dalloc(&m->ovl2, size_t(m->O) * m->B * sizeof(float));
+    return matrix_group(m, rc, matrix_free_fade, "update");
 }
 
 // what every update checks before it touches anything
@@ -635,8 +604,8 @@ int matrix_update_check(const matrix_t* m, int fade_blocks, int curve)
 int matrix_fade_arm(matrix_t* m, int fade_blocks, int curve, hipStream_t s)
 {
     if (m->ola) {
-        const int w1 = m->wpos ? m->wpos - 1 : m->ring - 1;
-        if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->ftab, m->B, m->P, m->ring, m->O, m->fade_S, w1, s))
+        if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->rtab, m->B, m->P, m->ring, m->O, m->fade_S,
+                                            matrix_row(m, -1), s))
             return rc;
         if (int rc = launch_matrix_fade_finish(m->part2, nullptr, 0, m->ovl, m->ovl2, m->tw, m->B, m->O, m->fade_S, true, true,
                                                0, 1, 0, s))
@@ -659,19 +628,14 @@ void matrix_fade_swap(matrix_t* m)
 // one block of a running fade: the window launch as ever, then both banks against the same FDL rows
 int matrix_fade_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
-#define NEO_MATRIX_WINDOW(OL)                                                                                          \
-    NEO_UPOLS_DISPATCH(m->B, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s, in, \
-                                                ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
-    if (m->ola) NEO_MATRIX_WINDOW(true) else NEO_MATRIX_WINDOW(false)
-#undef NEO_MATRIX_WINDOW
-    NEO_HIP_LAUNCH_CHECK();
-    if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->ftab, m->B, m->P, m->ring, m->O, m->fade_S, m->wpos, s))
+    if (int rc = matrix_window(m, in, ld_in, s)) return rc;
+    if (int rc = launch_matrix_fade_mac(m->H, m->H2, m->fdl, m->part2, m->rtab, m->B, m->P, m->ring, m->O, m->fade_S, m->wpos, s))
         return rc;
     const int64_t n0 = int64_t(m->fade_total - m->fade_left) * m->B;
     if (int rc = launch_matrix_fade_finish(m->part2, out, ld_out, m->ovl, m->ovl2, m->tw, m->B, m->O, m->fade_S, m->ola, false,
                                            n0, int64_t(m->fade_total) * m->B, m->fade_curve, s))
         return rc;
-    m->wpos = m->wpos + 1 >= m->ring ? 0 : m->wpos + 1;
+    m->wpos = matrix_row(m, 1);
     if (--m->fade_left == 0) matrix_fade_swap(m);
     return NEO_HIP_OK;
 }
@@ -735,6 +699,100 @@ int matrix_grow_ring(matrix_t* m, int rows)
     return NEO_HIP_OK;
 }
 
+// -- the filter calls: set_* = check, join, adopt, load into H on the handle's stream, matrix_set_end;
+// update_* = check, the fade's buffers, load into H2 on the call's stream, matrix_update_end ---------
+
+neo_hip_matrix_opts matrix_opts(const neo_hip_matrix_opts* opts) { return opts ? *opts : neo_hip_matrix_opts{-1, 0, 0}; }
+
+// device memory: the caller's stream; host memory: the handle's own unless one is given
+hipStream_t matrix_stream(const matrix_t* m, int is_device, void* stream)
+{
+    return is_device || stream ? as_stream(stream) : m->stream;
+}
+
+// a set call's route list against the handle's shape and options
+const char* matrix_check_routes(const matrix_t* m, const int* route_out, const int* route_in, int nroutes, matrix_plan& p)
+{
+    return make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused, m->o_split, m->o_tile, p);
+}
+
+int matrix_check_impulse(const matrix_t* m, const float* ir, int64_t length)
+{
+    if (!m || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
+    if (partitions_for(length, m->B) != m->P)
+        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
+                    (long long)partitions_for(length, m->B), m->P);
+    return NEO_HIP_OK;
+}
+
+// scratch of the loaders: stream-ordered (hipFreeAsync on the same stream), so a load never waits
+template<class T>
+int matrix_scratch(T** out, size_t bytes, hipStream_t s)
+{
+    if (hipMallocAsync(reinterpret_cast<void**>(out), bytes, s) == hipSuccess) return NEO_HIP_OK;
+    (void)hipGetLastError();
+    return fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", bytes);
+}
+
+// The caller's filter [nroutes][P][B + 1] (reference layout), in host or device memory, packed into
+// `bank` [nroutes][P][B] on s. No host-side wait; host memory is staged, the caller synchronises s.
+int matrix_load_filter(matrix_t* m, const void* filter, bool is_device, cf* bank, hipStream_t s)
+{
+    const int64_t rows = int64_t(m->plan.nroutes) * m->P;
+    const size_t bytes = size_t(rows) * size_t(m->B + 1) * sizeof(cf);
+    const cf* src = static_cast<const cf*>(filter);
+    cf* tmp = nullptr;
+    int rc = NEO_HIP_OK;
+    if (!is_device) {
+        if ((rc = matrix_scratch(&tmp, bytes, s))) return rc;
+        if (hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
+        src = tmp;
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_matrix_pack, dim3(unsigned((rows * m->B + 255) / 256)), dim3(256), 0, s, src, bank, m->B, rows);
+        if (hipGetLastError() != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "pack launch failed");
+    }
+    if (tmp && hipFreeAsync(tmp, s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "filter scratch free failed");
+    return rc;
+}
+
+// The same from impulse responses [nroutes][length]: one normalisation factor over all routes' rows,
+// as the dense setup takes it over channels (normalize_impulse.hpp:21-30), then uniform_partition.
+int matrix_load_impulse(matrix_t* m, const float* ir, int64_t length, bool normalize, bool is_device, cf* bank,
+                        hipStream_t s)
+{
+    const int nroutes = m->plan.nroutes;
+    const size_t bytes = size_t(nroutes) * size_t(length) * sizeof(float);
+    float* d = nullptr;
+    if (int rc = matrix_scratch(&d, bytes, s)) return rc;
+    int rc = NEO_HIP_OK;
+    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
+    if (!rc && normalize) rc = normalize_device(d, nroutes, length, s);
+    if (!rc) rc = partition_device(d, nroutes, length, m->B, true, bank, m->tw, s, int64_t(m->P) * m->B, m->B);
+    if (hipFreeAsync(d, s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "impulse scratch free failed");
+    return rc;
+}
+
+// a set call after its load (rc): all state reset, complete on return
+int matrix_set_end(matrix_t* m, int rc)
+{
+    if (!rc) rc = matrix_reset_state(m, m->stream);
+    if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    m->ready = !rc;
+    return rc;
+}
+
+// an update call after its load (rc): the fade armed; host memory: complete on return
+int matrix_update_end(matrix_t* m, int rc, bool is_device, int fade_blocks, int curve, hipStream_t s)
+{
+    if (!rc) rc = matrix_fade_arm(m, fade_blocks, curve, s);
+    if (!is_device && hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    if (rc) m->fade_left = m->fade_total = 0;
+    return rc;
+}
+
 }  // namespace
 }  // namespace neo_hip
 
@@ -747,7 +805,7 @@ NEO_HIP_API int neo_hip_matrix_plan(int inputs, int outputs, int block, int part
                                     neo_hip_matrix_plan_info* plan, int* tile_first, int* tile_count, int* tile_rows,
                                     int* union_off, int* union_in, int* cuts)
 {
-    const neo_hip_matrix_opts o = opts ? *opts : neo_hip_matrix_opts{-1, 0, 0};
+    const neo_hip_matrix_opts o = matrix_opts(opts);
     matrix_plan p;
     if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, route_out, route_in, nroutes, o.fused,
                                            o.split_workgroups, o.out_tile, p))
@@ -780,7 +838,7 @@ NEO_HIP_API int neo_hip_matrix_create(int inputs, int outputs, int block, int pa
     *out = nullptr;
     if (method < 0 || method > 1)
         return fail(NEO_HIP_EINVAL, "matrix convolvers: method must be 0 (upols) or 1 (upola); whole blocks only");
-    const neo_hip_matrix_opts o = opts ? *opts : neo_hip_matrix_opts{-1, 0, 0};
+    const neo_hip_matrix_opts o = matrix_opts(opts);
     {  // the shape and the options, before a device is touched (a one-route list stands in)
         const int zero = 0;
         matrix_plan p;
@@ -825,70 +883,28 @@ NEO_HIP_API int neo_hip_matrix_set_filter(neo_hip_matrix* m, const void* filter,
                                           const int* route_in, int nroutes, int is_device)
 {
     if (!m || !filter) return fail(NEO_HIP_EINVAL, "null handle or filter");
-    {  // a refused route list leaves the handle as it was
-        matrix_plan p;
-        if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused,
-                                               m->o_split, m->o_tile, p))
-            return fail(NEO_HIP_EINVAL, "matrix set_filter: %s", why);
-    }
+    matrix_plan p;  // a refused route list leaves the handle as it was
+    if (const char* why = matrix_check_routes(m, route_out, route_in, nroutes, p))
+        return fail(NEO_HIP_EINVAL, "matrix set_filter: %s", why);
     device_guard g(m->device);
     if (g.rc) return g.rc;
     if (int rc = matrix_join(m, is_device != 0)) return rc;
-    if (int rc = matrix_adopt(m, route_out, route_in, nroutes)) return rc;
-    const int64_t rows = int64_t(nroutes) * m->P;
-    const size_t bytes = size_t(rows) * size_t(m->B + 1) * sizeof(cf);
-    const cf* src = static_cast<const cf*>(filter);
-    cf* tmp = nullptr;
-    int rc = NEO_HIP_OK;
-    if (!is_device) {
-        if ((rc = dalloc(&tmp, bytes))) return rc;
-        if (hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, m->stream) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmp;
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(k_matrix_pack, dim3(unsigned((rows * m->B + 255) / 256)), dim3(256), 0, m->stream, src, m->H,
-                           m->B, rows);
-        if (hipGetLastError() != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "pack launch failed");
-    }
-    if (!rc) rc = matrix_reset_state(m, m->stream);
-    if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(tmp);  // the stream was joined above
-    m->ready = !rc;
-    return rc;
+    if (int rc = matrix_adopt(m, std::move(p))) return rc;
+    return matrix_set_end(m, matrix_load_filter(m, filter, is_device != 0, m->H, m->stream));
 }
 
 NEO_HIP_API int neo_hip_matrix_set_impulse(neo_hip_matrix* m, const float* ir, int64_t length, const int* route_out,
                                            const int* route_in, int nroutes, int normalize, int is_device)
 {
-    if (!m || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
-    if (partitions_for(length, m->B) != m->P)
-        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
-                    (long long)partitions_for(length, m->B), m->P);
-    {
-        matrix_plan p;
-        if (const char* why = make_matrix_plan(m->I, m->O, m->B, m->P, route_out, route_in, nroutes, m->o_fused,
-                                               m->o_split, m->o_tile, p))
-            return fail(NEO_HIP_EINVAL, "matrix set_impulse: %s", why);
-    }
+    if (int rc = matrix_check_impulse(m, ir, length)) return rc;
+    matrix_plan p;
+    if (const char* why = matrix_check_routes(m, route_out, route_in, nroutes, p))
+        return fail(NEO_HIP_EINVAL, "matrix set_impulse: %s", why);
     device_guard g(m->device);
     if (g.rc) return g.rc;
     if (int rc = matrix_join(m, is_device != 0)) return rc;
-    if (int rc = matrix_adopt(m, route_out, route_in, nroutes)) return rc;
-    const size_t bytes = size_t(nroutes) * size_t(length) * sizeof(float);
-    float* d = nullptr;
-    if (int rc = dalloc(&d, bytes)) return rc;
-    int rc = NEO_HIP_OK;
-    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, m->stream) != hipSuccess)
-        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
-    // one factor over all routes' rows, as the dense setup takes it over channels (normalize_impulse.hpp:21-30)
-    if (!rc && normalize) rc = normalize_device(d, nroutes, length, m->stream);
-    if (!rc) rc = partition_device(d, nroutes, length, m->B, true, m->H, m->tw, m->stream, int64_t(m->P) * m->B, m->B);
-    if (!rc) rc = matrix_reset_state(m, m->stream);
-    if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(d);
-    m->ready = !rc;
-    return rc;
+    if (int rc = matrix_adopt(m, std::move(p))) return rc;
+    return matrix_set_end(m, matrix_load_impulse(m, ir, length, normalize != 0, is_device != 0, m->H, m->stream));
 }
 
 NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64_t ld_in, float* out, int64_t ld_out,
@@ -904,7 +920,7 @@ NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64
     if (!nblocks) return NEO_HIP_OK;
     device_guard g(m->device);
     if (g.rc) return g.rc;
-    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;  // host I/O: own stream unless given
+    hipStream_t s = matrix_stream(m, is_device, stream);
     if (int rc = m->used.note(s)) return rc;
     if (is_device) return matrix_blocks(m, in, ld_in, out, ld_out, nblocks, s);
     // host memory: staged ([I][n] in, [O][n] out), synchronous
@@ -947,61 +963,24 @@ NEO_HIP_API int neo_hip_matrix_update_filter(neo_hip_matrix* m, const void* filt
     if (int rc = matrix_update_check(m, fade_blocks, curve)) return rc;
     device_guard g(m->device);
     if (g.rc) return g.rc;
-    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;
+    hipStream_t s = matrix_stream(m, is_device, stream);
     if (int rc = m->used.note(s)) return rc;
-    if (int rc = matrix_fade_buffers(m, s)) return rc;
-    const int64_t rows = int64_t(m->plan.nroutes) * m->P;
-    const size_t bytes = size_t(rows) * size_t(m->B + 1) * sizeof(cf);
-    const cf* src = static_cast<const cf*>(filter);
-    cf* tmp = nullptr;
-    int rc = NEO_HIP_OK;
-    if (!is_device) {
-        if ((rc = dalloc(&tmp, bytes))) return rc;
-        if (hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmp;
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(k_matrix_pack, dim3(unsigned((rows * m->B + 255) / 256)), dim3(256), 0, s, src, m->H2, m->B, rows);
-        if (hipGetLastError() != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "pack launch failed");
-    }
-    if (!rc) rc = matrix_fade_arm(m, fade_blocks, curve, s);
-    if (!is_device) {  // staged: returns when the bank is written
-        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-        dfree(tmp);
-    }
-    if (rc) m->fade_left = m->fade_total = 0;
-    return rc;
+    if (int rc = matrix_fade_buffers(m)) return rc;
+    return matrix_update_end(m, matrix_load_filter(m, filter, is_device != 0, m->H2, s), is_device != 0, fade_blocks, curve, s);
 }
 
 NEO_HIP_API int neo_hip_matrix_update_impulse(neo_hip_matrix* m, const float* ir, int64_t length, int normalize,
                                               int is_device, int fade_blocks, int curve, void* stream)
 {
-    if (!m || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
-    if (partitions_for(length, m->B) != m->P)
-        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
-                    (long long)partitions_for(length, m->B), m->P);
+    if (int rc = matrix_check_impulse(m, ir, length)) return rc;
     if (int rc = matrix_update_check(m, fade_blocks, curve)) return rc;
     device_guard g(m->device);
     if (g.rc) return g.rc;
-    hipStream_t s = is_device || stream ? as_stream(stream) : m->stream;
+    hipStream_t s = matrix_stream(m, is_device, stream);
     if (int rc = m->used.note(s)) return rc;
-    if (int rc = matrix_fade_buffers(m, s)) return rc;
-    const int nroutes = m->plan.nroutes;
-    const size_t bytes = size_t(nroutes) * size_t(length) * sizeof(float);
-    float* d = nullptr;  // stream-ordered: a device impulse leaves the call asynchronous
-    NEO_HIP_CHECK(hipMallocAsync(reinterpret_cast<void**>(&d), bytes, s));
-    int rc = NEO_HIP_OK;
-    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
-        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
-    if (!rc && normalize) rc = normalize_device(d, nroutes, length, s);
-    if (!rc) rc = partition_device(d, nroutes, length, m->B, true, m->H2, m->tw, s, int64_t(m->P) * m->B, m->B);
-    if (hipFreeAsync(d, s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "impulse scratch free failed");
-    if (!rc) rc = matrix_fade_arm(m, fade_blocks, curve, s);
-    if (!is_device)
-        if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    if (rc) m->fade_left = m->fade_total = 0;
-    return rc;
+    if (int rc = matrix_fade_buffers(m)) return rc;
+    return matrix_update_end(m, matrix_load_impulse(m, ir, length, normalize != 0, is_device != 0, m->H2, s), is_device != 0,
+                             fade_blocks, curve, s);
 }
 
 NEO_HIP_API int neo_hip_matrix_fade_info(neo_hip_matrix* m, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes)

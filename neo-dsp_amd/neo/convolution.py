@@ -1456,6 +1456,37 @@ def matrix_fade_gains(block: int, fade_blocks: int, curve="linear") -> np.ndarra
     return g
 
 
+def _matrix_arg(x, np_dtype, count, bad_tensor: str, bad_array: str):
+    """A filter or impulse argument of MatrixConvolver -> (array or tensor, which the caller keeps
+    alive over the call; its pointer; is_device; torch's current stream or 0). A CUDA tensor must be
+    contiguous, of the dtype and hold count(x) elements, and is complete first (_producer_join);
+    anything else becomes a contiguous host array of the dtype."""
+    if _is_torch(x) and x.is_cuda:
+        import torch
+
+        if x.dtype != getattr(torch, np.dtype(np_dtype).name) or not x.is_contiguous() or x.numel() != count(x):
+            raise ValueError(bad_tensor)
+        _producer_join(x)
+        return x, ctypes.c_void_p(x.data_ptr()), 1, torch.cuda.current_stream(x.device).cuda_stream
+    a = np.ascontiguousarray(x, dtype=np_dtype)
+    if a.size != count(a):
+        raise ValueError(bad_array.format(a.shape))
+    return a, _ptr(a), 0, 0
+
+
+def _matrix_filter_arg(partitions, shape):
+    return _matrix_arg(partitions, np.complex64, lambda _: int(np.prod(shape)),
+                       f"filter must be a contiguous complex64 tensor of {shape} elements",
+                       f"filter of {{}} does not hold {shape}")
+
+
+def _matrix_impulse_arg(ir, nroutes: int):
+    """(the rows' length is the last dimension of what comes back)"""
+    return _matrix_arg(ir, np.float32, lambda a: nroutes * a.shape[-1],
+                       "impulse must be a contiguous float32 tensor of one row per route",
+                       "impulse must hold one row per route")
+
+
 class MatrixConvolver:
     """I inputs routed to O outputs: output o = the sum over its routes (o, i) of the UPOLS (or
     UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
@@ -1484,44 +1515,16 @@ class MatrixConvolver:
         """routes None: dense partitions [O][I][P][B+1]; else [nroutes][P][B+1] with routes a list
         of (out, in). complex64 host array or CUDA tensor. Resets all state."""
         ro, ri = _routes(routes, self.inputs, self.outputs)
-        shape = (len(ro), self.partitions, self.block_size + 1)
-        lib = _native.load()
-        if _is_torch(partitions) and partitions.is_cuda:
-            import torch
-
-            t = partitions
-            if t.dtype != torch.complex64 or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-                raise ValueError(f"filter must be a contiguous complex64 tensor of {shape} elements")
-            _producer_join(t)
-            _native.check(lib.neo_hip_matrix_set_filter(self._h, ctypes.c_void_p(t.data_ptr()), _ptr(ro), _ptr(ri),
-                                                        len(ro), 1))
-            return
-        H = np.ascontiguousarray(partitions, dtype=np.complex64)
-        if H.size != int(np.prod(shape)):
-            raise ValueError(f"filter of {H.shape} does not hold {shape}")
-        _native.check(lib.neo_hip_matrix_set_filter(self._h, _ptr(H), _ptr(ro), _ptr(ri), len(ro), 0))
+        H, p, dev, _ = _matrix_filter_arg(partitions, (len(ro), self.partitions, self.block_size + 1))
+        _native.check(_native.load().neo_hip_matrix_set_filter(self._h, p, _ptr(ro), _ptr(ri), len(ro), dev))
 
     def set_impulse(self, ir, routes=None, normalize: bool = True) -> None:
         """ir [O][I][L] (routes None) or [nroutes][L] float32: normalize_impulse over all routes'
         rows (optional), then uniform_partition on the device."""
         ro, ri = _routes(routes, self.inputs, self.outputs)
-        lib = _native.load()
-        if _is_torch(ir) and ir.is_cuda:
-            import torch
-
-            t = ir
-            L = t.shape[-1]
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != len(ro) * L:
-                raise ValueError("impulse must be a contiguous float32 tensor of one row per route")
-            _producer_join(t)
-            _native.check(lib.neo_hip_matrix_set_impulse(self._h, ctypes.c_void_p(t.data_ptr()), L, _ptr(ro), _ptr(ri),
-                                                         len(ro), int(normalize), 1))
-            return
-        a = np.ascontiguousarray(ir, dtype=np.float32)
-        L = a.shape[-1]
-        if a.size != len(ro) * L:
-            raise ValueError("impulse must hold one row per route")
-        _native.check(lib.neo_hip_matrix_set_impulse(self._h, _ptr(a), L, _ptr(ro), _ptr(ri), len(ro), int(normalize), 0))
+        a, p, dev, _ = _matrix_impulse_arg(ir, len(ro))
+        _native.check(_native.load().neo_hip_matrix_set_impulse(self._h, p, a.shape[-1], _ptr(ro), _ptr(ri), len(ro),
+                                                                int(normalize), dev))
 
     def reset(self) -> None:
         """Clears all state; a running fade (update_filter) completes: the new filter is the filter."""
@@ -1543,22 +1546,9 @@ class MatrixConvolver:
         lib = _native.load()
         if not shape[0]:  # no filter set: the library's refusal
             _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(np.zeros(1, np.complex64)), 0, int(fade_blocks), c, None))
-        if _is_torch(partitions) and partitions.is_cuda:
-            import torch
-
-            t = partitions
-            if t.dtype != torch.complex64 or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-                raise ValueError(f"filter must be a contiguous complex64 tensor of {shape} elements")
-            _producer_join(t)
-            s = stream or torch.cuda.current_stream(t.device).cuda_stream
-            _native.check(lib.neo_hip_matrix_update_filter(self._h, ctypes.c_void_p(t.data_ptr()), 1, int(fade_blocks), c,
-                                                           ctypes.c_void_p(s)))
-            return
-        H = np.ascontiguousarray(partitions, dtype=np.complex64)
-        if H.size != int(np.prod(shape)):
-            raise ValueError(f"filter of {H.shape} does not hold {shape}")
-        _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(H), 0, int(fade_blocks), c,
-                                                       ctypes.c_void_p(stream) if stream else None))
+        H, p, dev, current = _matrix_filter_arg(partitions, shape)
+        _native.check(lib.neo_hip_matrix_update_filter(self._h, p, dev, int(fade_blocks), c,
+                                                       ctypes.c_void_p(stream or current or None)))
 
     def update_impulse(self, ir, normalize: bool = True, fade_blocks: int = 1, curve: str = "linear",
                        stream: int = 0) -> None:
@@ -1570,24 +1560,9 @@ class MatrixConvolver:
         lib = _native.load()
         if not nroutes:  # no filter set: the library's refusal
             _native.check(lib.neo_hip_matrix_update_filter(self._h, _ptr(np.zeros(1, np.complex64)), 0, int(fade_blocks), c, None))
-        if _is_torch(ir) and ir.is_cuda:
-            import torch
-
-            t = ir
-            L = t.shape[-1]
-            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != nroutes * L:
-                raise ValueError("impulse must be a contiguous float32 tensor of one row per route")
-            _producer_join(t)
-            s = stream or torch.cuda.current_stream(t.device).cuda_stream
-            _native.check(lib.neo_hip_matrix_update_impulse(self._h, ctypes.c_void_p(t.data_ptr()), L, int(normalize), 1,
-                                                            int(fade_blocks), c, ctypes.c_void_p(s)))
-            return
-        a = np.ascontiguousarray(ir, dtype=np.float32)
-        L = a.shape[-1]
-        if a.size != nroutes * L:
-            raise ValueError("impulse must hold one row per route")
-        _native.check(lib.neo_hip_matrix_update_impulse(self._h, _ptr(a), L, int(normalize), 0, int(fade_blocks), c,
-                                                        ctypes.c_void_p(stream) if stream else None))
+        a, p, dev, current = _matrix_impulse_arg(ir, nroutes)
+        _native.check(lib.neo_hip_matrix_update_impulse(self._h, p, a.shape[-1], int(normalize), dev, int(fade_blocks), c,
+                                                        ctypes.c_void_p(stream or current or None)))
 
     def fade_info(self) -> dict:
         """remaining_blocks of the running fade (0: none), its fade_blocks (0: none) and bank_bytes,

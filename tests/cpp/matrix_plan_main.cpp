@@ -2,7 +2,8 @@
 // undefined-behaviour sanitizers: random route lists through make_matrix_plan, checked against a
 // plain restatement, and the row walk of k_matrix_step (upols_matrix.hip) replayed on the host for
 // every (tile, split): every (route, partition) is met exactly once, every index stays in range,
-// and the loads add up to the plan's totals.
+// and the loads add up to the plan's totals. The two device tables the handle uploads
+// (matrix_tile_table, matrix_route_table) are checked against the plan and the caller's list.
 #include "../../neo-dsp_amd/csrc/matrix_plan.hpp"
 
 #include <cstdio>
@@ -96,6 +97,34 @@ static bool one_case(std::mt19937& rng, int n)
     }
     CHECK(fdl == p.fdl_loads && filt == p.filter_loads && int64_t(met.size()) == int64_t(R) * P);
     (void)nonempty_longest;
+
+    // the device tables. The tile table, read as k_matrix_step reads it, reproduces the plan
+    const std::vector<int> tt = neo_hip::matrix_tile_table(p);
+    CHECK(tt.size() == size_t(4) * p.ntiles + p.uni.size() + p.rt.size());
+    for (int t = 0; t < p.ntiles; ++t) {
+        const int nuni = tt[size_t(4) * t + 2];
+        CHECK(tt[size_t(4) * t] == p.tile_first[size_t(t)] && tt[size_t(4) * t + 1] == p.tile_count[size_t(t)]);
+        CHECK(nuni == p.uni_off[size_t(t) + 1] - p.uni_off[size_t(t)] && tt[size_t(4) * t + 3] == p.uni_off[size_t(t)]);
+        for (int k = 0; k < nuni; ++k)
+            CHECK(tt[size_t(4) * p.ntiles + tt[size_t(4) * t + 3] + k] == p.uni[size_t(p.uni_off[size_t(t)]) + k]);
+    }
+    const size_t rt0 = size_t(4) * p.ntiles + tt[size_t(4) * (p.ntiles - 1) + 3] + tt[size_t(4) * (p.ntiles - 1) + 2];
+    CHECK(rt0 + p.rt.size() == tt.size());
+    for (size_t k = 0; k < p.rt.size(); ++k) CHECK(tt[rt0 + k] == p.rt[k]);
+    // the route table: per output exactly its routes (each route of the caller's list once, under
+    // its own output, with its own input and index), inputs strictly ascending, offsets up to R
+    const std::vector<int> rtab = neo_hip::matrix_route_table(p);
+    CHECK(rtab.size() == size_t(O) + 1 + size_t(2) * R && rtab[0] == 0 && rtab[size_t(O)] == R);
+    std::vector<bool> seen(size_t(R), false);
+    for (int o = 0; o < O; ++o) {
+        CHECK(rtab[size_t(o)] <= rtab[size_t(o) + 1]);
+        for (int e = rtab[size_t(o)]; e < rtab[size_t(o) + 1]; ++e) {
+            const int i = rtab[size_t(O) + 1 + size_t(2) * e], r = rtab[size_t(O) + 2 + size_t(2) * e];
+            CHECK(r >= 0 && r < R && ro[size_t(r)] == o && ri[size_t(r)] == i && !seen[size_t(r)]);
+            seen[size_t(r)] = true;
+            CHECK(e == rtab[size_t(o)] || i > rtab[size_t(O) + 1 + size_t(2) * (e - 1)]);
+        }
+    }
 
     // refusals leave no plan behind that could be used: the reasons
     if (n % 10 == 0) {

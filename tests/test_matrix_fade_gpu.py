@@ -350,3 +350,71 @@ def test_batching_and_offline_windows_follow_the_new_filter(neo_gpu, oracle, met
     parts.append(conv.process(x[:, (k + 2) * B:]))
     conv.close()
     assert peak_err(np.concatenate(parts, axis=1), ref) <= TOL
+
+
+GEARS_R1 = [(0, 0), (0, 2), (1, 1)]
+
+
+@pytest.mark.parametrize("r2", [None, [(1, 0)]], ids=["dense", "one-route"])
+@pytest.mark.parametrize("method", ["upols", "upola"])
+def test_every_gear_on_one_handle_across_a_change_of_route_list(neo_gpu, oracle, method, r2):
+    """Batching and offline windows on before the first filter; route list R1: ONE call of 163 blocks
+    (an offline window, a pass of 32, passes of 2 and 1); an update over 3 blocks, calls of 5 and 160
+    blocks (the second offline pass runs on the new filter's spectra); then filter() with another
+    route list R2 (all six routes, or (1, 0) alone: output 0 has none) and 163 blocks more. The
+    buffers of the three gears follow the filter: gone at that filter(), back at the next use, and
+    the handle equals one that only ever saw R2."""
+    neo = neo_gpu
+    I, O, B, P = 3, 2, 16, 129  # two offline segments
+    n1, F, n2, n3, n4 = 163, 3, 5, 160, 163
+    nb = n1 + n2 + n3
+    rt, x, _, _, pa = problem(oracle, I, O, B, P, nb, GEARS_R1)
+    pb = bank_b(oracle, I, O, B, P, GEARS_R1)[2]
+    ref = mixed(neo, reference(oracle, I, O, B, P, nb, method, GEARS_R1),
+                reference_b(oracle, I, O, B, P, nb, method, tuple(GEARS_R1)), B, n1, F, "cosine")
+    rt2, x2, _, _, p2 = problem(oracle, I, O, B, P, n4 + 2, r2)
+    ref2 = reference(oracle, I, O, B, P, n4 + 2, method, r2)
+
+    def geared():
+        c = neo.MatrixConvolver(I, O, B, P, method=method)
+        c.set_batch(True)
+        c.set_offline(True)
+        return c
+
+    conv = geared()
+    conv.filter(pa, rt)
+    assert conv.offline_info()["spectra_bytes"] == 0 and conv.fade_info()["bank_bytes"] == 0
+    cuts = np.cumsum([0, n1, n2, n3]) * B
+    ys = [conv.process(x[:, cuts[0]:cuts[1]])]
+    spectra = len(rt) * 2 * 256 * B * 8
+    assert conv.offline_info()["spectra_bytes"] == spectra
+    conv.update_filter(pb, fade_blocks=F, curve="cosine")
+    assert conv.fade_info() == {"remaining_blocks": F, "fade_blocks": F, "bank_bytes": conv.info()["filter_bytes"]}
+    ys += [conv.process(x[:, cuts[1]:cuts[2]]), conv.process(x[:, cuts[2]:cuts[3]])]
+    assert conv.fade_info()["remaining_blocks"] == 0
+    for k, y in enumerate(ys):
+        err = peak_err(y, ref[:, cuts[k]:cuts[k + 1]])
+        print(f"{method} R1 stage {k}: err {err:.3g}")
+        assert err <= TOL, (k, err)
+    # another route list: the three groups are freed with the filter
+    conv.filter(p2, rt2)
+    assert conv.info()["routes"] == len(rt2)
+    assert conv.fade_info() == {"remaining_blocks": 0, "fade_blocks": 0, "bank_bytes": 0}
+    assert conv.offline_info()["spectra_bytes"] == 0
+    y4 = conv.process(x2[:, :n4 * B])
+    err = peak_err(y4, ref2[:, :n4 * B])
+    print(f"{method} R2 {len(rt2)} routes: err {err:.3g}")
+    assert err <= TOL
+    assert conv.offline_info()["spectra_bytes"] == len(rt2) * 2 * 256 * B * 8
+    fresh = geared()
+    fresh.filter(p2, rt2)
+    assert_same_bits(y4, fresh.process(x2[:, :n4 * B]), "after filter() with another route list: a fresh handle")
+    fresh.close()
+    if r2 is not None:
+        assert not y4[0].any(), "an output without a route must be exactly zero"
+    # the fade's buffers at their next use: an update to the same filter changes nothing
+    conv.update_filter(p2, fade_blocks=1)
+    assert conv.fade_info()["bank_bytes"] == conv.info()["filter_bytes"] == len(rt2) * P * B * 8
+    y5 = conv.process(x2[:, n4 * B:])
+    conv.close()
+    assert peak_err(np.concatenate([y4, y5], axis=1), ref2) <= TOL
