@@ -22,6 +22,7 @@
 #include <concepts>
 #include <cstddef>
 #include <memory>
+#include <span>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -680,6 +681,22 @@ struct hip_matrix_convolver {
     {
         offline_desc d{};
         neo::hip::check(neo_hip_matrix_offline_info(_h.get(), &d.blocks_per_pass, &d.segments, &d.ring_rows, &d.spectra_bytes));
+        return d;
+    }
+
+    /// window levels: long filters one block per call (neo_hip_matrix_set_levels). A single step then
+    /// reads only the head, partitions [0, 2 windows[0]), on every block and each level its band once per
+    /// window of its length, one window ahead. windows empty = the default (8, 32); split_workgroups 0 =
+    /// automatic. May be switched at any time between calls; throws on a bad window list
+    auto levels(bool on, std::span<int const> windows = {}, int split_workgroups = 0) -> void
+    {
+        neo::hip::check(neo_hip_matrix_set_levels(_h.get(), on ? 1 : 0, windows.empty() ? nullptr : windows.data(),
+                                                  int(windows.size()), split_workgroups));
+    }
+    [[nodiscard]] auto levels_info() const -> neo_hip_matrix_levels_desc
+    {
+        neo_hip_matrix_levels_desc d{};
+        neo::hip::check(neo_hip_matrix_levels_info(_h.get(), &d));
         return d;
     }
 

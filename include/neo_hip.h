@@ -85,8 +85,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.8.0: offline windows on matrix handles (neo_hip_matrix_set_offline, neo_hip_matrix_offline_info,
  *        neo_hip_matrix_offline_plan; neo_hip_matrix_desc gains offline_bytes at its end).
  * 0.9.0: crossfaded live filter updates on matrix handles (neo_hip_matrix_update_filter,
- *        neo_hip_matrix_update_impulse, neo_hip_matrix_fade_info, neo_hip_matrix_fade_gains). */
-#define NEO_HIP_VERSION 900 /* 0.9.0 */
+ *        neo_hip_matrix_update_impulse, neo_hip_matrix_fade_info, neo_hip_matrix_fade_gains).
+ * 0.10.0: window levels on matrix handles, long filters one block per call (neo_hip_matrix_set_levels,
+ *        neo_hip_matrix_levels_info, neo_hip_matrix_level_plan). */
+#define NEO_HIP_VERSION 1000 /* 0.10.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -501,11 +503,12 @@ NEO_HIP_API int neo_hip_upols_group_stats(neo_hip_upols_group* g, int* coalesced
  * along the block axis, for long filters with every block of a call known up front. A filter
  * changes in one of two ways: neo_hip_matrix_set_filter / _set_impulse take a new route list and
  * RESET all state; neo_hip_matrix_update_filter / _update_impulse (below) keep the route list and
- * ALL state and crossfade to the new filter while audio runs. Streaming levels,
+ * ALL state and crossfade to the new filter while audio runs. Window levels
+ * (neo_hip_matrix_set_levels below) are the gear for long filters with ONE block per call: only the
+ * first partitions are read on every block, the rest once per window of 8 or 32 blocks, one window
+ * ahead of time. The dense handle's streaming levels (a background stream),
  * latency mode, sub-block input (method 2), groups and the multi-device convolver
- * do not apply to this handle type; for very long filters with one block per call (from 256
- * partitions at 512 routes and more) O * I replicated channels on a neo_hip_upols
- * handle with streaming levels remain the faster form. */
+ * do not apply to this handle type (DESIGN 5.8 has the measurements of both forms). */
 typedef struct neo_hip_matrix neo_hip_matrix;
 typedef struct neo_hip_matrix_opts {
     int fused;            /* -1 auto (one MAC launch with the last-arriver tail up to 64 workgroups, tiles x splits),
@@ -686,6 +689,63 @@ typedef struct neo_hip_matrix_offline_plan_info {
 NEO_HIP_API int neo_hip_matrix_offline_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
                                             const int* route_in, int nroutes, int windows, int write_pos, int ring_rows,
                                             neo_hip_matrix_offline_plan_info* plan, int* pair_row, int* pair_of);
+/* Window levels: long filters in real time (one block per call). enable = 1: a single step reads
+ * only the HEAD, partitions [0, 2 T0), per block (the ordinary step on a compact second bank
+ * [routes][2 T0][B], copied from the filter at the first level step after a filter or a fade). A LEVEL
+ * with window length T (`windows`: ascending powers of two from 2, 4, 8, 16, 32, each at least twice
+ * the one before; NULL: the default 8, 32) takes the band of partitions [2 T, 2 T_next), the last level up
+ * to P; a level whose band is empty is dropped, and with P <= 2 T0 there is no level and the handle
+ * runs the ordinary step. n counts the blocks since the last reset (on every path); window W of a
+ * level is the blocks [W T, W T + T). The level's contribution to the T blocks of a window is one
+ * batched MAC over its band (k_matrix_lvl_mac), whose workgroups are cut into T parts of equal count:
+ * block n launches part n mod T of window n / T + 1 on the caller's stream, so every call does the
+ * same work, and a finish launch sums the head's slabs and row n mod T of every level's current
+ * window in a fixed order (head splits, then levels by T, splits ascending) and runs the inverse
+ * transform. Equal calls give equal bits; no atomics. Any block that runs without the parts (a
+ * batched or offline pass, a fade step, a step with the mode off) and a filter that changed (the end
+ * of a fade) leave the slabs stale; the next level step PRIMES them first (every level's current
+ * window whole, then the due parts of the next) and gives the bits the parts run in their turn
+ * would have given. Precedence in neo_hip_matrix_process: fade steps, offline windows, batched
+ * passes, then level steps. The ring stays at P rows (the schedule, priming included, never reads a
+ * row older than the ordinary step does). split_workgroups: the workgroup target of one PART (0
+ * automatic: 512, and no split of the longest output shorter than T rows; else taken as given), at
+ * most 64 splits per output. Allowed at any time between calls; joins the handle's streams; bad
+ * windows are refused and leave the handle as it was. */
+#define NEO_HIP_MATRIX_MAX_LEVELS 5
+NEO_HIP_API int neo_hip_matrix_set_levels(neo_hip_matrix* m, int enable, const int* windows, int nwindows,
+                                          int split_workgroups);
+typedef struct neo_hip_matrix_levels_desc {
+    int enabled, levels, head; /* levels in use (0: the ordinary step; 0 without a filter), head partitions */
+    int window[NEO_HIP_MATRIX_MAX_LEVELS], first[NEO_HIP_MATRIX_MAX_LEVELS], last[NEO_HIP_MATRIX_MAX_LEVELS];
+    int splits[NEO_HIP_MATRIX_MAX_LEVELS]; /* level l: window length, band [first, last), splits per output */
+    int ring_rows, primed;     /* rows of every input's ring; 1: the slabs are current */
+    int64_t partial_bytes;     /* the levels' double-buffered slabs, sum of 2 O S T rows (as planned) */
+    int64_t head_bank_bytes;   /* [routes][head][B] (as planned; allocated at the first level step) */
+} neo_hip_matrix_levels_desc;
+NEO_HIP_API int neo_hip_matrix_levels_info(neo_hip_matrix* m, neo_hip_matrix_levels_desc* desc);
+/* The level plan for a route list, on the host (no device needed; the handle is built from the same
+ * function). Per level l < levels: window[l], the band [first[l], last[l]), splits[l] per output,
+ * workgroups[l] = outputs x splits x chunks of a window, runs[l], and per WINDOW filter_rows[l]
+ * (routes x band) and fdl_rows[l] (per run its length + window - 1). bytes is the model of ONE block:
+ * 8 B (the head's filter and FDL row loads + 2 O head_splits slab rows) + per level 8 B (filter_rows +
+ * fdl_rows) / window + 8 B 2 O splits (the partial rows written per block and read by the finish) +
+ * 4 B (inputs + outputs). Arrays (each may be NULL): part_cut [5][33] (part k of level l is the
+ * workgroups [part_cut[33 l + k], part_cut[33 l + k + 1]), workgroup = (output x splits + split) x
+ * chunks + chunk); run_off [5][64 outputs + 1] (level l, split s of output o: runs k in [run_off[o S +
+ * s], run_off[o S + s + 1]) of that level's row); run_in, run_first, run_last [5][nroutes + 63 outputs]
+ * (run k covers partitions [run_first, run_last) of input run_in). */
+typedef struct neo_hip_matrix_level_plan_info {
+    int levels, head, ring_rows, chunks, head_splits, head_out_tile;
+    int window[NEO_HIP_MATRIX_MAX_LEVELS], first[NEO_HIP_MATRIX_MAX_LEVELS], last[NEO_HIP_MATRIX_MAX_LEVELS];
+    int splits[NEO_HIP_MATRIX_MAX_LEVELS], workgroups[NEO_HIP_MATRIX_MAX_LEVELS], runs[NEO_HIP_MATRIX_MAX_LEVELS];
+    int64_t filter_rows[NEO_HIP_MATRIX_MAX_LEVELS], fdl_rows[NEO_HIP_MATRIX_MAX_LEVELS];
+    int64_t head_filter_rows, head_fdl_rows; /* per block */
+    int64_t partial_bytes, head_bank_bytes, bytes;
+} neo_hip_matrix_level_plan_info;
+NEO_HIP_API int neo_hip_matrix_level_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                          const int* route_in, int nroutes, const int* windows, int nwindows,
+                                          int split_workgroups, neo_hip_matrix_level_plan_info* plan, int* part_cut,
+                                          int* run_off, int* run_in, int* run_first, int* run_last);
 /* The plan for a route list and options, on the host (no device needed; the handle is built from
  * the same function). Consecutive outputs form tiles of out_tile; a tile's row list is the union
  * of its outputs' inputs (ascending) x partitions 0..P-1, flattened, and split s of the S splits

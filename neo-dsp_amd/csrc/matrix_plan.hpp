@@ -319,4 +319,141 @@ inline const char* make_matrix_offline_plan(int I, int O, int B, int P, int nrou
     return nullptr;
 }
 
+// -- window levels (upols_matrix_levels.hip): long filters block by block ---------------------------
+//
+// n counts the blocks since the last reset; window W of a level with window length T is the blocks
+// [W T, W T + T). The head, the ordinary step on a compact bank, takes partitions [0, 2 T0); level k
+// takes the band [2 T_k, 2 T_(k+1)), the last one [2 T_last, P). For a band [a, b) with a >= 2 T
+//     slab[j] = sum over routes, p in [a, b) of H_r[p] X_i[W T + j - p],  j < T,
+// needs no row newer than block W T + T - 1 - a <= (W - 1) T - 1: every row was written before window
+// W - 1 began, so the slab may be computed at any step of window W - 1. Its workgroups (output x split
+// x bin chunk, the batched pass's walk over a run table restricted to the band) are cut into T parts
+// of equal count, to one; block n launches part n mod T of window n / T + 1.
+//
+// The ring. A step at block n has written the rows of blocks <= n and a ring of R rows holds blocks
+// n - R + 1 .. n. In their turn the parts of window W + 1 run at n <= W T + T - 1 and read back to
+// block (W + 1) T - P + 1: R >= P - 1. Priming at n = W T + m computes window W whole, of which the
+// rows j >= m are still to be read; row j reads back to block W T + j - P + 1 >= n - P + 1: R >= P
+// (the rows j < m may read overwritten ring rows: inside the ring, and nobody reads them). The head
+// reads back to n - 2 T0 + 1. So the ring is the plain step's, P rows, and nothing grows; a ring of
+// P - 1 rows loses the oldest row of a primed slab.
+constexpr int kMatrixMaxLevels = 5;  // 2, 4, 8, 16, 32
+// The most splits of a level. A level's partial slabs are 2 O S T rows (double-buffered) and the
+// finish reads O S of them per block, so the cap stays the batched pass's: at 32 x 32, B = 512, T = 32
+// 64 splits are 512 MiB of slabs and 128 workgroups per part.
+constexpr int kMatrixLevelMaxSplits = kMatrixMaxSplits;
+
+struct matrix_level {
+    int T = 0, a = 0, b = 0;   // window length, band [a, b)
+    int S = 1, nwg = 0;        // splits per output; workgroups of a window: O x S x G
+    std::vector<int> run_off;  // [O * S + 1] into the runs, split o * S + s
+    std::vector<int> runs;     // 4 ints per run: input, route, pa, pb (a <= pa < pb <= b)
+    std::vector<int> part_cut; // [T + 1] part k is the workgroups [part_cut[k], part_cut[k + 1])
+    int64_t filter_rows = 0, fdl_rows = 0;  // per window
+    int64_t slab_off = 0;      // of this level's slabs [2][O][S][T][B] in the partial buffer, in rows
+    int nruns() const { return int(runs.size() / 4); }
+};
+
+struct matrix_level_plan {
+    int head = 0, G = 1, O = 0, ring = 0;
+    matrix_plan hplan;                 // the head: the ordinary step over partitions [0, head), unfused
+    std::vector<int> route_out, route_in;  // the route list the head plan was made from
+    std::vector<matrix_level> levels;  // T ascending; empty: the handle runs the ordinary step
+    int64_t partial_rows = 0, partial_bytes = 0, head_bank_bytes = 0;
+    int64_t bytes = 0;                 // the model of one block
+};
+
+// windows == nullptr: the default (8, 32), ahead of (4, 8, 16, 32) at every shape of
+// tools/matrix_levels_sweep.py (each level is a launch per block). split_wgs: 0 auto (each PART aims at
+// kMatrixBatchAutoWgs workgroups, no split of the longest output shorter than T rows), else the
+// workgroup target of a part, taken as given; at most kMatrixLevelMaxSplits.
+inline const char* make_matrix_level_plan(const matrix_plan& pl, const int* windows, int nwindows, int split_wgs,
+                                          matrix_level_plan& lp)
+{
+    static constexpr int kDefault[] = {8, 32};
+    if (!windows) windows = kDefault, nwindows = 2;
+    if (nwindows < 1 || nwindows > kMatrixMaxLevels) return "1 to 5 windows";
+    for (int k = 0; k < nwindows; ++k) {
+        const int T = windows[k];
+        if (T < 2 || T > kMatrixBatch || (T & (T - 1))) return "a window must be 2, 4, 8, 16 or 32";
+        if (k && T < 2 * windows[k - 1]) return "windows must ascend, each at least twice the one before";
+    }
+    if (split_wgs < 0) return "split_workgroups must be >= 0";
+    lp = matrix_level_plan{};
+    const int I = pl.I, O = pl.O, P = pl.P, B = pl.B;
+    lp.O = O, lp.G = matrix_batch_chunks(B), lp.ring = P;
+    lp.head = std::min(P, 2 * windows[0]);
+    lp.route_out.assign(size_t(pl.nroutes), 0), lp.route_in.assign(size_t(pl.nroutes), 0);
+    for (int o = 0; o < O; ++o)
+        for (int i = 0; i < I; ++i)
+            if (const int r = pl.rt[size_t(o) * I + i]; r >= 0) lp.route_out[size_t(r)] = o, lp.route_in[size_t(r)] = i;
+    if (const char* why = make_matrix_plan(I, O, B, lp.head, lp.route_out.data(), lp.route_in.data(), pl.nroutes, 0, 0, 0, lp.hplan))
+        return why;
+    int maxin = 1;  // the inputs of the longest output
+    for (int o = 0; o < O; ++o) {
+        int n = 0;
+        for (int i = 0; i < I; ++i) n += pl.rt[size_t(o) * I + i] >= 0;
+        maxin = std::max(maxin, n);
+    }
+    // head: filter and FDL row loads, the slabs written and read; block I/O
+    int64_t bytes = 8 * int64_t(B) * (lp.hplan.filter_loads + lp.hplan.fdl_loads + 2 * int64_t(O) * lp.hplan.S) +
+                    4 * int64_t(B) * (I + O);
+    for (int k = 0; k < nwindows; ++k) {
+        matrix_level lv;
+        lv.T = windows[k], lv.a = 2 * lv.T, lv.b = k + 1 < nwindows ? std::min(P, 2 * windows[k + 1]) : P;
+        if (lv.a >= lv.b) continue;  // an empty band
+        const int len = lv.b - lv.a, maxrows = maxin * len;
+        const int64_t per_split = int64_t(O) * lp.G;
+        const int64_t want = (int64_t(split_wgs ? split_wgs : kMatrixBatchAutoWgs) * lv.T + per_split - 1) / per_split;
+        const int most = split_wgs ? maxrows : std::max(1, maxrows / lv.T);
+        lv.S = int(std::max<int64_t>(1, std::min<int64_t>({want, most, kMatrixLevelMaxSplits})));
+        lv.nwg = int(per_split) * lv.S;
+        lv.run_off.assign(1, 0);
+        for (int o = 0; o < O; ++o) {
+            int rows = 0;
+            for (int i = 0; i < I; ++i) rows += pl.rt[size_t(o) * I + i] >= 0 ? len : 0;
+            for (int s = 0; s < lv.S; ++s) {
+                const int r0 = int(int64_t(s) * rows / lv.S), r1 = int(int64_t(s + 1) * rows / lv.S);
+                int row = 0;
+                for (int i = 0; i < I && row < r1; ++i) {
+                    const int r = pl.rt[size_t(o) * I + i];
+                    if (r < 0) continue;
+                    const int x = std::max(r0, row), y = std::min(r1, row + len);
+                    if (x < y) {
+                        lv.runs.insert(lv.runs.end(), {i, r, lv.a + x - row, lv.a + y - row});
+                        lv.fdl_rows += y - x + lv.T - 1;
+                    }
+                    row += len;
+                }
+                lv.run_off.push_back(lv.nruns());
+            }
+        }
+        for (int t = 0; t <= lv.T; ++t) lv.part_cut.push_back(int(int64_t(t) * lv.nwg / lv.T));
+        lv.filter_rows = int64_t(pl.nroutes) * len;
+        lv.slab_off = lp.partial_rows;
+        lp.partial_rows += 2 * int64_t(O) * lv.S * lv.T;
+        // per block: the window's filter and FDL rows / T, O S partial rows written and O S read
+        bytes += 8 * int64_t(B) * (lv.filter_rows + lv.fdl_rows) / lv.T + 8 * int64_t(B) * 2 * O * lv.S;
+        lp.levels.push_back(std::move(lv));
+    }
+    if (lp.levels.empty()) {  // the ordinary step: what neo_hip_matrix_plan's bytes are
+        lp.head = P;
+        lp.hplan = matrix_plan{};
+        bytes = 8 * int64_t(B) * (pl.filter_loads + pl.fdl_loads) + 4 * int64_t(B) * (I + O);
+    } else {
+        lp.head_bank_bytes = int64_t(pl.nroutes) * lp.head * B * 8;
+    }
+    lp.partial_bytes = lp.partial_rows * B * 8;
+    lp.bytes = bytes;
+    return nullptr;
+}
+
+// what k_matrix_lvl_mac reads for one level: run_off [O S + 1], then the runs
+inline std::vector<int> matrix_level_table(const matrix_level& lv)
+{
+    std::vector<int> tab(lv.run_off);
+    tab.insert(tab.end(), lv.runs.begin(), lv.runs.end());
+    return tab;
+}
+
 }  // namespace neo_hip

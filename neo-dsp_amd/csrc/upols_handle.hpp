@@ -400,6 +400,20 @@ int launch_matrix_fade_mac(const cf* HA, const cf* HB, const cf* fdl, cf* part, 
                            int O, int S, int w, hipStream_t s);
 int launch_matrix_fade_finish(const cf* part, float* out, int64_t ld_out, float* ovl_a, float* ovl_b, const cf* tw, int B,
                               int O, int S, bool ola, bool prime, int64_t n0, int64_t total, int curve, hipStream_t s);
+// upols_matrix_levels.hip: window levels of a matrix handle. mac: the workgroups [wg0, wg1) of a
+// level's grid O x S x chunks (a part; none: no launch) for the window of T blocks whose block 0 is
+// ring row w, over the level's run table tab (matrix_level_table, matrix_plan.hpp), into that
+// window's slabs part [O][S][T][B]. finish: per output the head's slabs head [O][Sh][B] in order, then
+// per level l < n the S[l] rows row[l] + ((o S[l] + s) T[l]) B, s ascending, then the c2r tail.
+struct matrix_lvl_rows {
+    const cf* row[5];  // kMatrixMaxLevels
+    int S[5], T[5];
+    int n;
+};
+int launch_matrix_lvl_mac(const cf* H, const cf* fdl, cf* part, const int* tab, int B, int P, int ring, int O, int S, int T,
+                          int w, int wg0, int wg1, hipStream_t s);
+int launch_matrix_lvl_finish(int O, int B, bool ola, const cf* head, int Sh, const matrix_lvl_rows& lv, float* out,
+                             int64_t ld_out, float* ovl, const cf* tw, hipStream_t s);
 // Timing (neo_hip_upols_set_timing): the next event group of nev events if this launch
 // group is a timed one (every h->timing-th), else nullptr; mark(g, i, s) records event i.
 inline int timing_begin(upols_t* h, int nev, upols_t::ev_group** out)

@@ -49,7 +49,16 @@
 // passes as before. Overlap-add keeps a tail per bank; bank B's tail of the block before the update
 // is formed at the update call by one MAC at write position w - 1 (its rows are all intact).
 //
-// Host side: the buffers of batching, offline windows and updates are three groups of one shape
+// Window levels (neo_hip_matrix_set_levels; upols_matrix_levels.hip, the plan in matrix_plan.hpp) are
+// the gear for long filters with ONE block per call: a single step is then k_matrix_window,
+// k_matrix_step unfused over the head, partitions [0, 2 T0), of a compact bank H_head
+// [nroutes][2 T0][B], per level one k_matrix_lvl_mac launch (part n mod T of the window after this
+// block's, into that window's half of the level's slabs part_l [2][O][S][T][B]) and
+// k_matrix_lvl_finish (the head's slabs, row n mod T of every level's current window, the c2r tail).
+// n (nblk) counts the blocks since the last reset on every path; whatever advances it without the
+// parts leaves the slabs stale and the next level step primes them. The ring stays at P rows.
+//
+// Host side: the buffers of batching, offline windows, updates and levels are four groups of one shape
 // (matrix_group), each taken whole at its first use after a filter and freed with it; the four
 // filter calls are two loaders (matrix_load_filter, matrix_load_impulse: a bank, a stream, no wait)
 // followed by matrix_set_end (reset, complete on return) or matrix_update_end (the fade armed).
@@ -102,6 +111,20 @@ struct neo_hip_matrix {
     float* ovl2 = nullptr;         // [O][B] bank B's overlap-add tails
     int fade_S = 1;
     int fade_left = 0, fade_total = 0, fade_curve = 0;  // blocks left of the running fade (0: none)
+    // window levels (neo_hip_matrix_set_levels; upols_matrix_levels.hip)
+    int64_t nblk = 0;                  // blocks since the last reset, counted on every path
+    bool levels = false;
+    std::vector<int> lv_windows;       // the windows as given (empty: the default)
+    int lv_split = 0;                  // the workgroup target of a part as given (0 auto)
+    neo_hip::matrix_level_plan lplan;  // with the filter
+    neo_hip::cf* H_head = nullptr;     // [nroutes][head][B] the head's bank; these five from the first level step on
+    neo_hip::cf* part_h = nullptr;     // [O][head splits][B]
+    neo_hip::cf* part_l = nullptr;     // per level [2][O][S][T][B], level l at lplan.levels[l].slab_off rows
+    int* htab = nullptr;               // the head plan's tile table
+    int* ltab = nullptr;               // the levels' run tables, level l at lv_tab[l]
+    std::vector<int> lv_tab;
+    bool head_dirty = true;            // H_head follows the filter: copied at the next level step
+    bool lv_primed = false;            // the slabs hold the current windows and the due parts of the next
     neo_hip::stream_set used;
 };
 
@@ -335,7 +358,10 @@ int matrix_reset_state(matrix_t* m, hipStream_t s)
     NEO_HIP_CHECK(hipMemsetAsync(m->prev, 0, size_t(m->I) * m->B * sizeof(float), s));
     NEO_HIP_CHECK(hipMemsetAsync(m->ovl, 0, size_t(m->O) * m->B * sizeof(float), s));
     if (m->arrivals) NEO_HIP_CHECK(hipMemsetAsync(m->arrivals, 0, size_t(m->plan.ntiles) * sizeof(int), s));
+    if (m->part_l) NEO_HIP_CHECK(hipMemsetAsync(m->part_l, 0, size_t(m->lplan.partial_bytes), s));
     m->wpos = 0;
+    m->nblk = 0;
+    m->lv_primed = true;  // every row before block 0 is zero, so window 0's slabs are
     return NEO_HIP_OK;
 }
 
@@ -369,6 +395,12 @@ void matrix_free_fade(matrix_t* m)  // they follow the route list; a running fad
     m->fade_left = m->fade_total = 0;
 }
 
+void matrix_free_levels(matrix_t* m)  // they follow the level plan
+{
+    drop(m->H_head, m->part_h, m->part_l, m->htab, m->ltab);
+    m->head_dirty = true;
+}
+
 int64_t matrix_offline_bytes(const matrix_t* m)
 {
     if (!m->off_hf) return 0;
@@ -384,6 +416,7 @@ void matrix_free_filter(matrix_t* m)
     matrix_free_batch(m);
     matrix_free_offline(m);
     matrix_free_fade(m);
+    matrix_free_levels(m);
     drop(m->H, m->part, m->arrivals, m->tab);
     m->rtab = nullptr;
     m->ready = false;
@@ -425,6 +458,10 @@ int matrix_adopt(matrix_t* m, matrix_plan&& pl)
     m->plan = std::move(pl);
     // (refused only for a ring that set_batch refuses too: batching is off then)
     if (make_matrix_batch_plan(m->plan, kMatrixBatch, m->b_split, m->bplan)) m->bplan = matrix_batch_plan{};
+    // (the windows were checked by set_levels)
+    if (make_matrix_level_plan(m->plan, m->lv_windows.empty() ? nullptr : m->lv_windows.data(), int(m->lv_windows.size()),
+                               m->lv_split, m->lplan))
+        m->lplan = matrix_level_plan{};
     const matrix_plan& p = m->plan;
     std::vector<int> tab = matrix_tile_table(p);
     const size_t ntile = tab.size();
@@ -470,14 +507,15 @@ int matrix_pass_windows(matrix_t* m, const float* in, int64_t ld_in, int T, hipS
     return NEO_HIP_OK;
 }
 
-int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+// k_matrix_step at the write position for a plan over the first P partitions of the bank H [nroutes][P][B]
+// (the handle's own, or the head of the window levels: unfused, so out, ovl and arrivals are not touched)
+int matrix_step_launch(matrix_t* m, const matrix_plan& p, const cf* H, cf* part, int* arrivals, const int* tab, int P,
+                       float* out, int64_t ld_out, hipStream_t s)
 {
-    const matrix_plan& p = m->plan;
-    if (int rc = matrix_window(m, in, ld_in, s)) return rc;
     const unsigned grid = unsigned(p.ntiles) * unsigned(p.S);
-#define NEO_MATRIX_STEP(OT_, FU, OL)                                                                                   \
-    hipLaunchKernelGGL((k_matrix_step<BB, OT_, FU, OL>), dim3(grid), dim3(256), 0, s, out, ld_out, m->ovl, m->H,     \
-                       m->fdl, m->part, m->arrivals, m->tw, m->tab, p.ntiles, m->I, m->P, m->ring, p.S, m->wpos)
+#define NEO_MATRIX_STEP(OT_, FU, OL)                                                                              \
+    hipLaunchKernelGGL((k_matrix_step<BB, OT_, FU, OL>), dim3(grid), dim3(256), 0, s, out, ld_out, m->ovl, H, m->fdl, \
+                       part, arrivals, m->tw, tab, p.ntiles, m->I, P, m->ring, p.S, m->wpos)
 #define NEO_MATRIX_STEP_T(FU, OL)                                                              \
     NEO_UPOLS_DISPATCH(m->B, {                                                                 \
         constexpr int CAP = matrix_max_tile(BB);                                               \
@@ -493,6 +531,14 @@ int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t
 #undef NEO_MATRIX_STEP_T
 #undef NEO_MATRIX_STEP
     NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+int matrix_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    const matrix_plan& p = m->plan;
+    if (int rc = matrix_window(m, in, ld_in, s)) return rc;
+    if (int rc = matrix_step_launch(m, p, m->H, m->part, m->arrivals, m->tab, m->P, out, ld_out, s)) return rc;
     if (!p.fused) {
         // k_upols_finish: one workgroup per output sums its slabs [S][B] in order and runs the c2r
         // (overlap-add: the output's tail)
@@ -623,6 +669,7 @@ void matrix_fade_swap(matrix_t* m)
     if (m->ola) std::swap(m->ovl, m->ovl2);
     m->fade_left = m->fade_total = 0;
     m->off_dirty = true;
+    m->head_dirty = true;
 }
 
 // one block of a running fade: the window launch as ever, then both banks against the same FDL rows
@@ -640,20 +687,101 @@ int matrix_fade_step(matrix_t* m, const float* in, int64_t ld_in, float* out, in
     return NEO_HIP_OK;
 }
 
+// the head's bank and slabs, the levels' slabs (zero: window 0's after a reset) and the tables, at the
+// first level step after a filter or a set_levels
+int matrix_level_buffers(matrix_t* m, hipStream_t s)
+{
+    if (m->part_l) return NEO_HIP_OK;
+    const matrix_level_plan& lp = m->lplan;
+    std::vector<int> tab;
+    m->lv_tab.clear();
+    for (const matrix_level& lv : lp.levels) {
+        m->lv_tab.push_back(int(tab.size()));
+        const std::vector<int> t = matrix_level_table(lv);
+        tab.insert(tab.end(), t.begin(), t.end());
+    }
+    const size_t rowbytes = size_t(m->B) * sizeof(cf);
+    int rc = dalloc(&m->H_head, size_t(lp.head_bank_bytes));
+    if (!rc) rc = dalloc(&m->part_h, size_t(m->O) * lp.hplan.S * rowbytes);
+    if (!rc) rc = dalloc(&m->part_l, size_t(lp.partial_bytes));
+    if (!rc) rc = matrix_upload(&m->htab, matrix_tile_table(lp.hplan), s);
+    if (!rc) rc = matrix_upload(&m->ltab, tab, s);
+    if (!rc && hipMemsetAsync(m->part_l, 0, size_t(lp.partial_bytes), s) != hipSuccess) rc = NEO_HIP_ERUNTIME;
+    m->head_dirty = true;
+    m->lv_primed = m->nblk == 0;  // fresh slabs are window 0's after a reset, stale after any block
+    return matrix_group(m, rc, matrix_free_levels, "level");
+}
+
+// One block with window levels on (matrix_plan.hpp, "window levels"): the window launch, the head
+// (the ordinary step, unfused, on the compact bank), per level part n mod T of window n / T + 1 into
+// that window's half of the slabs, then the finish over the head's slabs and row n mod T of every
+// level's current window. Stale slabs (any block that ran without the parts, a changed filter) are
+// primed first: the current window whole, and the next window's parts already due in the same launch
+// as this block's part (a part is a range of workgroups, each of which computes what it computes in
+// any launch: the bits are those of the parts run in their turn).
+int matrix_level_step(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    const matrix_level_plan& lp = m->lplan;
+    if (int rc = matrix_level_buffers(m, s)) return rc;
+    const size_t rowbytes = size_t(m->B) * sizeof(cf);
+    if (m->head_dirty) {  // rows [0, head) of every route (the bank was written on this stream or is complete)
+        NEO_HIP_CHECK(hipMemcpy2DAsync(m->H_head, lp.head * rowbytes, m->H, m->P * rowbytes, lp.head * rowbytes,
+                                       size_t(m->plan.nroutes), hipMemcpyDeviceToDevice, s));
+        m->head_dirty = false;
+    }
+    if (int rc = matrix_window(m, in, ld_in, s)) return rc;
+    if (int rc = matrix_step_launch(m, lp.hplan, m->H_head, m->part_h, nullptr, m->htab, lp.head, out, ld_out, s)) return rc;
+    matrix_lvl_rows rows{};
+    for (size_t l = 0; l < lp.levels.size(); ++l) {
+        const matrix_level& lv = lp.levels[l];
+        const int T = lv.T, k = int(m->nblk % T);
+        const int64_t W = m->nblk / T, half = int64_t(m->O) * lv.S * T * m->B;
+        cf* cur = m->part_l + lv.slab_off * m->B + (W & 1) * half;
+        cf* next = m->part_l + lv.slab_off * m->B + ((W + 1) & 1) * half;
+        const int* tab = m->ltab + m->lv_tab[l];
+        if (!m->lv_primed)
+            if (int rc = launch_matrix_lvl_mac(m->H, m->fdl, cur, tab, m->B, m->P, m->ring, m->O, lv.S, T, matrix_row(m, -k), 0,
+                                               lv.nwg, s))
+                return rc;
+        if (int rc = launch_matrix_lvl_mac(m->H, m->fdl, next, tab, m->B, m->P, m->ring, m->O, lv.S, T, matrix_row(m, T - k),
+                                           lv.part_cut[size_t(m->lv_primed ? k : 0)], lv.part_cut[size_t(k) + 1], s))
+            return rc;
+        rows.row[l] = cur + int64_t(k) * m->B;
+        rows.S[l] = lv.S, rows.T[l] = T;
+    }
+    rows.n = int(lp.levels.size());
+    if (int rc = launch_matrix_lvl_finish(m->O, m->B, m->ola, m->part_h, lp.hplan.S, rows, out, ld_out, m->ovl, m->tw, s))
+        return rc;
+    m->wpos = matrix_row(m, 1);
+    ++m->nblk;
+    m->lv_primed = true;
+    return NEO_HIP_OK;
+}
+
+// T blocks ran without the levels' parts: their slabs are stale
+void matrix_advanced(matrix_t* m, int T)
+{
+    m->nblk += T;
+    m->lv_primed = false;
+}
+
 // the blocks of a call: while a fade has blocks left single fade steps; with offline windows on
 // passes of 256 (two windows, if allowed) and 128 blocks while that many are left; then with batching
-// on the largest power-of-two passes <= 32 of the blocks left, then single steps
+// on the largest power-of-two passes <= 32 of the blocks left, then single steps: level steps with
+// window levels on (and a filter long enough to have a level), else plain steps
 int matrix_blocks(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t nblocks, hipStream_t s)
 {
     for (int64_t t = 0; t < nblocks;) {
         if (m->fade_left > 0) {
             if (int rc = matrix_fade_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s)) return rc;
+            matrix_advanced(m, 1);
             ++t;
             continue;
         }
         if (m->offline && nblocks - t >= kMatrixOffWindow) {
             const int wp = m->off_wp != 1 && nblocks - t >= 2 * kMatrixOffWindow ? 2 : 1;
             if (int rc = matrix_offline(m, in + t * m->B, ld_in, out + t * m->B, ld_out, wp, s)) return rc;
+            matrix_advanced(m, wp * kMatrixOffWindow);
             t += wp * kMatrixOffWindow;
             continue;
         }
@@ -662,9 +790,15 @@ int matrix_blocks(matrix_t* m, const float* in, int64_t ld_in, float* out, int64
             T = kMatrixBatch;
             while (T > nblocks - t) T >>= 1;
         }
+        if (T == 1 && m->levels && !m->lplan.levels.empty()) {
+            if (int rc = matrix_level_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s)) return rc;
+            ++t;
+            continue;
+        }
         const int rc = T > 1 ? matrix_batch(m, in + t * m->B, ld_in, out + t * m->B, ld_out, T, s)
                              : matrix_step(m, in + t * m->B, ld_in, out + t * m->B, ld_out, s);
         if (rc) return rc;
+        matrix_advanced(m, T);
         t += T;
     }
     return NEO_HIP_OK;
@@ -1122,6 +1256,93 @@ NEO_HIP_API int neo_hip_matrix_batch_plan(int inputs, int outputs, int block, in
         if (run_in) run_in[k] = bp.runs[size_t(4) * k];
         if (run_first) run_first[k] = bp.runs[size_t(4) * k + 2];
         if (run_last) run_last[k] = bp.runs[size_t(4) * k + 3];
+    }
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_set_levels(neo_hip_matrix* m, int enable, const int* windows, int nwindows,
+                                          int split_workgroups)
+{
+    if (!m) return fail(NEO_HIP_EINVAL, "null handle");
+    if (enable < 0 || enable > 1 || split_workgroups < 0 || (windows && nwindows < 1))
+        return fail(NEO_HIP_EINVAL, "matrix set_levels: enable must be 0 or 1, split_workgroups >= 0, nwindows >= 1");
+    matrix_level_plan lp;  // refused windows leave the handle as it was
+    {
+        const int zero = 0;
+        matrix_plan one;  // without a filter a one-route list stands in: the windows are checked all the same
+        if (!m->ready) (void)make_matrix_plan(m->I, m->O, m->B, m->P, &zero, &zero, 1, -1, 0, 0, one);
+        if (const char* why = make_matrix_level_plan(m->ready ? m->plan : one, windows, nwindows, split_workgroups, lp))
+            return fail(NEO_HIP_EINVAL, "matrix set_levels: %s", why);
+    }
+    device_guard g(m->device);
+    if (g.rc) return g.rc;
+    if (int rc = matrix_join(m, false)) return rc;
+    if (enable && m->ring < lp.ring)  // (never today: the schedule's ring is the plain step's, P rows)
+        if (int rc = matrix_grow_ring(m, lp.ring)) return rc;
+    m->levels = enable != 0;  // off: plain steps; the next level step primes
+    m->lv_windows.assign(windows, windows + (windows ? nwindows : 0));
+    m->lv_split = split_workgroups;
+    matrix_free_levels(m);  // sized by the plan; the next level step allocates them
+    m->lplan = m->ready ? std::move(lp) : matrix_level_plan{};
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_levels_info(neo_hip_matrix* m, neo_hip_matrix_levels_desc* d)
+{
+    if (!m || !d) return fail(NEO_HIP_EINVAL, "null handle or descriptor");
+    std::memset(d, 0, sizeof *d);
+    d->enabled = m->levels ? 1 : 0;
+    d->ring_rows = m->ring;
+    if (!m->ready) return NEO_HIP_OK;
+    const matrix_level_plan& lp = m->lplan;
+    d->levels = int(lp.levels.size());
+    d->head = lp.head;
+    for (size_t l = 0; l < lp.levels.size(); ++l)
+        d->window[l] = lp.levels[l].T, d->first[l] = lp.levels[l].a, d->last[l] = lp.levels[l].b, d->splits[l] = lp.levels[l].S;
+    d->primed = m->levels && d->levels && m->lv_primed && (m->part_l || m->nblk == 0) ? 1 : 0;
+    d->partial_bytes = lp.partial_bytes;
+    d->head_bank_bytes = lp.head_bank_bytes;
+    return NEO_HIP_OK;
+}
+
+NEO_HIP_API int neo_hip_matrix_level_plan(int inputs, int outputs, int block, int partitions, const int* route_out,
+                                          const int* route_in, int nroutes, const int* windows, int nwindows,
+                                          int split_workgroups, neo_hip_matrix_level_plan_info* plan, int* part_cut,
+                                          int* run_off, int* run_in, int* run_first, int* run_last)
+{
+    static_assert(NEO_HIP_MATRIX_MAX_LEVELS == kMatrixMaxLevels && kMatrixLevelMaxSplits == 64 && kMatrixBatch == 32);
+    matrix_plan p;
+    if (const char* why = make_matrix_plan(inputs, outputs, block, partitions, route_out, route_in, nroutes, -1, 0, 0, p))
+        return fail(NEO_HIP_EINVAL, "matrix_level_plan: %s", why);
+    if (windows && nwindows < 1) return fail(NEO_HIP_EINVAL, "matrix_level_plan: nwindows must be >= 1");
+    matrix_level_plan lp;
+    if (const char* why = make_matrix_level_plan(p, windows, nwindows, split_workgroups, lp))
+        return fail(NEO_HIP_EINVAL, "matrix_level_plan: %s", why);
+    if (plan) {
+        std::memset(plan, 0, sizeof *plan);
+        plan->levels = int(lp.levels.size());
+        plan->head = lp.head, plan->ring_rows = lp.ring, plan->chunks = lp.G;
+        if (plan->levels) {
+            plan->head_splits = lp.hplan.S, plan->head_out_tile = lp.hplan.OT;
+            plan->head_filter_rows = lp.hplan.filter_loads, plan->head_fdl_rows = lp.hplan.fdl_loads;
+        }
+        plan->partial_bytes = lp.partial_bytes, plan->head_bank_bytes = lp.head_bank_bytes, plan->bytes = lp.bytes;
+    }
+    const int64_t run_cap = int64_t(nroutes) + int64_t(kMatrixLevelMaxSplits - 1) * outputs;
+    for (size_t l = 0; l < lp.levels.size(); ++l) {
+        const matrix_level& lv = lp.levels[l];
+        if (plan) {
+            plan->window[l] = lv.T, plan->first[l] = lv.a, plan->last[l] = lv.b, plan->splits[l] = lv.S;
+            plan->workgroups[l] = lv.nwg, plan->runs[l] = lv.nruns();
+            plan->filter_rows[l] = lv.filter_rows, plan->fdl_rows[l] = lv.fdl_rows;
+        }
+        if (part_cut) std::copy(lv.part_cut.begin(), lv.part_cut.end(), part_cut + l * (kMatrixBatch + 1));
+        if (run_off) std::copy(lv.run_off.begin(), lv.run_off.end(), run_off + l * (size_t(kMatrixLevelMaxSplits) * outputs + 1));
+        for (int k = 0; k < lv.nruns(); ++k) {
+            if (run_in) run_in[int64_t(l) * run_cap + k] = lv.runs[size_t(4) * k];
+            if (run_first) run_first[int64_t(l) * run_cap + k] = lv.runs[size_t(4) * k + 2];
+            if (run_last) run_last[int64_t(l) * run_cap + k] = lv.runs[size_t(4) * k + 3];
+        }
     }
     return NEO_HIP_OK;
 }

@@ -16,7 +16,8 @@ from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_c
                           sparse_upols_convolver, PerceptualSparsity, a_weighting, amplitude_to_db, perceptual_histogram,
                           perceptual_histogram_host, perceptual_mask, perceptual_mask_host, perceptual_weights,
                           threshold_for_tile_density, tile_density_curve,
-                          MatrixConvolver, matrix_batch_plan, matrix_convolve, matrix_fade_gains, matrix_offline_plan, matrix_plan)
+                          MatrixConvolver, matrix_batch_plan, matrix_convolve, matrix_fade_gains, matrix_level_plan,
+                          matrix_offline_plan, matrix_plan)
 
 __version__ = "0.1.0"
 
@@ -52,6 +53,7 @@ __all__ = [
     "matrix_plan",
     "matrix_batch_plan",
     "matrix_offline_plan",
+    "matrix_level_plan",
     "matrix_convolve",
     "matrix_fade_gains",
     "a_weighting",

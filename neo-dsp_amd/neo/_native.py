@@ -62,6 +62,26 @@ class MatrixOfflinePlanInfo(ctypes.Structure):
                                               "pair_rows_written", "output_rows", "bytes", "cache_bytes")]
 
 
+MATRIX_MAX_LEVELS = 5  # NEO_HIP_MATRIX_MAX_LEVELS
+
+
+class MatrixLevelsDesc(ctypes.Structure):
+    """neo_hip_matrix_levels_desc (include/neo_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("enabled", "levels", "head")] + \
+               [(n, ctypes.c_int * MATRIX_MAX_LEVELS) for n in ("window", "first", "last", "splits")] + \
+               [("ring_rows", ctypes.c_int), ("primed", ctypes.c_int),
+                ("partial_bytes", ctypes.c_int64), ("head_bank_bytes", ctypes.c_int64)]
+
+
+class MatrixLevelPlanInfo(ctypes.Structure):
+    """neo_hip_matrix_level_plan_info (include/neo_hip.h)."""
+    _fields_ = [(n, ctypes.c_int) for n in ("levels", "head", "ring_rows", "chunks", "head_splits", "head_out_tile")] + \
+               [(n, ctypes.c_int * MATRIX_MAX_LEVELS) for n in ("window", "first", "last", "splits", "workgroups", "runs")] + \
+               [(n, ctypes.c_int64 * MATRIX_MAX_LEVELS) for n in ("filter_rows", "fdl_rows")] + \
+               [(n, ctypes.c_int64) for n in ("head_filter_rows", "head_fdl_rows", "partial_bytes", "head_bank_bytes",
+                                              "bytes")]
+
+
 class Perceptual(ctypes.Structure):
     """neo_hip_perceptual (include/neo_hip.h)."""
     _fields_ = [("sample_rate", ctypes.c_double), ("threshold_db", ctypes.c_float),
@@ -156,6 +176,9 @@ SIGNATURES = {
     "neo_hip_matrix_update_impulse": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "neo_hip_matrix_fade_info": (_i, [_vp, _vp, _vp, _vp]),
     "neo_hip_matrix_fade_gains": (_i, [_i, _i, _i, _vp]),
+    "neo_hip_matrix_set_levels": (_i, [_vp, _i, _vp, _i, _i]),
+    "neo_hip_matrix_levels_info": (_i, [_vp, _vp]),
+    "neo_hip_matrix_level_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _i, _vp] + [_vp] * 5),
     "neo_hip_overlap_create": (_i, [_i, _i, _i64, _i64, _i, ctypes.POINTER(_vp)]),
     "neo_hip_overlap_destroy": (_i, [_vp]),
     "neo_hip_overlap_info": (_i, [_vp] + [ctypes.POINTER(_i64)] * 3),
@@ -185,7 +208,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 900 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1000 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -57,6 +57,7 @@ __all__ = [
     "matrix_plan",
     "matrix_batch_plan",
     "matrix_offline_plan",
+    "matrix_level_plan",
     "matrix_convolve",
     "matrix_fade_gains",
     "a_weighting",
@@ -1437,6 +1438,56 @@ def matrix_offline_plan(inputs: int, outputs: int, block_size: int, partitions: 
     return d
 
 
+def _windows(windows):
+    """windows=None: the library's default (a NULL list). -> (int32 array or None, pointer, count)"""
+    if windows is None:
+        return None, None, 0
+    w = np.ascontiguousarray(list(windows), dtype=np.int32).reshape(-1)
+    n = len(w)
+    if not n:  # an empty list is not the default: a real pointer and a count of 0, the library's refusal
+        w = np.zeros(1, np.int32)
+    return w, _ptr(w), n
+
+
+def matrix_level_plan(inputs: int, outputs: int, block_size: int, partitions: int, routes=None, windows=None,
+                      split_workgroups: int = 0) -> dict:
+    """The window-level plan of a matrix convolver (neo_hip_matrix_level_plan; no device needed, the
+    function the handle itself is built from). `windows`: ascending powers of two from 2 .. 32, each
+    at least twice the one before (None: the default, 8, 32). The head, the ordinary step, takes partitions
+    [0, head); level l with window length `window` takes the band [first, last) and is, per window of
+    `window` blocks, `workgroups` = outputs x splits x chunks workgroups (workgroup = (output x splits
+    + split) x chunks + chunk), cut into `window` parts: part k is the workgroups [part_cuts[k],
+    part_cuts[k + 1]), launched at block n = k (mod window) for the window after that block's.
+    Per level, outputs[o][s] lists the runs (input, first partition, one past the last) of split s of
+    output o; filter_rows and fdl_rows are the row loads of one window. ring_rows: the least ring of
+    the schedule, priming included. partial_bytes: the levels' double-buffered slabs;
+    head_bank_bytes: the head's compact bank. `bytes`: the model of ONE block (include/neo_hip.h).
+    levels == [] (partitions <= head): the handle runs the ordinary step."""
+    ro, ri = _routes(routes, inputs, outputs)
+    w, wp, nw = _windows(windows)
+    info = _native.MatrixLevelPlanInfo()
+    O, L = max(1, int(outputs)), _native.MATRIX_MAX_LEVELS
+    cuts, off = np.zeros((L, 33), np.int32), np.zeros((L, 64 * O + 1), np.int32)
+    rin, rfirst, rlast = (np.zeros((L, len(ro) + 63 * O), np.int32) for _ in range(3))
+    _native.check(_native.load().neo_hip_matrix_level_plan(int(inputs), int(outputs), int(block_size), int(partitions),
+                                                           _ptr(ro), _ptr(ri), len(ro), wp, nw, int(split_workgroups),
+                                                           ctypes.byref(info), _ptr(cuts), _ptr(off), _ptr(rin),
+                                                           _ptr(rfirst), _ptr(rlast)))
+    levels = []
+    for l in range(info.levels):
+        T, S = info.window[l], info.splits[l]
+        outs = [[[(int(rin[l, k]), int(rfirst[l, k]), int(rlast[l, k])) for k in range(off[l, o * S + s], off[l, o * S + s + 1])]
+                 for s in range(S)] for o in range(int(outputs))]
+        levels.append({"window": T, "first": info.first[l], "last": info.last[l], "splits": S,
+                       "workgroups": info.workgroups[l], "runs": info.runs[l],
+                       "part_cuts": [int(c) for c in cuts[l, :T + 1]], "outputs": outs,
+                       "filter_rows": info.filter_rows[l], "fdl_rows": info.fdl_rows[l]})
+    return {"head": info.head, "levels": levels, "ring_rows": info.ring_rows, "chunks": info.chunks,
+            "head_splits": info.head_splits, "head_out_tile": info.head_out_tile,
+            "head_filter_rows": info.head_filter_rows, "head_fdl_rows": info.head_fdl_rows,
+            "partial_bytes": info.partial_bytes, "head_bank_bytes": info.head_bank_bytes, "bytes": info.bytes}
+
+
 def _fade_curve(curve) -> int:
     if isinstance(curve, str):
         if curve not in MatrixConvolver.FADE_CURVES:
@@ -1492,7 +1543,8 @@ class MatrixConvolver:
     UPOLA) convolution of input i with that route's filter. One delay line per input, one inverse
     transform per output (neo_hip_matrix_*, include/neo_hip.h). Whole blocks: one block per step,
     with set_batch(True) up to 32 blocks of a call per pass over the filters, with set_offline(True)
-    windows of 128 blocks by 256-point transforms along the block axis (long filters)."""
+    windows of 128 blocks by 256-point transforms along the block axis (long filters), with
+    set_levels(True) long filters one block per call (the tail of the filter once per window)."""
 
     OPTION_DEFAULTS = {"fused": -1, "split_workgroups": 0, "out_tile": 0}
 
@@ -1599,6 +1651,28 @@ class MatrixConvolver:
         _native.check(_native.load().neo_hip_matrix_offline_info(self._h, ctypes.byref(b), ctypes.byref(g),
                                                                  ctypes.byref(r), ctypes.byref(n)))
         return {"blocks_per_pass": b.value, "segments": g.value, "ring_rows": r.value, "spectra_bytes": n.value}
+
+    def set_levels(self, enable: bool, windows=None, split_workgroups: int = 0) -> None:
+        """Window levels (neo_hip_matrix_set_levels): long filters one block per call. A single step
+        then reads only the head, partitions [0, 2 windows[0]), on every block; each level reads its
+        band of partitions once per window of its length, one window ahead, in equal parts spread
+        over the window's blocks (matrix_level_plan has the plan). windows None: (8, 32);
+        split_workgroups: the workgroup target of a part, 0 = automatic. May be turned on or off at
+        any time between calls; blocks that ran another way (batched or offline passes, a fade, the
+        mode off) are made up for by priming at the next level step, with the same bits."""
+        w, wp, nw = _windows(windows)
+        _native.check(_native.load().neo_hip_matrix_set_levels(self._h, int(bool(enable)), wp, nw, int(split_workgroups)))
+
+    def levels_info(self) -> dict:
+        """enabled, head (partitions of the ordinary step), levels (a list of window, first, last,
+        splits; empty without a filter or with partitions <= head: the ordinary step runs), ring_rows,
+        primed (the slabs are current), partial_bytes and head_bank_bytes as planned."""
+        d = _native.MatrixLevelsDesc()
+        _native.check(_native.load().neo_hip_matrix_levels_info(self._h, ctypes.byref(d)))
+        levels = [{"window": d.window[l], "first": d.first[l], "last": d.last[l], "splits": d.splits[l]}
+                  for l in range(d.levels)]
+        return {"enabled": bool(d.enabled), "head": d.head, "levels": levels, "ring_rows": d.ring_rows,
+                "primed": bool(d.primed), "partial_bytes": d.partial_bytes, "head_bank_bytes": d.head_bank_bytes}
 
     # -- processing ---------------------------------------------------------
     def process(self, x, stream: int = 0):
