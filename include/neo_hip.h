@@ -87,8 +87,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.9.0: crossfaded live filter updates on matrix handles (neo_hip_matrix_update_filter,
  *        neo_hip_matrix_update_impulse, neo_hip_matrix_fade_info, neo_hip_matrix_fade_gains).
  * 0.10.0: window levels on matrix handles, long filters one block per call (neo_hip_matrix_set_levels,
- *        neo_hip_matrix_levels_info, neo_hip_matrix_level_plan). */
-#define NEO_HIP_VERSION 1000 /* 0.10.0 */
+ *        neo_hip_matrix_levels_info, neo_hip_matrix_level_plan).
+ * 0.11.0: staggered level windows (neo_hip_upols_opts gains windows at its end: 11 ints;
+ *        neo_hip_upols_stagger_plan). */
+#define NEO_HIP_VERSION 1100 /* 0.11.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -169,6 +171,13 @@ typedef struct neo_hip_upols_opts {
                              transform kept in registers for the window's products), 2 two steps (the fresh
                              transform stored to its slot, read back with the products one step later: half the
                              chain per step); step groups always run 1 */
+    int windows;          /* streaming levels with step groups: 0 auto, 1 aligned (every slice of a level's window
+                             shares the window's start, bands from 2 T), 2 staggered (a level of window T >= 4 G and
+                             the far level are cut into T / G classes of channels, each with a window phase of its
+                             own: bands from T + 4 G, fewer rows per step; needs step groups and the far level's
+                             stored form; no latency mode). Auto: staggered where the step group
+                             is chosen automatically and channels x block / 16 >= 65536, aligned everywhere else
+                             (a group's members too) */
 } neo_hip_upols_opts;
 NEO_HIP_API int neo_hip_upols_create_ex(int channels, int block, int partitions, int device, int method,
                                         const neo_hip_upols_opts* opts, neo_hip_upols** h);
@@ -357,6 +366,23 @@ NEO_HIP_API int neo_hip_upols_level_plan(int partitions, int* a0, int* nlevels, 
  * the cycle into loads[loads_cap]. uniform != 0: equal parts and no offsets (for comparison). */
 NEO_HIP_API int neo_hip_upols_part_plan(int channels, int block, int partitions, int step_group, int uniform, int* phi,
                                         int* cycle, int* cuts, int cuts_cap, int* ncuts, double* loads, int loads_cap);
+/* The staggered plan (neo_hip_upols_opts.windows = 2) of a (channels, block, partitions) convolver
+ * with step groups of step_group blocks (0: the automatic group; 2, 4 or 8) and far window group
+ * far_group (0: auto), no device needed; for tests. Per level l < *nlevels its window T[l], band
+ * [a[l], b[l]) and staggered[l] (1: T >= 4 G, cut into T / G classes of channels, band from T + 4 G; 0: as in
+ * the aligned plan); *far_a, the far level's first partition, and its *nseg segments of 128;
+ * *even_share, the even classes' share of a pair of classes in 1/1024ths (the far level's; every
+ * level has its own, chosen so that odd and even groups carry the same bytes). Then for every staggered
+ * level in level order, and last for the far level (if any), T / G + 1 channel cuts into
+ * cuts[cuts_cap] (*ncuts = how many there are in all): class k = channels [cut[k], cut[k + 1]) is
+ * computed in the background launches of the groups g = k mod T / G, for its window that starts at
+ * block (g + 2) G -- offs[] holds that start modulo T beside the class's first cut (0 beside a
+ * list's last cut). The far level's phase 1 of a class runs two groups before. loads[loads_cap]: the
+ * predicted background bytes per group of the far window (*nloads = 128 / G). */
+NEO_HIP_API int neo_hip_upols_stagger_plan(int channels, int block, int partitions, int step_group, int far_group,
+                                           int* nlevels, int* T, int* a, int* b, int* staggered, int* far_a, int* nseg,
+                                           int* even_share, int* cuts, int* offs, int cuts_cap, int* ncuts, double* loads,
+                                           int loads_cap, int* nloads);
 /* Paced background work (step groups only; a no-op with one launch per block): enable = 1 issues
  * the step group's background launch in G pieces, one per call, and every block waits for the
  * piece of the call before it; enable = 2 issues it in two pieces, at the group's calls 0 and
@@ -395,6 +421,9 @@ NEO_HIP_API int neo_hip_upols_get_far_form(neo_hip_upols* h, int* form);
 /* steps per background launch of the streaming levels' slices (neo_hip_upols_opts.step_group or
  * the automatic choice): 1 = one launch per step */
 NEO_HIP_API int neo_hip_upols_get_step_group(neo_hip_upols* h, int* steps);
+/* the level windows the handle runs: 1 aligned, 2 staggered (neo_hip_upols_opts.windows or the
+ * automatic choice) */
+NEO_HIP_API int neo_hip_upols_get_windows(neo_hip_upols* h, int* windows);
 /* make `stream` wait (device-side, no host wait) for every background slice launch of the
  * handle's step groups issued so far; a no-op with one launch per step. Outputs never need
  * it (a block's launch already waits for the slices it reads); a caller bracketing steps with

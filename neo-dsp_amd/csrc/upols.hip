@@ -531,13 +531,13 @@ int create_convolver(int channels, int block, int partitions, int device, bool o
                      const neo_hip_upols_opts* opt, neo_hip_upols** out, hipStream_t borrow = nullptr)
 {
     if (!out) return fail(NEO_HIP_EINVAL, "handle pointer is null");
-    const neo_hip_upols_opts o = opt ? *opt : neo_hip_upols_opts{-1, 0, 0, 0, -1, -1, 0, 0, 0, 0};
+    const neo_hip_upols_opts o = opt ? *opt : neo_hip_upols_opts{-1, 0, 0, 0, -1, -1, 0, 0, 0, 0, 0};
     if (o.fused < -1 || o.fused > 1 || o.levels < -1 || o.levels > 1 || o.far_level < -1 || o.far_level > 2 ||
         o.split_workgroups < 0 ||
         (o.batch_blocks && (o.batch_blocks < 2 || o.batch_blocks > kMaxBatch || (o.batch_blocks & (o.batch_blocks - 1)))) ||
         o.batch_bins < 0 || o.batch_bins > 2 || o.far_group < 0 || o.far_group > 4 || o.toep_split < 0 || o.toep_split > 2 ||
         (o.step_group != 0 && o.step_group != 1 && o.step_group != 2 && o.step_group != 4 && o.step_group != 8) ||
-        o.far_phase2 < 0 || o.far_phase2 > 2)
+        o.far_phase2 < 0 || o.far_phase2 > 2 || o.windows < 0 || o.windows > 2)
         return fail(NEO_HIP_EINVAL, "invalid convolver options");
     *out = nullptr;
     if (channels < 1) return fail(NEO_HIP_EINVAL, "channels must be >= 1");
@@ -557,6 +557,21 @@ int create_convolver(int channels, int block, int partitions, int device, bool o
     h->f2mode = o.far_phase2;
     h->sg = o.step_group ? o.step_group : step_group_for(channels, block, partitions);
     h->bg_pad = bg_pad_for(channels, block);
+    // staggered level windows (plan_levels_stag): on request with any step group of 2, 4 or 8 and
+    // the far level's stored form; automatic only from kStaggerUnits 16-column units with an
+    // automatic step group, the one size measured to gain (c5full, 65536 units: 107.4 -> 99.4 us per
+    // step; DESIGN 6, profiles/stagger_ab.json). Smaller handles and a group's members (borrow)
+    // keep the aligned plan.
+    {
+        const bool can = h->sg > 1 && o.far_level != 0 && o.far_level != 2 && !v2 && block <= 1024;
+        if (o.windows == 2 && !can) {
+            delete h;
+            return fail(NEO_HIP_EINVAL, "staggered windows take step groups and the far level's stored form");
+        }
+        if (o.windows == 2 ||
+            (o.windows == 0 && can && !o.step_group && !borrow && int64_t(channels) * (block / 16) >= kStaggerUnits))
+            plan_levels_stag(partitions, channels, block, h->sg, o.far_group, h->lv);
+    }
     // the far level's form: the stored spectra (phase 1 + 2) by default; recomputed every window
     // (far2r_role) on request -- fewer bytes (C5: 15 instead of 23 rows per column and step) but
     // 2 nseg + 1 transforms per unit and window: same-box A/B with step groups, stored vs

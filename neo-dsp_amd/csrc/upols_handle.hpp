@@ -151,8 +151,24 @@ struct level_plan {
     int a0 = 1;                      // the block step takes partitions [0, a0)
     int n = 0;                       // Toeplitz levels
     int T[kLvToep] = {}, a[kLvToep] = {}, b[kLvToep] = {};  // window (blocks) and partition band [a, b) per level
-    int nseg = 0;                    // far segments of kFarT partitions from kFarA (0: no far level)
+    int nseg = 0;                    // far segments of kFarT partitions from farA (0: no far level)
+    int farA = kFarA;                // the far level's first partition (staggered windows: plan_levels_stag)
+    int stag = 0;                    // staggered windows: the step group G they are planned for (0: aligned)
 };
+
+// Staggered windows (upols_levels.hip, plan_levels_stag): a level of window T >= 4 G (and the far
+// level) is cut into T / G classes of channels, class k computed in the background launches of the
+// groups g = k mod T / G for the window starting at block (g + 2) G, so its band starts at T + 4 G.
+// A channel's class: its position in 1/1024ths of a pair of far classes is (c M) >> 20 with
+// M = ((64 / G) << 30) / C, shifted right by log2(128 / T) for a level of window T; the even class
+// of a pair takes the first ef of its 1024 parts.
+__host__ __device__ inline int stag_class(unsigned long long M, int ef, int c, int shift)
+{
+    const int p = int((static_cast<unsigned long long>(c) * M) >> 20) >> shift;
+    return 2 * (p >> 10) + ((p & 1023) >= ef ? 1 : 0);
+}
+// windows of class k start where (n + phi) mod T = 0
+__host__ __device__ inline int stag_phi(int T, int G, int k) { return (-(k + 2) * G) & (T - 1); }
 }  // namespace neo_hip
 
 struct neo_hip_upols {
@@ -190,6 +206,10 @@ struct neo_hip_upols {
     int lv_cyc = 1;
     std::vector<int> lv_cut[neo_hip::kLvToep];
     std::vector<int> fv_cut;  // step groups: the far slices' first units (ns + 1 cuts; empty: equal slices)
+    // staggered windows (lv.stag): the first channel of every class per level and of the far level
+    // (T / G + 1 cuts), the even classes' share of a pair in 1/1024ths per level and of the far level
+    std::vector<int> st_cut[neo_hip::kLvToep], st_fcut;
+    int st_ef[neo_hip::kLvToep] = {}, st_fef = 512;
     neo_hip::cf* fv_hf = nullptr;   // far segment spectra [C][nseg][256][B]
     neo_hip::cf* fv_xf = nullptr;   // far FDL row-pair spectra, ring of nseg slots [C][nseg][256][B]
     neo_hip::cf* fv_ff = nullptr;   // far field [2][C][128][B]
@@ -443,6 +463,9 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
                   float* snap = nullptr);
 // far: -1 auto (= 1), 0 the big Toeplitz level, 1 the far level
 void plan_levels(int P, level_plan& lp, int far = -1);
+// the staggered plan for step groups of G blocks (far_k: the forced far window group, 0 auto)
+void plan_levels_stag(int P, int C, int B, int G, int far_k, level_plan& lp);
+constexpr int64_t kStaggerUnits = 65536;  // 16-column units from which windows = 0 (auto) staggers (upols.hip)
 // the block role of streaming step n (FDL ring row w) again for channel c alone, with another
 // input block (upols_group.hip: a speculatively stepped channel whose caller's block differed);
 // the step's slabs and far field must not have been overwritten since

@@ -86,6 +86,58 @@ void plan_levels(int P, level_plan& lp, int far)
     }
 }
 
+// Staggered windows (step groups of G blocks). In the aligned plan every slice of a window shares
+// the window's start, so the band starts at 2 T: a slice computed early in the previous window
+// waits up to T - 1 steps for its first read. Here a level of window T >= 4 G is cut into T / G
+// classes of channels and class k has a window phase of its own: it is computed whole in the
+// background launch of group g = k mod T / G, for the window that starts at block s = (g + 2) G.
+// That launch is guaranteed the FDL rows before (g - 2) G = s - 4 G (an even group's launch only
+// follows its odd predecessor, which waited for the blocks before the group before it) and is
+// first waited for at block (g + 2) G (launch_levels), and the window's rows s + j - p end at
+// s + T - 1 - a: the band may start at a = T + 4 G. The far level likewise (phase 1 of a class two
+// groups before its phase 2, whose fresh row pair ends at s - F + 127): F >= 128 + 4 G. A class's
+// slab buffer is rewritten T / G groups after it was written, T - 2 G >= 2 G steps after the block
+// launch that waited for it was issued.
+// G = 4: [8, 16) [16, 32) as aligned, T = 16 [32, 48), T = 32 [48, F), far from F in [144, 240]:
+// the F with the fewest bytes by the model of DESIGN 5 (the T = 32 band's 2 (F - 48) + 63 rows per
+// 32 steps against the far level's 512 (nseg - 1) / K + 256 (K + 3) + 384 per 128), the fewer
+// segments where two are within half a percent.
+static int far_group_auto(int C, int B, int ns);
+constexpr int kT32BandMax = 192;  // the T = 32 level's LDS tile (kT32Band)
+
+void plan_levels_stag(int P, int C, int B, int G, int far_k, level_plan& lp)
+{
+    lp = level_plan{};
+    lp.stag = G;
+    lp.a0 = std::min(P, kLvA0);
+    int A[5];
+    for (int l = 0; l < 4; ++l) A[l] = (kLvT0 << l) > 4 * G ? (kLvT0 << l) + 4 * G : 2 * (kLvT0 << l);
+    const int Fmin = kFarT + 4 * G, Fmax = A[3] + kT32BandMax;
+    int F = P, nseg = 0;
+    if (P > Fmin) {
+        double best = 1e300;
+        for (int ns = std::max(1, (P - Fmax + kFarT - 1) / kFarT); ns <= (P - Fmin + kFarT - 1) / kFarT; ++ns) {
+            const int f = std::max(Fmin, P - kFarT * ns), K = ns < 2 ? 1 : (far_k ? far_k : far_group_auto(C, B, ns));
+            const double rows = (2.0 * (f - A[3]) + 63) / 32 + (512.0 * (ns - 1) / K + 256.0 * (K + 3) + 384) / kFarT;
+            if (rows < best * 0.995) {
+                best = rows;
+                F = f;
+                nseg = ns;
+            }
+        }
+    }
+    A[4] = F;
+    for (int l = 0; l < 4; ++l) {
+        if (P <= A[l]) break;
+        lp.T[lp.n] = kLvT0 << l;
+        lp.a[lp.n] = A[l];
+        lp.b[lp.n] = std::min(P, A[l + 1]);
+        ++lp.n;
+    }
+    lp.farA = F;
+    lp.nseg = nseg;
+}
+
 // ---------------------------------------------------------------------------------------
 // device helpers
 
@@ -131,11 +183,18 @@ struct slice_args {
     int64_t scs[kLvToep];   // channel strides
     const cf* ff;           // far field row of this block, channel 0 (null: no far level)
     int64_t fcs;
+    // staggered windows (stag = G, else 0): the row depends on the channel's class (stag_class, stag_phi).
+    // A level with ssh[l] >= 0 (the far level: fsh) gives its slab's base in sl[l] (ff) and the block
+    // role adds the buffer and row of step snm = n mod 256 in the class's window
+    int stag, snm, fsh, fef;
+    int ssh[kLvToep], sef[kLvToep];  // per level: position shift, the even classes' share (1/1024ths)
+    unsigned long long sM;
     // Toeplitz roles
     int ntp;
     toep_arg tp[kLvToep];
     // far level (16-column units), common
     int M, nseg, fnfresh, P;
+    int fA;       // the far level's first partition (level_plan::farA)
     int64_t fsc;  // segment / row-pair spectra channel stride (spec_cs; M = nseg slots)
     const cf* hf;
     cf* xf;
@@ -162,9 +221,10 @@ struct slice_args {
     int bid0;     // paced background pieces: the first workgroup of the launch this piece runs
 };
 
-// the T = 32 Toeplitz level stages its band in LDS: filter rows [64, 256) and the FDL rows
-// they meet, 16 columns each, column-major with padded strides
-constexpr int kT32Band = 192;                                       // [64, 256)
+// the T = 32 Toeplitz level stages its band in LDS: the filter rows of its band and the FDL rows
+// they meet, 16 columns each, column-major with padded strides. The tile holds kT32Band rows:
+// the aligned band [64, 256) fills it, the staggered band [48, F) uses its first F - 48
+constexpr int kT32Band = kT32BandMax;
 constexpr int kFarLds = (16 * 16 * 16 + 2 * 256 + 8 * 256) * int(sizeof(cf));  // far roles: transposes, bin-0 exchange,
                                                                                // twiddles, far2r_role's half pair
 // toep_tile<32, 192>: 53760 B, 3 workgroups per CU (VGPRs allow 3 too; the band in two chunks
@@ -204,7 +264,10 @@ __device__ __forceinline__ void cmac(cf& y, cf h, cf x, bool bin0)
     }
 }
 
-template<int B, bool OLA, bool WT = false>
+// STAG: the block kernel's build for staggered windows (the slab and far-field rows by the channel's
+// class); every other build keeps the aligned rows' code as it was -- the block launches are the
+// latency-bound chain of the 256-channel shapes
+template<int B, bool OLA, bool WT = false, bool STAG = false>
 __device__ __forceinline__ void block_role(const slice_args& a, int c, char* smem)
 {
     using K = upols_cfg<B>;
@@ -272,17 +335,28 @@ __device__ __forceinline__ void block_role(const slice_args& a, int c, char* sme
                 xb[p - 1] = a.fdl[crow + int64_t(r) * a.pstride + k1];
             }
         }
+        // staggered windows: the channel's class per level picks the slab buffer and row
+        // (uniform per workgroup: scalar arithmetic, no loads)
+        auto stag_row = [&](int sh, int ef, int lt, int64_t cs) {  // window T = 1 << lt
+            const int m = a.snm + stag_phi(1 << lt, a.stag, stag_class(a.sM, ef, c, sh));
+            return int64_t((m >> lt) & 1) * a.C * cs + int64_t(m & ((1 << lt) - 1)) * B;
+        };
 #pragma unroll
         for (int l = 0; l < kLvToep; ++l) {
             if (l < a.nsl) {
                 const cf* sr = a.sl[l] + int64_t(c) * a.scs[l];
+                if constexpr (STAG)
+                    if (a.ssh[l] >= 0) sr += stag_row(a.ssh[l], a.sef[l], l + 2, a.scs[l]);
                 sla[l] = sr[k0];
                 slb[l] = sr[k1];
             }
         }
         if (a.ff) {
-            sla[kLvToep] = a.ff[int64_t(c) * a.fcs + k0];
-            slb[kLvToep] = a.ff[int64_t(c) * a.fcs + k1];
+            const cf* fr = a.ff + int64_t(c) * a.fcs;
+            if constexpr (STAG)
+                if (a.fsh >= 0) fr += stag_row(a.fsh, a.fef, 7, a.fcs);
+            sla[kLvToep] = fr[k0];
+            slb[kLvToep] = fr[k1];
         }
     }
     if (tid < 64) {  // wave 0: previous block, window r2c
@@ -959,9 +1033,9 @@ __device__ __forceinline__ void far2a_role(const slice_args& sa, int bid, char* 
     const __amdgpu_buffer_rsrc_t xres = buf_rsrc(sa.xf + int64_t(c) * sa.fsc, int64_t(M) * spec);
     const int vo = int((int64_t(a) * fs + k) * int(sizeof(cf)));
     for (int s = 0; s < s0; ++s) {  // uniform per workgroup (one segment in steady state)
-        // rows tw - (s + 3) 128 + a + 16 n (the ring holds >= kFarRing > 256 rows: one wrap at most)
+        // rows tw - fA - (s + 1) 128 + a + 16 n (the ring holds >= kFarRing > 256 rows: one wrap at most)
         cf x[16];
-        int r0 = (sa.f2tw - (s + 3) * kFarT + a) % sa.ring;
+        int r0 = (sa.f2tw - sa.fA - (s + 1) * kFarT + a) % sa.ring;
         r0 = r0 < 0 ? r0 + sa.ring : r0;
 #pragma unroll
         for (int n = 0; n < 16; ++n) {
@@ -1080,10 +1154,10 @@ __device__ __forceinline__ void far2c_role(const slice_args& sa, int bid, char* 
     const int vo = int((int64_t(a) * fs + k) * int(sizeof(cf)));
     const int ao = (a * 16 + cp) * int(sizeof(cf)), as = 16 * 16 * int(sizeof(cf));  // f = a + 16 i
     auto z0 = [&](int i) { return unit0 && cp == 0 && ((a + 16 * i) & (kFN / 2 - 1)) == 0; };
-    // the fresh row pair: rows tw - 3 128 + a + 16 n (one wrap of the ring at most)
+    // the fresh row pair: rows tw - fA - 128 + a + 16 n (one wrap of the ring at most)
     cf x[16];
     {
-        int r0 = (sa.f2tw - 3 * kFarT + a) % sa.ring;
+        int r0 = (sa.f2tw - sa.fA - kFarT + a) % sa.ring;
         r0 = r0 < 0 ? r0 + sa.ring : r0;
 #pragma unroll
         for (int n = 0; n < 16; ++n) {
@@ -1174,7 +1248,7 @@ __device__ __forceinline__ void far2r_role(const slice_args& sa, int bid, char* 
     f2v acc[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = f2v(0.f);
-    int r0 = (sa.f2tw - 3 * kFarT + a) % sa.ring;  // pair 0's row a (the ring holds > P + 256 rows)
+    int r0 = (sa.f2tw - sa.fA - kFarT + a) % sa.ring;  // pair 0's row a (the ring holds > P + 256 rows)
     r0 = r0 < 0 ? r0 + sa.ring : r0;
     for (int s = 0; s < sa.nseg; ++s) {  // uniform per workgroup
         cf x[16], hv[16];
@@ -1182,7 +1256,7 @@ __device__ __forceinline__ void far2r_role(const slice_args& sa, int bid, char* 
         for (int n = 0; n < 8; ++n) {
             const int r = r0 + 16 * n >= sa.ring ? r0 + 16 * n - sa.ring : r0 + 16 * n;
             x[n] = buf_ld(fres, int(int64_t(r) * sa.pstride * int(sizeof(cf))) + ko, 0);
-            const int p = (s + 2) * kFarT + a + 16 * n;
+            const int p = sa.fA + s * kFarT + a + 16 * n;
             hv[n] = p < sa.P ? buf_ld(hres, int(int64_t(p) * sa.pstride * int(sizeof(cf))) + ko, 0) : cf{0.f, 0.f};
             hv[n + 8] = cf{0.f, 0.f};
         }
@@ -1372,7 +1446,7 @@ __device__ __forceinline__ bool toep_level(const slice_args& a, int& bid, char* 
         bid -= ta.nwg;
         return false;
     }
-    static_assert(kLvT0 == 4 && kLvToep == 5, "level slots: windows 4, 8, 16, 32 (bands 2T, 2T, 2T, 6T), 128");
+    static_assert(kLvT0 == 4 && kLvToep == 5, "level slots: windows 4, 8, 16, 32, 128");
     if constexpr (L == 0) {  // T = 4, 8: a lane takes its column's whole band in registers
         if (NEO_ROLES & 2) toep_role<4, 8, 1, 1>(a, ta, bid, smem);
     } else if constexpr (L == 1) {
@@ -1427,7 +1501,7 @@ constexpr int step_wpe() { return B > 512 ? 2 : (KMAX == 1 ? NEO_RAW_WPE : NEO_S
 #endif
 // PART: 0 every role (one launch per step), 1 the block role alone, 2 every role but the block
 // (step groups: the block of each call and the level slices of G calls in launches of their own)
-template<int B, bool OLA, int KMAX, int PART = 0>
+template<int B, bool OLA, int KMAX, int PART = 0, bool STAG = false>
 __device__ __forceinline__ int lvl_roles(const slice_args& a, char* smem)
 {
     int bid = int(blockIdx.x) + a.bid0;
@@ -1458,7 +1532,7 @@ __device__ __forceinline__ int lvl_roles(const slice_args& a, char* smem)
             bid -= a.nblk;
             return false;
         }
-        if (NEO_ROLES & 1) block_role<B, OLA>(a, a.blk_c0 + bid, smem);
+        if (NEO_ROLES & 1) block_role<B, OLA, false, STAG>(a, a.blk_c0 + bid, smem);
         return true;
     };
     if constexpr (PART == 1) {  // the block and the levels too short for the background (T < 2 G)
@@ -1566,12 +1640,12 @@ __device__ __forceinline__ void tl_record(const slice_args& a, F roles)
 #define NEO_TL_ROLES(WG, EXPR) (void)(EXPR)
 #endif
 
-template<int B, bool OLA>
+template<int B, bool OLA, bool STAG = false>
 __global__ __launch_bounds__(lstep_cfg<B>::WG) __attribute__((amdgpu_waves_per_eu(NEO_BLOCK_WPE))) void k_lvl_block(slice_args a)
 {
     __shared__ __attribute__((aligned(16))) char smem[block_lds<B>()];
     if constexpr (NEO_BLOCK_PRIO > 0) __builtin_amdgcn_s_setprio(NEO_BLOCK_PRIO);
-    NEO_TL_ROLES(lstep_cfg<B>::WG, (lvl_roles<B, OLA, 2, 1>(a, smem)));
+    NEO_TL_ROLES(lstep_cfg<B>::WG, (lvl_roles<B, OLA, 2, 1, STAG>(a, smem)));
 }
 
 // step groups: every role but the block for the slices of G steps (the background stream);
@@ -1593,10 +1667,12 @@ __global__ __launch_bounds__(lstep_cfg<B>::WG) __attribute__((amdgpu_waves_per_e
 // Segment spectra (grid C x NSEG x B/16): hf[c][s][f][k] = DFT256 over r < 128 of
 // H[c][128 (s + seg0) + r][k] (zero past P); packed bin 0 (two real sequences, DC and Nyquist)
 // in the real-FFT packing of far_role (pack_bin0). seg0 = 2: the far level's segments (p >=
-// 256); 0: every segment (offline windows, k_off_mac).
+// 256); 0: every segment (offline windows, k_off_mac); p0: partitions before segment seg0
+// (staggered windows: the far level from p0 = F, seg0 = 0).
 __global__ __launch_bounds__(256) void k_lvf_filter(const cf* __restrict__ H, cf* __restrict__ hf,
                                                     const cf* __restrict__ twg, int B, int P, int nseg,
-                                                    int64_t cstride, int64_t pstride, int seg0, int64_t hcs)
+                                                    int64_t cstride, int64_t pstride, int seg0, int64_t hcs,
+                                                    int p0 = 0)
 {
     __shared__ cf lds[16 * 16 * 16];
     __shared__ cf z[kFN];
@@ -1609,7 +1685,7 @@ __global__ __launch_bounds__(256) void k_lvf_filter(const cf* __restrict__ H, cf
     cf v[16];
 #pragma unroll
     for (int n2 = 0; n2 < 16; ++n2) {
-        const int r = a + 16 * n2, p = (s + seg0) * kFarT + r;
+        const int r = a + 16 * n2, p = p0 + (s + seg0) * kFarT + r;
         v[n2] = (r < kFarT && p < P) ? H[int64_t(c) * cstride + int64_t(p) * pstride + k] : cf{0.f, 0.f};
     }
     col_fft<-1, 16>(v, lds, tw, a, cp, true);
@@ -1853,6 +1929,7 @@ static slice_args base_args(const upols_t* h)
         a.xf = h->fv_xf;
         a.twf = h->fv_tw;
         a.P = h->P;
+        a.fA = h->lv.farA;
     }
     return a;
 }
@@ -1896,13 +1973,15 @@ static int launch_step_kernel(const upols_t* h, const slice_args& a_in, hipStrea
     // kFarGroupUnits), else the build for any group
     const bool pairs = a.fK <= 2, raw = h->far_raw;
     if (part == 1) {
+#define NEO_BLK(OL, ST)                                                                                           \
+    NEO_UPOLS_DISPATCH(h->B, if constexpr (BB <= 1024) hipLaunchKernelGGL((k_lvl_block<BB, OL, ST>), dim3(grid), \
+                                                                         dim3(lstep_cfg<BB>::WG), 0, s, a))
         if (h->ola) {
-            NEO_UPOLS_DISPATCH(h->B, if constexpr (BB <= 1024) hipLaunchKernelGGL((k_lvl_block<BB, true>), dim3(grid),
-                                                                                  dim3(lstep_cfg<BB>::WG), 0, s, a))
+            if (a.stag) NEO_BLK(true, true) else NEO_BLK(true, false)
         } else {
-            NEO_UPOLS_DISPATCH(h->B, if constexpr (BB <= 1024) hipLaunchKernelGGL((k_lvl_block<BB, false>), dim3(grid),
-                                                                                  dim3(lstep_cfg<BB>::WG), 0, s, a))
+            if (a.stag) NEO_BLK(false, true) else NEO_BLK(false, false)
         }
+#undef NEO_BLK
     } else if (part == 2) {
         // 1 KB of dynamic LDS holds the slices kernel to two workgroups per CU (three by its 53.8 KB
         // of static LDS and 149 VGPRs), leaving room for block workgroups beside it: where the
@@ -2129,6 +2208,88 @@ static void part_plan(const part_level* lv, int nl, int G, int64_t FU, int ns, d
 
 static int64_t toep_units(const upols_t* h, int T);
 static bool block_level(const upols_t* h, int T);
+static int far_group(const upols_t* h);
+
+// staggered windows: level l has classes of its own (plan_levels_stag)
+static bool stag_level(const level_plan& lp, int l) { return lp.stag && lp.T[l] >= 4 * lp.stag; }
+static bool stag_far(const level_plan& lp) { return lp.stag && lp.nseg; }
+static int log2i(int v) { return v <= 1 ? 0 : 1 + log2i(v >> 1); }
+static unsigned long long stag_mul(const upols_t* h) { return ((64ull / unsigned(h->lv.stag)) << 30) / unsigned(h->C); }
+
+// The staggered levels' classes: every background launch carries one class of every staggered
+// level, phase 2 of one far class and phase 1 of the next, the same work in every group -- but the
+// aligned levels of window 2 G ride on the odd groups alone (X bytes per two groups). Classes come
+// in pairs of an even and an odd one (class parity = group parity of its Toeplitz slice and both
+// its far phases), so the even classes take the share e / 2 of every pair with e = 1 + X / (2 D),
+// D the staggered bytes per group: both parities then carry the same bytes. Classes are whole
+// channels, so the far level (the most classes) takes its share first and every level after it
+// the rest that the rounding of those before it left.
+static void stag_classes(upols_t* h, std::vector<double>* loads)
+{
+    const level_plan& lp = h->lv;
+    const int G = lp.stag, C = h->C;
+    const double col = double(h->B) * 8;  // bytes of one row of one channel
+    double X = 0, St = 0, c1 = 0, c2 = 0;
+    for (int l = 0; l < lp.n; ++l) {
+        const double wb = col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);  // per channel and window
+        if (stag_level(lp, l)) St += wb * G / lp.T[l];
+        else if (!block_level(h, lp.T[l]) && lp.T[l] == 2 * G) X += wb;
+    }
+    if (lp.nseg) {
+        const int K = far_group(h);
+        c1 = col * (256.0 * 2 * (lp.nseg - 1) / K + 256) * G / kFarT;
+        c2 = col * (256.0 * (3 + K - 1) + 128 + 256) * G / kFarT;
+    }
+    double Drest = St + c2 + c1, Xrest = X;  // what the levels not yet cut can still move
+    const unsigned long long M = stag_mul(h);
+    auto cuts = [&](int T, double Dl, std::vector<int>& cut) {
+        const int ncls = T / G, sh = log2i(kFarT / T);
+        const double e = Drest > 0 ? std::max(0.5, std::min(1.5, 1.0 + Xrest / (2.0 * Drest))) : 1.0;
+        const int ef = int(std::lround(512.0 * e));
+        cut.assign(size_t(ncls) + 1, C);
+        cut[0] = 0;
+        for (int c = C - 1; c >= 0; --c) {
+            const int k = stag_class(M, ef, c, sh);
+            for (int j = k; j >= 1 && cut[size_t(j)] > c; --j) cut[size_t(j)] = c;  // first channel of class >= j
+        }
+        int even = 0;
+        for (int k = 0; k < ncls; k += 2) even += cut[size_t(k) + 1] - cut[size_t(k)];
+        Xrest -= (4.0 * even / C - 2.0) * Dl;  // the share the whole channels gave
+        Drest -= Dl;
+        return ef;
+    };
+    h->st_fcut.clear();
+    h->st_fef = 512;
+    if (lp.nseg) h->st_fef = cuts(kFarT, c1 + c2, h->st_fcut);
+    for (int l = lp.n - 1; l >= 0; --l) {
+        h->st_cut[l].clear();
+        h->st_ef[l] = 512;
+        if (stag_level(lp, l))
+            h->st_ef[l] = cuts(lp.T[l], col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1) * G / lp.T[l], h->st_cut[l]);
+    }
+    if (loads) {  // predicted background bytes per group over the far window, from the integer cuts
+        const int cyc = kFarT / G;
+        loads->assign(size_t(cyc), 0.0);
+        for (int g = 0; g < cyc; ++g) {
+            double& L = (*loads)[size_t(g)];
+            for (int l = 0; l < lp.n; ++l) {
+                const double wb = col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);
+                if (stag_level(lp, l)) {
+                    const int k = g % (lp.T[l] / G);
+                    L += wb * (h->st_cut[l][size_t(k) + 1] - h->st_cut[l][size_t(k)]);
+                } else if (!block_level(h, lp.T[l])) {  // aligned: equal parts at the window's groups 1 .. T / G - 1
+                    const int Tg = lp.T[l] / G, j = ((g * G + part_phi(lp.T[l], G, true)) % lp.T[l]) / G;
+                    if (j >= 1) L += wb * C / (Tg - 1);
+                }
+            }
+            if (lp.nseg) {
+                const int k2 = g % cyc, k1 = (g + 2) % cyc;
+                L += c2 * kFarT / G * (h->st_fcut[size_t(k2) + 1] - h->st_fcut[size_t(k2)]);
+                L += c1 * kFarT / G * (h->st_fcut[size_t(k1) + 1] - h->st_fcut[size_t(k1)]);
+            }
+        }
+    }
+}
 
 // the handle's plan (lvl_prime): levels, far slices and their bytes as bench.algorithmic_bytes
 // counts them
@@ -2142,11 +2303,11 @@ static void plan_handle_parts(upols_t* h, std::vector<double>* loads = nullptr, 
         toep_geom(h, lp.T[l], JH, UPW);
         pl[l].T = lp.T[l];
         pl[l].UPW = UPW;
-        pl[l].bg = h->sg > 1 && !h->persist && !block_level(h, lp.T[l]);  // latency mode: its own schedule
+        pl[l].bg = h->sg > 1 && !h->persist && !block_level(h, lp.T[l]) && !stag_level(lp, l);  // latency mode: its own schedule
         pl[l].U = toep_units(h, lp.T[l]);
         pl[l].wbytes = CB * 8 * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);
     }
-    const int ns = h->sg > 1 && !h->persist && lp.nseg ? far_nslices(h) : 0;
+    const int ns = h->sg > 1 && !h->persist && lp.nseg && !lp.stag ? far_nslices(h) : 0;
     const int64_t FU = far_units(h);
     double c1 = 0, c2 = 0;  // bytes per far unit (16 columns) of phase 1 and 2 per window
     if (ns) {
@@ -2158,7 +2319,9 @@ static void plan_handle_parts(upols_t* h, std::vector<double>* loads = nullptr, 
             c2 = 16.0 * 8 * (256.0 * (3 + K - 1) + 128 + 256);       // fresh pair, products, field, sums in
         }
     }
-    part_plan(pl, lp.n, h->sg, FU, ns, c1, c2, h->far_raw, balance, h->lv_phi, h->lv_cyc, h->lv_cut, h->fv_cut, loads);
+    part_plan(pl, lp.n, h->sg, FU, ns, c1, c2, h->far_raw, balance, h->lv_phi, h->lv_cyc, h->lv_cut, h->fv_cut,
+              lp.stag ? nullptr : loads);
+    if (lp.stag) stag_classes(h, loads);
 }
 
 // The block role of step n (block t0 + n at FDL ring row w) for the channels [c0, c0 + nc): its
@@ -2178,14 +2341,23 @@ static void block_part(const upols_t* h, int64_t n, int w, int c0, int nc, const
     a.twg = h->tw;
     a.w = w;
     a.a0 = lp.a0;
+    if (lp.stag) {  // the block role picks the row by the channel's class
+        a.stag = lp.stag;
+        a.sM = stag_mul(h);
+        a.fef = h->st_fef;
+        a.snm = int(n % (2 * kFarT));
+    }
     for (int l = 0; l < lp.n; ++l) {
         const int T = lp.T[l];
         const int64_t m = n + h->lv_phi[l];  // window m / T, its row m mod T
-        a.sl[a.nsl] = h->lv_slab[l] + (m / T & 1) * C * slab_cs(T, B) + (m % T) * B;
+        a.ssh[a.nsl] = stag_level(lp, l) ? log2i(kFarT / T) : -1;
+        a.sef[a.nsl] = h->st_ef[l];
+        a.sl[a.nsl] = stag_level(lp, l) ? h->lv_slab[l] : h->lv_slab[l] + (m / T & 1) * C * slab_cs(T, B) + (m % T) * B;
         a.scs[a.nsl++] = slab_cs(T, B);
     }
     if (lp.nseg) {
-        a.ff = h->fv_ff + (n / kFarT & 1) * C * ff_cs(B) + (n % kFarT) * B;
+        a.fsh = lp.stag ? 0 : -1;
+        a.ff = lp.stag ? h->fv_ff : h->fv_ff + (n / kFarT & 1) * C * ff_cs(B) + (n % kFarT) * B;
         a.fcs = ff_cs(B);
     }
 }
@@ -2294,13 +2466,30 @@ static void block_levels(const upols_t* h, int64_t n, int w, slice_args& a)
 // in T / G - 1 parts at the steps t_W + G j, j = 1 .. T / G - 1 (part j - 1; its rows end at t_W - 1),
 // the last due one group before t_{W+1}; the far level's slice q (kFarT / G - 2 of them) runs
 // phase 1 at group q + 1 and phase 2 (2a and 2b in one workgroup) at group q + 2 of the window before.
+// Staggered windows (plan_levels_stag): the launch of group g = n0 / G carries class g mod T / G of
+// every staggered level, whole, for the window starting at s = n0 + 2 G; of the far level phase 2
+// of class g mod 128 / G for its window starting at s and phase 1 of the class after the next, whose
+// window starts two groups later (a class's two phases in groups of one parity). n0 < 0: the launches before step 0 that priming replays (lvl_prime) --
+// only the staggered roles, and only windows that start after step 0.
 static void slice_part(const upols_t* h, int64_t n0, int w0, slice_args& a)
 {
     const level_plan& lp = h->lv;
     const int G = h->sg;
+    const int64_t g = n0 / G;  // n0 is a multiple of G
     for (int l = 0; l < lp.n; ++l) {
         const int T = lp.T[l], Tg = T / G;
         if (block_level(h, T)) continue;  // in the block launches
+        if (stag_level(lp, l)) {
+            const int64_t s = n0 + 2 * G;
+            if (s <= 0) continue;
+            const int k = int((g % Tg + Tg) % Tg), phi = stag_phi(T, G, k);
+            int JH, UPW;
+            toep_geom(h, T, JH, UPW);
+            const int64_t upc = int64_t(h->B / 16) * JH;  // units per channel
+            toep_slice(h, l, (s + phi) / T, h->st_cut[l][size_t(k)] * upc, h->st_cut[l][size_t(k) + 1] * upc, n0 + phi, w0, a);
+            continue;
+        }
+        if (n0 < 0) continue;
         const int64_t m0 = n0 + h->lv_phi[l], j = (m0 % T) / G, W = m0 / T;  // group j of window W
         if (j < 1) continue;
         const int64_t gw = (W * T - h->lv_phi[l]) / G, cyc = h->lv_cyc;  // window W's first group
@@ -2308,7 +2497,28 @@ static void slice_part(const upols_t* h, int64_t n0, int w0, slice_args& a)
         const int* cut = h->lv_cut[l].data() + size_t(k) * size_t(Tg);  // the window's cuts [0, Tg)
         toep_slice(h, l, W + 1, cut[j - 1], cut[j], m0, w0, a);  // tw from m0: block t_{W+1} = (W + 1) T - phi
     }
-    if (lp.nseg && h->far_raw) {  // recomputed: slice q - 2 of window W whole, at phase 2's time
+    if (stag_far(lp)) {
+        const int nc = kFarT / G, gpc = h->B / 16, K = far_group(h);
+        const int64_t s2 = n0 + 2 * G, s1 = n0 + 4 * G;
+        if (s1 > 0) {  // phase 1 of the class whose phase 2 runs two launches later (the same group parity)
+            const int k = int(((g + 2) % nc + nc) % nc);
+            const int64_t W = (s1 + stag_phi(kFarT, G, k)) / kFarT;
+            a.f1wn = int(W);
+            far1_range(h, a, h->st_fcut[size_t(k)] * gpc, h->st_fcut[size_t(k) + 1] * gpc, K == 1 ? 0 : (W < K ? 2 : 1),
+                       int(W % K));
+        }
+        if (s2 > 0) {  // phase 2, 2a and 2b in one workgroup per unit (far2c_role)
+            const int k = int((g % nc + nc) % nc);
+            const int64_t W = (s2 + stag_phi(kFarT, G, k)) / kFarT;
+            a.f3u0 = h->st_fcut[size_t(k)] * gpc;
+            a.f3nwg = h->st_fcut[size_t(k) + 1] * gpc - a.f3u0;
+            a.f3wn = int(W);
+            a.f2grp = K > 1;
+            a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
+            a.f2tw = ring_add(w0, 2 * G, h->ring);
+            a.f2comb = 1;
+        }
+    } else if (lp.nseg && h->far_raw) {  // recomputed: slice q - 2 of window W whole, at phase 2's time
         const int q = int(n0 % kFarT) / G;
         if (q >= 2 && q - 2 < far_nslices(h)) far_raw_args(h, n0 / kFarT + 1, q - 2, w0, n0, a);
     } else if (lp.nseg) {
@@ -2355,6 +2565,62 @@ int lvl_join(upols_t* h, hipStream_t s)
 // p >= 2T, of H[p] X[t_W + j - p]: rows before t0), the far window's row-pair spectra, partial
 // sums and field (rows t_W - 128 (q + 1) ... + 255 < t0). Then priming is zeroing the level
 // buffers (all of them: a superset of what the two launches write), a fraction of their time.
+// Staggered windows: class k's window 0 (the one that holds step 0) began phi_k steps ago, so the
+// classes prime one by one -- launch pair i takes class i of every staggered level and of the far
+// level (every segment transformed, 2b in the second launch) -- and then the background launches of
+// the groups -3 .. -1 run as they would have (slice_part: the windows that start at steps G .. 3 G,
+// far phase 1 two groups before phase 2), on the caller's stream: every row they read is before
+// step 0.
+static int lvl_prime_stag(upols_t* h, hipStream_t s)
+{
+    const level_plan& lp = h->lv;
+    const int B = h->B, w = h->wpos, G = lp.stag, gpc = B / 16;
+    const int nc = lp.nseg ? kFarT / G : (lp.n ? lp.T[lp.n - 1] / G : 0);
+    for (int i = 0; i < nc; ++i) {
+        slice_args a = base_args(h), f = base_args(h);
+        for (int l = 0; l < lp.n; ++l) {
+            if (!stag_level(lp, l) || i >= lp.T[l] / G) continue;
+            int JH, UPW;
+            toep_geom(h, lp.T[l], JH, UPW);
+            toep_arg& ta = a.tp[l];
+            ta.jh = JH;
+            ta.slab = h->lv_slab[l];
+            ta.cs = slab_cs(lp.T[l], B);
+            ta.T = lp.T[l];
+            ta.a = lp.a[l];
+            ta.b = lp.b[l];
+            ta.tw = ring_add(w, -stag_phi(lp.T[l], G, i), h->ring);
+            ta.u0 = h->st_cut[l][size_t(i)] * gpc * JH;
+            ta.u1 = h->st_cut[l][size_t(i) + 1] * gpc * JH;
+            ta.nwg = (ta.u1 - ta.u0 + UPW - 1) / UPW;
+            a.ntp = l + 1;
+        }
+        const int u0 = lp.nseg ? h->st_fcut[size_t(i)] * gpc : 0, u1 = lp.nseg ? h->st_fcut[size_t(i) + 1] * gpc : 0;
+        if (u1 > u0) {
+            a.fnfresh = lp.nseg;  // every segment transformed
+            a.f1wn = 0;
+            far1_range(h, a, u0, u1, 0, 0);  // zero partial sums (no stored segments)
+            a.f2u0 = u0;
+            a.f2nwg = u1 - u0;
+            a.f2tw = ring_add(w, -stag_phi(kFarT, G, i), h->ring);
+            a.f2wn = 0;
+            f.fnfresh = lp.nseg;
+            f.f3u0 = u0;
+            f.f3nwg = u1 - u0;
+            f.f3wn = 0;
+            f.f3ff = h->fv_ff;
+        }
+        if (int rc = launch_step_kernel(h, a, s)) return rc;
+        if (int rc = launch_step_kernel(h, f, s)) return rc;
+    }
+    for (int g = -3; g < 0; ++g) {
+        slice_args b = base_args(h);
+        slice_part(h, int64_t(g) * G, ring_add(w, int64_t(g) * G, h->ring), b);
+        if (int rc = launch_step_kernel(h, b, s, 2)) return rc;
+    }
+    return NEO_HIP_OK;
+}
+
 static int lvl_prime(upols_t* h, hipStream_t s)
 {
     const level_plan& lp = h->lv;
@@ -2363,7 +2629,7 @@ static int lvl_prime(upols_t* h, hipStream_t s)
     if (lp.nseg && h->fv_dirty && !h->far_raw) {
         const unsigned grid = unsigned(C) * unsigned(lp.nseg) * unsigned(B / 16);
         hipLaunchKernelGGL(k_lvf_filter, dim3(grid), dim3(256), 0, s, h->H, h->fv_hf, h->fv_tw, B, h->P, lp.nseg,
-                           h->cstride, h->pstride, kFarA / kFarT, spec_cs(lp.nseg, B));
+                           h->cstride, h->pstride, 0, spec_cs(lp.nseg, B), lp.farA);
         NEO_HIP_LAUNCH_CHECK();
         h->fv_dirty = false;
     }
@@ -2388,6 +2654,7 @@ static int lvl_prime(upols_t* h, hipStream_t s)
         int JH, UPW;
         toep_geom(h, lp.T[l], JH, UPW);
         toep_arg& ta = a.tp[a.ntp++];
+        if (stag_level(lp, l)) continue;  // class by class (lvl_prime_stag)
         ta.jh = JH;
         ta.slab = h->lv_slab[l];
         ta.cs = slab_cs(lp.T[l], B);
@@ -2414,6 +2681,12 @@ static int lvl_prime(upols_t* h, hipStream_t s)
         a.f3ff = h->fv_ff;
         a.f2tw = w;
         a.f2comb = 2;
+    }
+    if (lp.stag) {
+        if (int rc = launch_step_kernel(h, a, s)) return rc;
+        if (f_any)
+            if (int rc = launch_step_kernel(h, f, s)) return rc;
+        return lvl_prime_stag(h, s);
     }
     if (lp.nseg && !h->far_raw) {  // far window 0: phase 1 and 2a of every unit beside the levels
         const int U = int(far_units(h));
@@ -2817,6 +3090,7 @@ const char* persist_ineligible(const upols_t* h)
         return h->C * h->S > 256 ? "the plain step's channels x splits above 256 workgroups" : nullptr;
     if (h->lv.n && h->lv.T[h->lv.n - 1] == kBigT) return "the 128-block Toeplitz form of the far band (far_level 0)";
     if (h->lv.nseg && h->far_raw) return "the recomputed far level (far_level 2)";
+    if (h->lv.stag) return "staggered level windows (neo_hip_upols_opts.windows)";
     if (h->lv.nseg && far_group(h) > 2) return "a far window group above 2 (neo_hip_upols_opts.far_group)";
     if (h->B > 512) return "blocks above 512 samples with the streaming levels";
     return nullptr;
@@ -3149,6 +3423,61 @@ extern "C" NEO_HIP_API int neo_hip_upols_part_plan(int channels, int block, int 
     return NEO_HIP_OK;
 }
 
+// The staggered plan (neo_hip_upols_opts.windows = 2) of a (channels, block, partitions) convolver
+// with step groups of G blocks (0: the automatic group) and far window group far_group (0: auto),
+// for tests (no device needed): per level its window, band [a, b) and whether it is staggered; the
+// far level's first partition and segments; the even classes' share of a class pair in 1/1024ths
+// (the far level's, else the last level's: each level has its own, the cuts show them);
+// then, for every staggered level in level order and last the far level, T / G + 1 channel cuts
+// (class k = channels [cut[k], cut[k + 1]), computed in the launches of the groups k mod T / G; far
+// phase 1 two groups before) and
+// beside each cut the class's window start modulo T (offs; the entry beside the last cut is 0);
+// the predicted background bytes per group over the far window into loads.
+extern "C" NEO_HIP_API int neo_hip_upols_stagger_plan(int channels, int block, int partitions, int step_group,
+                                                      int far_group, int* nlevels, int* T, int* a, int* b, int* staggered,
+                                                      int* far_a, int* nseg, int* even_share, int* cuts, int* offs,
+                                                      int cuts_cap, int* ncuts, double* loads, int loads_cap, int* nloads)
+{
+    if (channels < 1 || block < 16 || block > 1024 || partitions < 1 || step_group < 0 || far_group < 0 || far_group > 4)
+        return neo_hip::fail(NEO_HIP_EINVAL, "stagger plan: bad shape");
+    neo_hip_upols h{};
+    h.C = channels;
+    h.B = block;
+    h.P = partitions;
+    h.far_k = far_group;
+    h.sg = step_group ? step_group : neo_hip::step_group_for(channels, block, partitions);
+    if (h.sg != 2 && h.sg != 4 && h.sg != 8) return neo_hip::fail(NEO_HIP_EINVAL, "stagger plan: step groups of 2, 4 or 8");
+    neo_hip::plan_levels_stag(partitions, channels, block, h.sg, far_group, h.lv);
+    std::vector<double> ld;
+    neo_hip::plan_handle_parts(&h, &ld, true);
+    const neo_hip::level_plan& lp = h.lv;
+    if (nlevels) *nlevels = lp.n;
+    for (int l = 0; l < lp.n; ++l) {
+        if (T) T[l] = lp.T[l];
+        if (a) a[l] = lp.a[l];
+        if (b) b[l] = lp.b[l];
+        if (staggered) staggered[l] = neo_hip::stag_level(lp, l);
+    }
+    if (far_a) *far_a = lp.farA;
+    if (nseg) *nseg = lp.nseg;
+    if (even_share) *even_share = h.lv.nseg ? h.st_fef : (h.lv.n ? h.st_ef[h.lv.n - 1] : 512);
+    int n = 0;
+    auto put = [&](const std::vector<int>& c, int Tl) {
+        for (size_t k = 0; k < c.size(); ++k, ++n)
+            if (n < cuts_cap) {
+                if (cuts) cuts[n] = c[k];
+                if (offs) offs[n] = k + 1 < c.size() ? (Tl - neo_hip::stag_phi(Tl, h.sg, int(k))) % Tl : 0;
+            }
+    };
+    for (int l = 0; l < lp.n; ++l) put(h.st_cut[l], lp.T[l]);
+    put(h.st_fcut, neo_hip::kFarT);
+    if (ncuts) *ncuts = n;
+    if (nloads) *nloads = int(ld.size());
+    if (loads)
+        for (int g = 0; g < std::min(loads_cap, int(ld.size())); ++g) loads[g] = ld[size_t(g)];
+    return NEO_HIP_OK;
+}
+
 // The far level's phase-1 window group of a handle (far_group: auto or forced by
 // neo_hip_upols_opts.far_group); 0 without a far transform level.
 extern "C" NEO_HIP_API int neo_hip_upols_get_far_group(neo_hip_upols* h, int* windows)
@@ -3162,6 +3491,15 @@ extern "C" NEO_HIP_API int neo_hip_upols_get_far_form(neo_hip_upols* h, int* for
 {
     if (!h || !form) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
     *form = h->lv.nseg ? (h->far_raw ? 2 : 1) : (h->lv.n && h->lv.T[h->lv.n - 1] == neo_hip::kBigT ? 3 : 0);
+    return NEO_HIP_OK;
+}
+
+// 1 aligned level windows, 2 staggered (neo_hip_upols_opts.windows or the automatic choice); 1
+// while the levels are off (the plain step runs, whatever the plan)
+extern "C" NEO_HIP_API int neo_hip_upols_get_windows(neo_hip_upols* h, int* windows)
+{
+    if (!h || !windows) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
+    *windows = h->lv.stag && h->ahead ? 2 : 1;
     return NEO_HIP_OK;
 }
 

@@ -27,7 +27,7 @@ class UpolsOpts(ctypes.Structure):
     _fields_ = [("fused", ctypes.c_int), ("split_workgroups", ctypes.c_int), ("batch_blocks", ctypes.c_int),
                 ("batch_bins", ctypes.c_int), ("levels", ctypes.c_int), ("far_level", ctypes.c_int),
                 ("far_group", ctypes.c_int), ("toep_split", ctypes.c_int), ("step_group", ctypes.c_int),
-                ("far_phase2", ctypes.c_int)]
+                ("far_phase2", ctypes.c_int), ("windows", ctypes.c_int)]
 
 
 class MatrixOpts(ctypes.Structure):
@@ -143,6 +143,10 @@ SIGNATURES = {
                                                                           ctypes.POINTER(ctypes.c_double), _i]),
     "neo_hip_upols_get_far_group": (_i, [_vp, ctypes.POINTER(_i)]),
     "neo_hip_upols_get_step_group": (_i, [_vp, ctypes.POINTER(_i)]),
+    "neo_hip_upols_get_windows": (_i, [_vp, ctypes.POINTER(_i)]),
+    "neo_hip_upols_stagger_plan": (_i, [_i] * 5 + [ctypes.POINTER(_i)] * 10 + [_i, ctypes.POINTER(_i),
+                                                                               ctypes.POINTER(ctypes.c_double), _i,
+                                                                               ctypes.POINTER(_i)]),
     "neo_hip_upols_join_background": (_i, [_vp, _vp]),
     "neo_hip_upols_set_paced": (_i, [_vp, _i]),
     "neo_hip_upols_set_persistent": (_i, [_vp, _i, ctypes.c_double]),
@@ -208,7 +212,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1000 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1100 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -144,6 +144,37 @@ def part_plan(channels: int, block: int, partitions: int, step_group: int, unifo
     return {"phi": list(phi[:len(lp["T"])]), "cycle": cyc.value, "cuts": out, "loads": list(loads[:cyc.value])}
 
 
+def stagger_plan(channels: int, block: int, partitions: int, step_group: int = 0, far_group: int = 0) -> dict:
+    """The staggered plan (options windows = 2) of a convolver with step groups of `step_group`
+    blocks (neo_hip_upols_stagger_plan; no device needed). Returns a0, the levels' T / a / b and
+    `staggered` flags, the far level's first partition `far_a` and `nseg`, `even_share` (1/1024ths
+    of a class pair), `step_group`, and `classes`: {level index, or "far": [(first channel, end
+    channel, group residue, window start modulo T), ...]} -- class k of a level of window T is
+    computed in the background launches of the groups g = k mod T / G for its window starting at
+    block (g + 2) G (far: phase 2 there, phase 1 two groups before) -- and `loads`, the predicted
+    background bytes per group over the far window."""
+    L = _native.load()
+    nl, fa, ns, ef, nc, nld = (ctypes.c_int() for _ in range(6))
+    T, a, b, st = ((ctypes.c_int * 8)() for _ in range(4))
+    cuts, offs, loads = (ctypes.c_int * 256)(), (ctypes.c_int * 256)(), (ctypes.c_double * 64)()
+    _native.check(L.neo_hip_upols_stagger_plan(int(channels), int(block), int(partitions), int(step_group),
+                                               int(far_group), ctypes.byref(nl), T, a, b, st, ctypes.byref(fa),
+                                               ctypes.byref(ns), ctypes.byref(ef), cuts, offs, 256, ctypes.byref(nc),
+                                               loads, 64, ctypes.byref(nld)))
+    n = nl.value
+    out = {"a0": min(partitions, 8), "T": list(T[:n]), "a": list(a[:n]), "b": list(b[:n]),
+           "staggered": [bool(v) for v in st[:n]], "far_a": fa.value, "nseg": ns.value, "even_share": ef.value,
+           "loads": list(loads[:nld.value]), "classes": {}}
+    G = out["step_group"] = 128 // nld.value
+    i = 0
+    for key, Tl in [(l, T[l]) for l in range(n) if st[l]] + ([("far", 128)] if ns.value else []):
+        k = Tl // G
+        out["classes"][key] = [(cuts[i + j], cuts[i + j + 1], j, offs[i + j]) for j in range(k)]
+        i += k + 1
+    assert i == nc.value
+    return out
+
+
 def host_register(array: np.ndarray) -> np.ndarray:
     """Page-lock a host array in place (neo_hip_host_register) so that host-buffer calls
     (UpolsConvolver.__call__) read and write it over PCIe without staging; call
@@ -223,7 +254,7 @@ class UpolsConvolver:
 
     OPTION_DEFAULTS = {"fused": -1, "split_workgroups": 0, "batch_blocks": 0, "batch_bins": 0, "levels": -1,
                        "far_level": -1, "far_group": 0, "toep_split": 0, "step_group": 0,
-                       "far_phase2": 0}
+                       "far_phase2": 0, "windows": 0}
 
     def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
                  options: dict | None = None):
@@ -237,7 +268,9 @@ class UpolsConvolver:
         step_group (0 auto / 1 one launch per block / 2 or 4: the block of every call alone on the
         caller's stream, the level slices of G calls as one launch on a background stream),
         far_phase2 (G = 1: 0 auto / 1 one workgroup per unit / 2 the fresh transform one step
-        before the products). Every choice gives the same results up to float summation order."""
+        before the products), windows (step groups: 0 auto / 1 aligned level windows / 2 staggered: a
+        window phase per class of channels, bands from T + 4 G, fewer rows per step; see stagger_plan).
+        Every choice gives the same results up to float summation order."""
         lib = _native.load()
         h = ctypes.c_void_p()
         methods = {"upols": 0, "upola": 1, "upola_v2": 2}
@@ -406,6 +439,12 @@ class UpolsConvolver:
         """Steps per background launch of the streaming levels' slices (1: one launch per step)."""
         k = ctypes.c_int()
         _native.check(_native.load().neo_hip_upols_get_step_group(self._h, ctypes.byref(k)))
+        return k.value
+
+    def windows(self) -> int:
+        """The level windows the handle runs: 1 aligned, 2 staggered (neo_hip_upols_get_windows)."""
+        k = ctypes.c_int()
+        _native.check(_native.load().neo_hip_upols_get_windows(self._h, ctypes.byref(k)))
         return k.value
 
     def far_form(self) -> int:
