@@ -89,8 +89,9 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.10.0: window levels on matrix handles, long filters one block per call (neo_hip_matrix_set_levels,
  *        neo_hip_matrix_levels_info, neo_hip_matrix_level_plan).
  * 0.11.0: staggered level windows (neo_hip_upols_opts gains windows at its end: 11 ints;
- *        neo_hip_upols_stagger_plan). */
-#define NEO_HIP_VERSION 1100 /* 0.11.0 */
+ *        neo_hip_upols_stagger_plan).
+ * 0.12.0: the step groups' background stream is readable (neo_hip_upols_get_background_stream). */
+#define NEO_HIP_VERSION 1200 /* 0.12.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -430,6 +431,12 @@ NEO_HIP_API int neo_hip_upols_get_windows(neo_hip_upols* h, int* windows);
  * events on `stream`, or reusing the device's bandwidth right after, does. No reference
  * counterpart: the reference's operator() is synchronous (uniform_partitioned_convolver.hpp:47-65). */
 NEO_HIP_API int neo_hip_upols_join_background(neo_hip_upols* h, void* stream);
+/* the background stream of the handle's step groups (a hipStream_t), null while there is none:
+ * before the first grouped step, with one launch per step and in latency mode. For tests and
+ * tools that enqueue work of their own on it to shift the two streams against each other. Any
+ * setup call (filter, options, set_ahead, set_persistent, destroy) may destroy the stream, so a
+ * caller fetches it again after one. */
+NEO_HIP_API int neo_hip_upols_get_background_stream(neo_hip_upols* h, void** stream);
 /* -- Multichannel convolver over several devices ------------------------------
  * C channels cut into n contiguous shards, shard i = channels [C i / n, C (i + 1) / n) on
  * devices[i] (a device may repeat), each a neo_hip_upols handle of its own (own stream).

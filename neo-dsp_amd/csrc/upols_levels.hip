@@ -3518,6 +3518,16 @@ extern "C" NEO_HIP_API int neo_hip_upols_join_background(neo_hip_upols* h, void*
     return neo_hip::lvl_join(h, static_cast<hipStream_t>(stream));
 }
 
+// The step groups' background stream; null while there is none (group_streams creates it at the
+// first grouped step, lvl_free destroys it) and where no step uses it (one launch per step, the
+// latency mode's own schedule).
+extern "C" NEO_HIP_API int neo_hip_upols_get_background_stream(neo_hip_upols* h, void** stream)
+{
+    if (!h || !stream) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
+    *stream = h->sg > 1 && !h->persist ? static_cast<void*>(h->bg) : nullptr;
+    return NEO_HIP_OK;
+}
+
 #ifdef NEO_PS_PROBE
 // diagnostic builds only (not in include/neo_hip.h): the latency mode's per-step probe records,
 // [kPsRing][2] {seen, done} then [kPsRing][8] block-role points (wall clock, 100 MHz)

@@ -148,6 +148,7 @@ SIGNATURES = {
                                                                                ctypes.POINTER(ctypes.c_double), _i,
                                                                                ctypes.POINTER(_i)]),
     "neo_hip_upols_join_background": (_i, [_vp, _vp]),
+    "neo_hip_upols_get_background_stream": (_i, [_vp, ctypes.POINTER(_vp)]),
     "neo_hip_upols_set_paced": (_i, [_vp, _i]),
     "neo_hip_upols_set_persistent": (_i, [_vp, _i, ctypes.c_double]),
     "neo_hip_upols_get_persistent": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
@@ -212,7 +213,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1100 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1200 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

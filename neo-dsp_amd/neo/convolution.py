@@ -459,6 +459,14 @@ class UpolsConvolver:
         slice launches of the step groups issued so far (device-side; no host wait)."""
         _native.check(_native.load().neo_hip_upols_join_background(self._h, ctypes.c_void_p(stream)))
 
+    def background_stream(self) -> int:
+        """The step groups' background stream as a raw hipStream_t, 0 while there is none (before
+        the first grouped step, one launch per step, latency mode). A setup call may destroy it:
+        fetch it again after one (neo_hip_upols_get_background_stream)."""
+        s = ctypes.c_void_p()
+        _native.check(_native.load().neo_hip_upols_get_background_stream(self._h, ctypes.byref(s)))
+        return s.value or 0
+
     def set_paced(self, enable) -> None:
         """Step groups: issue the group's background launch in pieces, each block after the
         piece before it (neo_hip_upols_set_paced): an even host round trip per block. True / 1:

@@ -103,6 +103,54 @@ def test_staggered_windows_strided_io_ola(neo_gpu, oracle):
     assert compare(neo_gpu, oracle, torch, 3, 64, 450, {"step_group": 4}, strided=True, method="upola") <= TOL
 
 
+# (G, P, far_group, levels' windows, last level's band, far level's first partition, nseg): the plan's
+# band edges at C = 3, B = 64 (neo.convolution.stagger_plan). G = 4: a = [8, 16, 32, 48], F in [144, 240];
+# G = 2: a = [8, 16, 24, 40], F in [136, 232]; G = 8: a = [8, 16, 32, 64], F in [160, 256]
+BAND_EDGES = [
+    (4, 33, 0, [4, 8, 16], (32, 33), 33, 0),          # the T = 16 band of one partition
+    (4, 48, 0, [4, 8, 16], (32, 48), 48, 0),          # the T = 16 band full, no T = 32 level
+    (4, 49, 0, [4, 8, 16, 32], (48, 49), 49, 0),      # the T = 32 band of one partition, no far level
+    (4, 144, 0, [4, 8, 16, 32], (48, 144), 144, 0),   # the last P without a far level
+    (4, 145, 0, [4, 8, 16, 32], (48, 144), 144, 1),   # the far level appears: one partition in its segment
+    (4, 337, 0, [4, 8, 16, 32], (48, 209), 209, 1),   # the longest filter of one segment ...
+    (4, 338, 0, [4, 8, 16, 32], (48, 144), 144, 2),   # ... and two: F falls back to 144
+    (4, 368, 4, [4, 8, 16, 32], (48, 240), 240, 1),   # F = 240: the T = 32 level's full 192-row tile
+    (2, 17, 0, [4, 8], (16, 17), 17, 0),              # the T = 8 band of one partition (staggered at G = 2)
+    (2, 25, 0, [4, 8, 16], (24, 25), 25, 0),
+    (2, 41, 0, [4, 8, 16, 32], (40, 41), 41, 0),
+    (2, 137, 0, [4, 8, 16, 32], (40, 136), 136, 1),
+    (2, 329, 0, [4, 8, 16, 32], (40, 201), 201, 1),
+    (2, 360, 4, [4, 8, 16, 32], (40, 232), 232, 1),   # the full tile at G = 2
+    (8, 65, 0, [4, 8, 16, 32], (64, 65), 65, 0),
+    (8, 161, 0, [4, 8, 16, 32], (64, 160), 160, 1),
+    (8, 353, 0, [4, 8, 16, 32], (64, 225), 225, 1),
+    (8, 384, 4, [4, 8, 16, 32], (64, 256), 256, 1)]   # the full tile at G = 8
+
+
+@pytest.mark.parametrize("G,P,K,T,band,F,nseg", BAND_EDGES)
+def test_staggered_band_edges(neo_gpu, oracle, G, P, K, T, band, F, nseg):
+    """The edges of the staggered plan's bands: a level or the far level with one partition, the
+    longest band of the T = 32 level's LDS tile, the step from one far segment to two. Each case
+    first asserts the band it is named for, so a change of the plan cannot turn it into another."""
+    torch = pytest.importorskip("torch")
+    C, B = 3, 64
+    plan = neo_gpu.convolution.stagger_plan(C, B, P, G, K)
+    assert plan["T"] == T and (plan["a"][-1], plan["b"][-1]) == band and plan["staggered"][-1]
+    assert (plan["far_a"], plan["nseg"]) == (F, nseg)
+    assert nseg == 0 or P - F - 128 * (nseg - 1) >= 1  # partitions of the last segment
+    # levels = 1: below 64 partitions a handle runs the plain step unless asked
+    assert compare(neo_gpu, oracle, torch, C, B, P, {"step_group": G, "far_group": K, "levels": 1}) <= TOL
+
+
+@pytest.mark.parametrize("method", ["upols", "upola"])
+@pytest.mark.parametrize("B", [16, 128, 512, 1024])
+def test_staggered_block_sizes(neo_gpu, oracle, B, method):
+    """The block kernel's staggered build is an instantiation of its own per block size and method:
+    the sizes that the other cases here do not force."""
+    torch = pytest.importorskip("torch")
+    assert compare(neo_gpu, oracle, torch, 3, B, 170, {"step_group": 4}, method=method) <= TOL
+
+
 def test_automatic_choice(neo_gpu, oracle):
     """windows = 0: staggered where the step group is automatic and the shape has 65536 16-column
     units or more, aligned below and with an explicit step group; the handle reports the plain
