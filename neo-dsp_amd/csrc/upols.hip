@@ -370,7 +370,7 @@ void destroy(upols_t* h)
 int launch_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
     if (int rc = note_stream(h, s)) return rc;
-    if (h->persist) return persist_process(h, in, ld_in, out, ld_out, 1);  // synchronous: s is not used
+    if (h->sched.persist) return persist_process(h, in, ld_in, out, ld_out, 1);  // synchronous: s is not used
     return launch_step_normal(h, in, ld_in, out, ld_out, s);
 }
 
@@ -464,7 +464,7 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
     const int T = h->batch ? batch_blocks(h) : 1;
     const bool a16 = !((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) &&
                      !((ld_in | ld_out) & 3);
-    if (h->persist) {  // latency mode: every block through the persistent kernel, complete on return
+    if (h->sched.persist) {  // latency mode: every block through the persistent kernel, complete on return
         if (n % B || !a16) return fail(NEO_HIP_EINVAL, "latency mode: whole 16-byte aligned blocks");
         return persist_process(h, in, ld_in, out, ld_out, n / B);
     }
@@ -547,41 +547,13 @@ int create_convolver(int channels, int block, int partitions, int device, bool o
     if (g.rc) return g.rc;
     auto* h = new upols_t{};
     (void)hipGetDevice(&h->device);
-    h->C = channels;
-    h->B = block;
-    h->P = partitions;
-    h->ring = partitions + kMaxBatch - 1;
-    plan_levels(partitions, h->lv, o.far_level);
-    h->far_k = o.far_group;
-    h->toep_jh = o.toep_split;
-    h->f2mode = o.far_phase2;
-    h->sg = o.step_group ? o.step_group : step_group_for(channels, block, partitions);
-    h->bg_pad = bg_pad_for(channels, block);
-    // staggered level windows (plan_levels_stag): on request with any step group of 2, 4 or 8 and
-    // the far level's stored form; automatic only from kStaggerUnits 16-column units with an
-    // automatic step group, the one size measured to gain (c5full, 65536 units: 107.4 -> 99.4 us per
-    // step; DESIGN 6, profiles/stagger_ab.json). Smaller handles and a group's members (borrow)
-    // keep the aligned plan.
-    {
-        const bool can = h->sg > 1 && o.far_level != 0 && o.far_level != 2 && !v2 && block <= 1024;
-        if (o.windows == 2 && !can) {
-            delete h;
-            return fail(NEO_HIP_EINVAL, "staggered windows take step groups and the far level's stored form");
-        }
-        if (o.windows == 2 ||
-            (o.windows == 0 && can && !o.step_group && !borrow && int64_t(channels) * (block / 16) >= kStaggerUnits))
-            plan_levels_stag(partitions, channels, block, h->sg, o.far_group, h->lv);
+    // the shape, the level plan and schedule options, the FDL ring's rows (levels_plan.hpp)
+    if (const char* why = make_level_sched(channels, block, partitions, partitions + kMaxBatch - 1, o, borrow != nullptr, v2,
+                                           h->sched)) {
+        delete h;
+        return fail(NEO_HIP_EINVAL, "%s", why);
     }
-    // the far level's form: the stored spectra (phase 1 + 2) by default; recomputed every window
-    // (far2r_role) on request -- fewer bytes (C5: 15 instead of 23 rows per column and step) but
-    // 2 nseg + 1 transforms per unit and window: same-box A/B with step groups, stored vs
-    // recomputed, us per step: c5full 107-109 vs 115-124 (VALU), C5 15.9 vs 15.8-16.4, C4 12.4 vs
-    // 18-20 (the 27-transform chain of 13 segments bounds the background launch)
-    h->far_raw = h->lv.nseg && o.far_level == 2;
-    if (h->lv.nseg) h->ring = std::max(h->ring, kFarRing);  // far slices read 383 blocks back
-    // recomputed: a window's slices read the band's rows back to t_W - 128 (nseg + 2) > t_W - P - 128
-    // while blocks up to t_W + 3 may be written beside them (step groups)
-    if (h->far_raw) h->ring = std::max(h->ring, partitions + 2 * kFarT);
+    h->bg_pad = bg_pad_for(channels, block);
     // offline windows (k_off_mac): a pass of 128 wp blocks reads rows back to t_W - 128 nseg while
     // writing rows t_W .. t_W + 128 wp - 1
     h->off = !v2 && partitions >= kOffMinP;
@@ -1163,7 +1135,7 @@ NEO_HIP_API int neo_hip_upols_set_ahead(neo_hip_upols* h, int enable)
     if (enable && h->B > 1024) return fail(NEO_HIP_EINVAL, "streaming levels take blocks up to 1024");
     device_guard g(h->device);
     if (int rc = persist_stop(h)) return rc;
-    if (!enable) h->persist = false;  // the latency mode runs the levels
+    if (!enable) h->sched.persist = false;  // the latency mode runs the levels
     h->ahead = enable != 0;
     h->lv_n = -1;  // the FDL is complete at any block boundary: the next step primes the levels
     return NEO_HIP_OK;
@@ -1196,18 +1168,18 @@ NEO_HIP_API int neo_hip_upols_set_persistent(neo_hip_upols* h, int enable, doubl
         if (!(idle_ms > 0.0 && idle_ms <= 10000.0)) return fail(NEO_HIP_EINVAL, "idle_ms must be in (0, 10000]");
         if (int rc = setup_join(h)) return rc;  // this handle's steps queued on any stream come first
         h->ps_idle_ms = idle_ms;
-        h->persist = true;
+        h->sched.persist = true;
         h->ps_valid = false;  // the persistent schedule primes the levels at its first block
         return NEO_HIP_OK;
     }
-    h->persist = false;
+    h->sched.persist = false;
     return persist_stop(h);
 }
 
 NEO_HIP_API int neo_hip_upols_get_persistent(neo_hip_upols* h, int* enabled, int* running, int64_t* launches)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
-    if (enabled) *enabled = h->persist;
+    if (enabled) *enabled = h->sched.persist;
     if (running) *running = h->ps_running && h->ps_mb && __atomic_load_n(&h->ps_mb->alive, __ATOMIC_ACQUIRE);
     if (launches) *launches = h->ps_launches;
     return NEO_HIP_OK;
@@ -1237,8 +1209,8 @@ NEO_HIP_API int neo_hip_upols_get_ahead(neo_hip_upols* h, int* enabled, int* pha
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     if (enabled) *enabled = h->ahead;
     if (phase) *phase = int(h->lv_n < 0 ? 0 : h->lv_n % kFarT);
-    if (window) *window = h->lv.nseg ? kFarT : (h->lv.n ? h->lv.T[h->lv.n - 1] : 1);
-    if (splits) *splits = h->lv.n + (h->lv.nseg ? 1 : 0);
+    if (window) *window = h->sched.lv.nseg ? kFarT : (h->sched.lv.n ? h->sched.lv.T[h->sched.lv.n - 1] : 1);
+    if (splits) *splits = h->sched.lv.n + (h->sched.lv.nseg ? 1 : 0);
     return NEO_HIP_OK;
 }
 

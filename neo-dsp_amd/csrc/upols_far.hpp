@@ -1,7 +1,7 @@
 // upols_far.hpp — device helpers of the 256-point transforms along the block axis, shared by the
 // far level and the offline windows of dense handles (upols_levels.hip) and the offline windows of
 // matrix handles (upols_matrix_offline.hip): the column transform, the packed complex MAC, the
-// real-FFT packing of bin 0, buffer loads and stores, and the padded strides of the level buffers.
+// real-FFT packing of bin 0, buffer loads and stores.
 #pragma once
 
 #include "upols_device.hpp"
@@ -9,19 +9,8 @@
 
 namespace neo_hip {
 
-constexpr int kFN = 2 * kFarT;  // far level: partition-axis transform length
-
-// Channel strides (complex units) of the level buffers: kPad rows more than the data, so that no
-// channel stride is a multiple of a large power of two -- every channel's row n of a slab, of the
-// far field or of a segment spectrum would otherwise sit at the same offset modulo 512 KB .. 8 MB
-// (an FDL ring of 1280 rows, 5 x 2^20 bytes per channel at B = 512, cost the c5full step 4 %)
-#ifndef NEO_PAD
-#define NEO_PAD 1  // diagnostic builds (A/B): 0 = unpadded strides
-#endif
-constexpr int kPad = NEO_PAD;
-__host__ __device__ constexpr int64_t slab_cs(int T, int B) { return int64_t(T + kPad) * B; }
-__host__ __device__ constexpr int64_t ff_cs(int B) { return int64_t(kFarT + kPad) * B; }
-__host__ __device__ constexpr int64_t spec_cs(int nseg, int B) { return (int64_t(nseg) * kFN + kPad) * B; }
+// kFN (the transform length) and the padded strides of the level buffers (slab_cs, ff_cs, spec_cs):
+// levels_plan.hpp
 
 // 256-point transforms of NC columns held by lanes (a, cp), a < 16, cp < NC: on entry
 // v[n2] = x[a + 16 n2], on exit v[k1] = X[16 k1 + a] (16-point DFTs in registers, twiddle,

@@ -1,9 +1,14 @@
 // upols_handle.hpp — the UPOLS convolver handle (neo_hip_upols) and the host helpers
 // shared by the translation units that implement it (upols.hip, upols_batch.hip,
-// upols_setup.hip).
+// upols_setup.hip, upols_levels.hip).
+//   constants, the latency mode's mailbox and device helpers
+//   neo_hip_upols: the handle; its level schedule is a level_sched (levels_plan.hpp: the level
+//       constants, level_plan, the plan and the schedule of the streaming levels, host only)
+//   what the translation units share: launches, setup helpers, the streaming levels' entry points
 #pragma once
 
 #include "common.hpp"
+#include "levels_plan.hpp"
 
 #include <cstdint>
 #include <deque>
@@ -17,15 +22,6 @@ constexpr double kCacheBudgetBytes = 216.0 * 1024 * 1024;  // filter bytes read 
 // the batched passes leave more of the Infinity Cache to the slabs (same-box A/B at C5, 4 runs
 // each: 168 MiB 17.8 us/step, 216 MiB 18.3, 126 MiB 18.1)
 constexpr double kBatchCacheBudgetBytes = 168.0 * 1024 * 1024;
-// streaming levels (upols_levels.hip)
-constexpr int kLvA0 = 8;     // partitions the block itself MACs (p < kLvA0)
-constexpr int kLvToep = 5;   // Toeplitz level slots: l < 4 window kLvT0 << l; slot 4 the big level
-constexpr int kLvT0 = 4;
-constexpr int kBigT = 128;   // big Toeplitz level: window, band [2 kBigT, P) instead of the far level (opt-in:
-                             // 26.9 vs 19.2 us per C5 step, its 89 M complex MACs per step are VALU / LDS bound)
-constexpr int kFarT = 128;   // far level: blocks per window (256-point partition-axis transform)
-constexpr int kFarA = 256;   // far level: first partition (2 kFarT)
-constexpr int kFarRing = 2 * kFarA;  // far level: FDL ring rows needed (a slice reads back 383 blocks)
 // offline windows (k_off_mac): batched calls of >= 128 blocks take windows of kFarT blocks through
 // partition-axis transforms of every 128-partition segment, from this many partitions
 #ifndef NEO_OFF_MIN_P
@@ -147,33 +143,17 @@ __device__ __forceinline__ bool ps_record(const persist_ctl& pc, int64_t n, bool
     return true;
 }
 
-struct level_plan {
-    int a0 = 1;                      // the block step takes partitions [0, a0)
-    int n = 0;                       // Toeplitz levels
-    int T[kLvToep] = {}, a[kLvToep] = {}, b[kLvToep] = {};  // window (blocks) and partition band [a, b) per level
-    int nseg = 0;                    // far segments of kFarT partitions from farA (0: no far level)
-    int farA = kFarA;                // the far level's first partition (staggered windows: plan_levels_stag)
-    int stag = 0;                    // staggered windows: the step group G they are planned for (0: aligned)
-};
-
-// Staggered windows (upols_levels.hip, plan_levels_stag): a level of window T >= 4 G (and the far
-// level) is cut into T / G classes of channels, class k computed in the background launches of the
-// groups g = k mod T / G for the window starting at block (g + 2) G, so its band starts at T + 4 G.
-// A channel's class: its position in 1/1024ths of a pair of far classes is (c M) >> 20 with
-// M = ((64 / G) << 30) / C, shifted right by log2(128 / T) for a level of window T; the even class
-// of a pair takes the first ef of its 1024 parts.
-__host__ __device__ inline int stag_class(unsigned long long M, int ef, int c, int shift)
-{
-    const int p = int((static_cast<unsigned long long>(c) * M) >> 20) >> shift;
-    return 2 * (p >> 10) + ((p & 1023) >= ef ? 1 : 0);
-}
-// windows of class k start where (n + phi) mod T = 0
-__host__ __device__ inline int stag_phi(int T, int G, int k) { return (-(k + 2) * G) & (T - 1); }
 }  // namespace neo_hip
 
 struct neo_hip_upols {
-    int device = 0, C = 0, B = 0, P = 0, S = 1, rows = 1;
-    int ring = 0;  // FDL ring rows R = P + kMaxBatch - 1 (at least kFarRing with a far level)
+    // the shape, the FDL ring's rows and everything the streaming levels' plan and schedule read
+    // (levels_plan.hpp); C, B, P and ring live there
+    neo_hip::level_sched sched;
+    int &C = sched.C, &B = sched.B, &P = sched.P, &ring = sched.ring;
+    neo_hip_upols() = default;
+    neo_hip_upols(const neo_hip_upols&) = delete;  // the references above
+    neo_hip_upols& operator=(const neo_hip_upols&) = delete;
+    int device = 0, S = 1, rows = 1;
     hipStream_t stream = nullptr;
     neo_hip::cf* H = nullptr;
     neo_hip::cf* fdl = nullptr;
@@ -192,40 +172,20 @@ struct neo_hip_upols {
     neo_hip::cf* part_b = nullptr;   // batched partial spectra [C][Sb][T][B]
     // streaming levels (upols_levels.hip): on for HBM-bound shapes (neo_hip_upols_set_ahead)
     bool ahead = false;
-    neo_hip::level_plan lv;
     int64_t lv_n = -1;              // blocks since the levels were primed (-1: prime at the next step)
     bool fdl_zero = false;          // FDL ring all zero, nothing stepped since (reset_state): every level
                                     // window the prime computes is zero, so priming is zeroing
     bool grouped = false;           // created by a convolver group (create_handle): no eager priming
     bool lv_ready = false;          // level buffers allocated
     neo_hip::cf* lv_slab[neo_hip::kLvToep] = {};  // Toeplitz level slabs [2][C][T][B]
-    // step groups (upols_levels.hip part_plan, set when the levels prime): per Toeplitz level the
-    // window offset phi (windows start at t0 + W T - phi) and the unit cuts of its background parts
-    // per window of a cycle of lv_cyc groups
-    int lv_phi[neo_hip::kLvToep] = {};
-    int lv_cyc = 1;
-    std::vector<int> lv_cut[neo_hip::kLvToep];
-    std::vector<int> fv_cut;  // step groups: the far slices' first units (ns + 1 cuts; empty: equal slices)
-    // staggered windows (lv.stag): the first channel of every class per level and of the far level
-    // (T / G + 1 cuts), the even classes' share of a pair in 1/1024ths per level and of the far level
-    std::vector<int> st_cut[neo_hip::kLvToep], st_fcut;
-    int st_ef[neo_hip::kLvToep] = {}, st_fef = 512;
     neo_hip::cf* fv_hf = nullptr;   // far segment spectra [C][nseg][256][B]
     neo_hip::cf* fv_xf = nullptr;   // far FDL row-pair spectra, ring of nseg slots [C][nseg][256][B]
     neo_hip::cf* fv_ff = nullptr;   // far field [2][C][128][B]
     neo_hip::cf* fv_tw = nullptr;   // 256-point twiddles
     neo_hip::cf* fv_acc = nullptr;  // far phase-1 partial sums [K][units][256][16] (K = far_group)
     bool fv_dirty = true;           // far segment spectra to recompute (filter changed)
-    int far_k = 0;                  // far phase-1 windows per pass forced by neo_hip_upols_opts.far_group (0: auto)
-    int toep_jh = 0;                // T = 32 window parts forced by neo_hip_upols_opts.toep_split (0: auto)
-    int f2mode = 0;                 // far phase 2 at G = 1 forced by neo_hip_upols_opts.far_phase2 (0: auto)
-    bool far_raw = false;           // far level recomputed every window from the filter and FDL rows
-                                    // (neo_hip_upols_opts.far_level 2; far2r_role): no fv_hf / fv_xf / fv_acc
-    // step groups (neo_hip_upols_opts.step_group, G = sg): G = 1 runs a step as ONE launch (the
-    // block and 1/T of every level's next window); G > 1 runs the block of every call alone on the
-    // caller's stream and the level slices of G steps as one launch on the handle's background
-    // stream bg, one step group ahead (events ev_blk / ev_sl order the two; upols_levels.hip)
-    int sg = 1;
+    // step groups (sched.sg > 1): the level slices of G steps run as one launch on the handle's
+    // background stream bg, one step group ahead (events ev_blk / ev_sl order the two; upols_levels.hip)
     int bg_pad = 0;  // dynamic LDS bytes of the slices launches (bg_pad_for): 1024 holds them to 2 workgroups per CU
     hipStream_t bg = nullptr;
     hipEvent_t ev_blk = nullptr, ev_sl[2] = {}, ev_join = nullptr;
@@ -285,7 +245,7 @@ struct neo_hip_upols {
     int64_t part_n[4] = {};
     std::vector<float> group_ms;   // whole-group durations, in order (neo_hip_upols_step_times)
     // latency mode (neo_hip_upols_set_persistent): a persistent step kernel on ps_stream
-    bool persist = false;          // requested
+    // (requested: sched.persist)
     bool ps_running = false;       // a persistent kernel was launched and not yet joined
     bool ps_valid = false;         // the level slabs follow the persistent schedule (relaunch without priming)
     hipStream_t ps_stream = nullptr;
@@ -457,23 +417,14 @@ inline int timing_mark(upols_t::ev_group* g, int i, hipStream_t s)
 }
 
 // upols_levels.hip: one streaming block step (level slabs + the newest partitions) and 1/T
-// of every level's next window; the level plan; buffers; filter-change hook
+// of every level's next window; buffers; filter-change hook (the plan: levels_plan.hpp)
 // (snap: also copy each channel's input block, as read, to snap [C][B])
 int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s,
                   float* snap = nullptr);
-// far: -1 auto (= 1), 0 the big Toeplitz level, 1 the far level
-void plan_levels(int P, level_plan& lp, int far = -1);
-// the staggered plan for step groups of G blocks (far_k: the forced far window group, 0 auto)
-void plan_levels_stag(int P, int C, int B, int G, int far_k, level_plan& lp);
-constexpr int64_t kStaggerUnits = 65536;  // 16-column units from which windows = 0 (auto) staggers (upols.hip)
 // the block role of streaming step n (FDL ring row w) again for channel c alone, with another
 // input block (upols_group.hip: a speculatively stepped channel whose caller's block differed);
 // the step's slabs and far field must not have been overwritten since
 int launch_block_only(upols_t* h, int64_t n, int w, int c, const float* in, float* out, hipStream_t s);
-// the automatic far phase-1 window group / T = 32 window parts a handle of C channels would use
-int far_group_for(int C, int B, int P);
-int toep_split_for(int C, int B);
-int step_group_for(int C, int B, int P);
 int bg_pad_for(int C, int B);
 // latency mode: whole blocks through the persistent kernel, synchronous (upols_levels.hip)
 int persist_process(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t nblocks);

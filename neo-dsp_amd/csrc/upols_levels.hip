@@ -22,6 +22,12 @@
 // them). S_{q+1} of window W+1 is S_q of window W, so each window transforms ONE new row
 // pair per bin (segment 2) and keeps the spectra in a ring of NSEG slots (XF); the rest is a
 // stream of XF . HF products (far1_role / far2_role).
+//
+// This file: the kernels and their device roles; the launches (launch_step_kernel, base_args and
+// bind, which turn a launch's records into kernel arguments), the level buffers, the streams and
+// events of the step groups (launch_levels), the latency mode's host side, and the exports. The
+// level plan and the schedule -- which role computes which units of which window in which launch --
+// are host-only functions in levels_plan.hpp.
 #include "upols_device.hpp"
 #include "upols_far.hpp"
 #include "upols_handle.hpp"
@@ -62,164 +68,12 @@ namespace neo_hip {
 
 
 // ---------------------------------------------------------------------------------------
-// level plan (host; also exported for the CPU schedule test, neo_hip_upols_level_plan)
-void plan_levels(int P, level_plan& lp, int far)
-{
-    lp = level_plan{};
-    lp.a0 = std::min(P, kLvA0);
-    static constexpr int T[4] = {4, 8, 16, 32}, A[4] = {8, 16, 32, 64}, Bd[4] = {16, 32, 64, kFarA};
-    for (int l = 0; l < 4; ++l) {
-        if (P <= A[l]) break;
-        lp.T[lp.n] = T[l];
-        lp.a[lp.n] = A[l];
-        lp.b[lp.n] = std::min(P, Bd[l]);
-        ++lp.n;
-    }
-    if (P <= kFarA) return;
-    if (far != 0) {
-        lp.nseg = (P - kFarA + kFarT - 1) / kFarT;
-    } else {  // [256, P) by the big Toeplitz level (slot 4)
-        lp.T[lp.n] = kBigT;
-        lp.a[lp.n] = 2 * kBigT;
-        lp.b[lp.n] = P;
-        ++lp.n;
-    }
-}
-
-// Staggered windows (step groups of G blocks). In the aligned plan every slice of a window shares
-// the window's start, so the band starts at 2 T: a slice computed early in the previous window
-// waits up to T - 1 steps for its first read. Here a level of window T >= 4 G is cut into T / G
-// classes of channels and class k has a window phase of its own: it is computed whole in the
-// background launch of group g = k mod T / G, for the window that starts at block s = (g + 2) G.
-// That launch is guaranteed the FDL rows before (g - 2) G = s - 4 G (an even group's launch only
-// follows its odd predecessor, which waited for the blocks before the group before it) and is
-// first waited for at block (g + 2) G (launch_levels), and the window's rows s + j - p end at
-// s + T - 1 - a: the band may start at a = T + 4 G. The far level likewise (phase 1 of a class two
-// groups before its phase 2, whose fresh row pair ends at s - F + 127): F >= 128 + 4 G. A class's
-// slab buffer is rewritten T / G groups after it was written, T - 2 G >= 2 G steps after the block
-// launch that waited for it was issued.
-// G = 4: [8, 16) [16, 32) as aligned, T = 16 [32, 48), T = 32 [48, F), far from F in [144, 240]:
-// the F with the fewest bytes by the model of DESIGN 5 (the T = 32 band's 2 (F - 48) + 63 rows per
-// 32 steps against the far level's 512 (nseg - 1) / K + 256 (K + 3) + 384 per 128), the fewer
-// segments where two are within half a percent.
-static int far_group_auto(int C, int B, int ns);
-constexpr int kT32BandMax = 192;  // the T = 32 level's LDS tile (kT32Band)
-
-void plan_levels_stag(int P, int C, int B, int G, int far_k, level_plan& lp)
-{
-    lp = level_plan{};
-    lp.stag = G;
-    lp.a0 = std::min(P, kLvA0);
-    int A[5];
-    for (int l = 0; l < 4; ++l) A[l] = (kLvT0 << l) > 4 * G ? (kLvT0 << l) + 4 * G : 2 * (kLvT0 << l);
-    const int Fmin = kFarT + 4 * G, Fmax = A[3] + kT32BandMax;
-    int F = P, nseg = 0;
-    if (P > Fmin) {
-        double best = 1e300;
-        for (int ns = std::max(1, (P - Fmax + kFarT - 1) / kFarT); ns <= (P - Fmin + kFarT - 1) / kFarT; ++ns) {
-            const int f = std::max(Fmin, P - kFarT * ns), K = ns < 2 ? 1 : (far_k ? far_k : far_group_auto(C, B, ns));
-            const double rows = (2.0 * (f - A[3]) + 63) / 32 + (512.0 * (ns - 1) / K + 256.0 * (K + 3) + 384) / kFarT;
-            if (rows < best * 0.995) {
-                best = rows;
-                F = f;
-                nseg = ns;
-            }
-        }
-    }
-    A[4] = F;
-    for (int l = 0; l < 4; ++l) {
-        if (P <= A[l]) break;
-        lp.T[lp.n] = kLvT0 << l;
-        lp.a[lp.n] = A[l];
-        lp.b[lp.n] = std::min(P, A[l + 1]);
-        ++lp.n;
-    }
-    lp.farA = F;
-    lp.nseg = nseg;
-}
-
-// ---------------------------------------------------------------------------------------
 // device helpers
 
-// kFN, the padded strides, col_fft, pk_coef, the buffer loads and stores and the bin-0 packing:
-// upols_far.hpp (shared with upols_matrix_offline.hip)
+// col_fft, pk_coef, the buffer loads and stores and the bin-0 packing: upols_far.hpp (shared with
+// upols_matrix_offline.hip); kFN and the padded strides: levels_plan.hpp
 
-// ---------------------------------------------------------------------------------------
-// The per-step slices kernel: one launch after every block step, workgroups by role.
-//   rest      the next block's spectrum without partition 0: its partitions 1 .. a0 - 1
-//             (rows up to this block's) plus the level slabs of the next block
-//   Toeplitz  1/T of the next window of each Toeplitz level (a slice of its columns)
-//   far       1/128 of the next far window (a slice of its 8-column units)
-// Every role reads FDL rows up to this step's block only; the block step of the next call
-// then needs nothing but its window, this spectrum and H0.
-struct toep_arg {
-    cf* slab;           // the target window's slabs [C][T][B]
-    int T, a, b;        // window, band [a, b)
-    int tw;             // ring row of the window's first block
-    int u0, u1, nwg;    // units (16 columns x one of JH window parts) of this slice, workgroups
-    int jh;             // window parts per column group (toep_geom)
-    int64_t cs;         // the slab's channel stride (slab_cs)
-};
-
-struct slice_args {
-    const cf* H;
-    cf* fdl;
-    int ring, C, B;
-    int64_t cstride, pstride;
-    // block role: this step's block, one workgroup per channel (nblk = 0 in priming launches)
-    // from channel blk_c0 on
-    int nblk, blk_c0;
-    const float* in;
-    int64_t ld_in;
-    float* out;
-    int64_t ld_out;
-    float* prev;
-    float* snap;            // not null: a copy of each channel's input block, [C][B] (upols_group.hip: the
-                            // frame the leader's launch read in place, for the later members' comparisons)
-    const cf* twg;
-    int w, a0;              // ring row of the block; partitions the block role MACs directly
-    int nsl;
-    const cf* sl[kLvToep];  // slab row of this block per level, channel 0
-    int64_t scs[kLvToep];   // channel strides
-    const cf* ff;           // far field row of this block, channel 0 (null: no far level)
-    int64_t fcs;
-    // staggered windows (stag = G, else 0): the row depends on the channel's class (stag_class, stag_phi).
-    // A level with ssh[l] >= 0 (the far level: fsh) gives its slab's base in sl[l] (ff) and the block
-    // role adds the buffer and row of step snm = n mod 256 in the class's window
-    int stag, snm, fsh, fef;
-    int ssh[kLvToep], sef[kLvToep];  // per level: position shift, the even classes' share (1/1024ths)
-    unsigned long long sM;
-    // Toeplitz roles
-    int ntp;
-    toep_arg tp[kLvToep];
-    // far level (16-column units), common
-    int M, nseg, fnfresh, P;
-    int fA;       // the far level's first partition (level_plan::farA)
-    int64_t fsc;  // segment / row-pair spectra channel stride (spec_cs; M = nseg slots)
-    const cf* hf;
-    cf* xf;
-    const cf* twf;
-    int fU;     // units (16 columns) of all channels
-    // far phase 1: stored-segment MAC, groups of kF1UG units; in pair mode a group takes two
-    // windows at once (far1_role)
-    int f1nwg, f1u0, f1u1, f1wn, f1fpl;  // slice units [f1u0, f1u1); target window; f rows per lane
-    int fK;                              // windows per phase-1 pass (1: one window per pass)
-    int f1g0, f1gs, f1mode, f1cls;       // first group, group step; 0 single, 1 the class's groups, 2 every group; class
-    cf* f1acc;  // partial sums [fK (window mod fK)][fU][256 f][16]
-    // far phase 2a (the slice phase 1 takes in the same launch): the fresh row pairs'
-    // transforms, stored to their ring slots
-    int f2nwg, f2u0, f2tw, f2wn;
-    // far phase 2b (the slice of the previous launch): the stored fresh spectra's products,
-    // phase 1's partial sums, the window group's extra segments, the inverse transform
-    int f3nwg, f3u0, f3wn;
-    int f2grp;    // phase-1 window groups on: a unit in window j of its group takes segments 1..j in 2b
-    int f2comb;   // 1: 2b also runs 2a's fresh transform for its units (f2tw: its rows), no slot read-back (far2c_role);
-                  // 2: the recomputed far level (far2r_role, every segment from the filter and FDL rows)
-    cf* f2acc;    // as f1acc
-    cf* f3ff;     // 2b's target far window [C][128][B]
-    void* tl;     // timeline builds (NEO_TIMELINE): per-workgroup records of the launch
-    int bid0;     // paced background pieces: the first workgroup of the launch this piece runs
-};
+// The step kernels' arguments (slice_args, toep_arg): levels_plan.hpp
 
 // the T = 32 Toeplitz level stages its band in LDS: the filter rows of its band and the FDL rows
 // they meet, 16 columns each, column-major with padded strides. The tile holds kT32Band rows:
@@ -811,7 +665,7 @@ __device__ __forceinline__ void toep_lds_role(const slice_args& sa, const toep_a
 // FDL rows through its L2). The band goes through an LDS tile in chunks of kBigNC
 // partitions; lane (col, quad, quarter) owns 4 outputs of the part over a quarter of each
 // chunk (t32_walk), and the quarters meet through LDS at the end.
-constexpr int kBigJH = 8, kBigJP = kBigT / kBigJH, kBigNC = 192;
+constexpr int kBigJP = kBigT / kBigJH, kBigNC = 192;
 constexpr int kBigHS = kBigNC + 2, kBigXS = kBigNC + kBigJP + 2;  // even column strides
 static_assert(16 * (kBigHS + kBigXS) * int(sizeof(cf)) <= kSliceLds, "big level tile");
 
@@ -916,8 +770,7 @@ __device__ __forceinline__ void toep_big_role(const slice_args& sa, const toep_a
 // of window wn + j (slots not yet stored when the pass runs: phase 2 of windows wn .. wn + j - 1
 // writes them) are phase 2's, in that window (f2grp). K ~ sqrt(2 (nseg - 1)) (far_group) balances
 // the two: 2 (nseg - 1) / K + K - 1 spectra per window and column instead of 2 (nseg - 1).
-constexpr int kF1UG = 4;
-constexpr int kFarKMax = 4;
+// (kF1UG, kFarKMax: levels_plan.hpp)
 
 // first window >= 1 whose phase-1 pass a unit group of class c starts (earlier windows after
 // priming: one window per pass)
@@ -1712,104 +1565,11 @@ __global__ __launch_bounds__(256) void k_lvf_filter(const cf* __restrict__ H, cf
 // ---------------------------------------------------------------------------------------
 // host side
 
-// phase 1 f rows per lane: one load round covers the stored segments (far1_role)
-static int far1_fpl(const upols_t* h)
-{
-#ifdef NEO_FAR_FPL  // diagnostic builds
-    return NEO_FAR_FPL;
-#endif
-    return h->lv.nseg - 1 <= 4 ? 4 : (h->lv.nseg - 1 <= 8 ? 2 : 1);
-}
-
-static int64_t far_units(const upols_t* h) { return int64_t(h->C) * (h->B / 16); }
-
-// windows per far phase-1 pass (far1_mac): K ~ sqrt(2 (nseg - 1)) minimizes the spectra read per
-// window and column, 2 (nseg - 1) / K + K - 1; but phase 2 takes up to K - 1 extra segments in
-// its one-workgroup-per-unit chain, which bounds the step where a step has few far units
-// (measured: K = 3 / 4 instead of 2 at 64 / 32 units per step, C5 / C4: 13 % / 25 % slower; at
-// 512, the 2048-channel headline: 3 % faster; round 5, the 4-GPU shard of the headline, 512
-// channels = 128 units per step: K = 3 2-3.5 % faster, tools/gpu_shard_sweep.sh), so K = 2 below
-// kFarGroupUnits units
-constexpr int64_t kFarGroupUnits = 16384;  // 128 units per step
-
-static int far_group_auto(int C, int B, int ns)
-{
-    if (ns < 2) return 1;
-    if (int64_t(C) * (B / 16) < kFarGroupUnits) return 2;
-    const int K = int(std::lround(std::sqrt(2.0 * (ns - 1))));
-    return std::min(kFarKMax, std::max(2, K));
-}
-
-int far_group_for(int C, int B, int P)
-{
-    level_plan lp;
-    plan_levels(P, lp);
-    return lp.nseg ? far_group_auto(C, B, lp.nseg) : 0;
-}
-
-static int far_group(const upols_t* h)
-{
-    const int ns = h->lv.nseg;
-    if (ns < 2 || h->far_raw) return 1;  // recomputed: every window on its own
-    if (h->far_k) return h->far_k;  // neo_hip_upols_opts.far_group (tests, A/B runs)
-    return far_group_auto(h->C, h->B, ns);
-}
-
-// far phase 1 over the slice units [u0, u1): mode 0 one window per group, 1 only the groups of
-// class cls (K windows each), 2 every group (class cls: K windows; classes not started: one)
-__host__ __device__ inline void far1_range_k(slice_args& a, int u0, int u1, int mode, int cls, int K, int fpl)
-{
-    a.f1u0 = u0;
-    a.f1u1 = u1;
-    a.f1fpl = fpl;
-    a.f1mode = mode;
-    a.f1cls = cls;
-    a.f1nwg = 0;
-    if (u1 <= u0) return;
-    const int ga = u0 / kF1UG, gb = (u1 - 1) / kF1UG;  // groups holding slice units
-    a.f1g0 = mode == 1 ? ga + ((cls - ga % K) % K + K) % K : ga;
-    a.f1gs = mode == 1 ? K : 1;
-    const int ng = a.f1g0 > gb ? 0 : (gb - a.f1g0) / a.f1gs + 1;
-    a.f1nwg = ng * (kFN / (4 * fpl));
-}
-
-static void far1_range(const upols_t* h, slice_args& a, int u0, int u1, int mode, int cls)
-{
-    far1_range_k(a, u0, u1, mode, cls, far_group(h), far1_fpl(h));
-}
-
-// Latency mode's far level (persist_far): the far work of step n (block t0 + n, ring row w) in the
-// one-launch schedule, with kFarT - 2 slices (one more step of slack: the field of window W is
-// complete two steps before its first block, as the Toeplitz slabs): phase 1 of slice q and phase 2
-// (far2c_role) of slice q - 1 of window W = n / kFarT + 1 at q = n mod kFarT
-__host__ __device__ inline void persist_far_args(slice_args& a, int64_t n, int w, int U, int K, int fpl, cf* ff)
-{
-    constexpr int ns = kFarT - 2;
-    const int64_t W = n / kFarT + 1;
-    const int q = int(n % kFarT);
-    a.f1nwg = a.f2nwg = a.f3nwg = 0;
-    if (q < ns) {
-        a.f1wn = int(W);
-        far1_range_k(a, int(int64_t(q) * U / ns), int(int64_t(q + 1) * U / ns), K == 1 ? 0 : (W < K ? 2 : 1),
-                     int(W % K), K, fpl);
-    }
-    if (q >= 1 && q <= ns) {
-        a.f3u0 = int(int64_t(q - 1) * U / ns);
-        a.f3nwg = int(int64_t(q) * U / ns) - a.f3u0;
-        a.f3wn = int(W);
-        a.f2grp = K > 1;
-        a.f3ff = ff + (W & 1) * int64_t(a.C) * ff_cs(a.B);
-        const int64_t t = (int64_t(w) + W * kFarT - n) % a.ring;
-        a.f2tw = int(t < 0 ? t + a.ring : t);
-        a.f2comb = 1;
-    }
-}
-
 // device buffers of the level pipeline (allocated on the first streaming step), all or none
 static int lvl_buffers(upols_t* h)
 {
     if (h->lv_ready) return NEO_HIP_OK;
-    const level_plan& lp = h->lv;
+    const level_plan& lp = h->sched.lv;
     const size_t C = size_t(h->C), B = size_t(h->B);
     std::vector<void**> got;
     auto alloc = [&](void** p, size_t bytes) {
@@ -1831,10 +1591,10 @@ static int lvl_buffers(upols_t* h)
     if (lp.nseg) {
         const size_t spec = C * size_t(spec_cs(lp.nseg, int(B))) * sizeof(cf);
         const size_t ffb = 2 * C * size_t(ff_cs(int(B))) * sizeof(cf);
-        if (!h->far_raw) {  // the stored form: segment and row-pair spectra, phase 1 -> 2 partial sums
+        if (!h->sched.far_raw) {  // the stored form: segment and row-pair spectra, phase 1 -> 2 partial sums
             if (!alloc(reinterpret_cast<void**>(&h->fv_hf), spec)) return undo("far segment spectra", spec);
             if (!alloc(reinterpret_cast<void**>(&h->fv_xf), spec)) return undo("far FDL spectra", spec);
-            const size_t accb = size_t(far_group(h)) * size_t(far_units(h)) * kFN * 16 * sizeof(cf);
+            const size_t accb = size_t(far_group(h->sched)) * size_t(far_units(h->sched)) * kFN * 16 * sizeof(cf);
             if (!alloc(reinterpret_cast<void**>(&h->fv_acc), accb)) return undo("far partial sums", accb);
         }
         if (!alloc(reinterpret_cast<void**>(&h->fv_ff), ffb)) return undo("far field", ffb);
@@ -1878,32 +1638,7 @@ void lvl_filter_changed(upols_t* h)
     h->lv_n = -1;
 }
 
-static int ring_add(int64_t r, int64_t d, int R) { return int(((r + d) % R + R) % R); }
-
-// Toeplitz role geometry per window T (k_lvl_step's level roles): window parts per column
-// group and units per workgroup. T = 32 splits its window in two where a step has fewer than
-// 8 of its units (few channels: the part halves the step's longest chain).
-int toep_split_for(int C, int B) { return C * (B / 16) < 8 * 32 ? 2 : 1; }
-
-// steps per background launch of the level slices (launch_levels): 4 from kStepGroupUnits
-// 16-column units (same-box A/B, ms per step at G = 1 / 4: C5 0.0183 / 0.0165, C4 0.0155 / 0.0134,
-// c5full 0.1213 / 0.1215 with the host round trip per block 133 -> 63 us; at one channel, C3, the
-// block launch and the cross-stream waits cost more than the overlap gives: 0.0063 / 0.0083)
-constexpr int64_t kStepGroupUnits = 2048;
-
 int bg_pad_for(int C, int B) { return int64_t(C) * (B / 16) <= 4096 ? 1024 : 0; }
-
-int step_group_for(int C, int B, int P)
-{
-    (void)P;
-    return int64_t(C) * (B / 16) >= kStepGroupUnits && B <= 1024 ? 4 : 1;
-}
-
-static void toep_geom(const upols_t* h, int T, int& JH, int& UPW)
-{
-    JH = T == kBigT ? kBigJH : (T == 32 ? (h->toep_jh ? h->toep_jh : toep_split_for(h->C, h->B)) : 1);
-    UPW = T <= 8 ? 16 : (T <= 32 ? 32 / T : 1);  // toep_role<T, 2T, 1, 1>: 16 units; toep_tile: 32 / T
-}
 
 static slice_args base_args(const upols_t* h)
 {
@@ -1915,23 +1650,37 @@ static slice_args base_args(const upols_t* h)
     a.B = h->B;
     a.cstride = h->cstride;
     a.pstride = h->pstride;
-    if (h->lv.nseg) {
-        a.M = h->lv.nseg;
-        a.nseg = h->lv.nseg;
-        a.fsc = spec_cs(h->lv.nseg, h->B);
+    if (h->sched.lv.nseg) {
+        a.M = h->sched.lv.nseg;
+        a.nseg = h->sched.lv.nseg;
+        a.fsc = spec_cs(h->sched.lv.nseg, h->B);
         a.fcs = ff_cs(h->B);
         a.fnfresh = 1;
-        a.fU = int(far_units(h));
-        a.fK = far_group(h);
+        a.fU = int(far_units(h->sched));
+        a.fK = far_group(h->sched);
         a.f1acc = h->fv_acc;
         a.f2acc = h->fv_acc;
         a.hf = h->fv_hf;
         a.xf = h->fv_xf;
         a.twf = h->fv_tw;
         a.P = h->P;
-        a.fA = h->lv.farA;
+        a.fA = h->sched.lv.farA;
     }
     return a;
+}
+
+// the pointer fields the schedule named by buffer and row (level_sel): the handle's slabs and far field
+static void bind(const upols_t* h, const level_sel& sel, slice_args& a)
+{
+    const level_plan& lp = h->sched.lv;
+    const int64_t C = h->C, B = h->B;
+    for (int l = 0; l < lp.n; ++l) {
+        const int64_t cs = slab_cs(lp.T[l], h->B);
+        if (sel.tp[l] >= 0) a.tp[l].slab = h->lv_slab[l] + sel.tp[l] * C * cs;
+        if (sel.sl[l] >= 0) a.sl[l] = h->lv_slab[l] + sel.sl[l] * C * cs + sel.sl_row[l] * B;
+    }
+    if (sel.ff >= 0) a.ff = h->fv_ff + sel.ff * C * ff_cs(h->B) + sel.ff_row * B;
+    if (sel.f3 >= 0) a.f3ff = h->fv_ff + sel.f3 * C * ff_cs(h->B);
 }
 
 #ifdef NEO_TIMELINE
@@ -1971,7 +1720,7 @@ static int launch_step_kernel(const upols_t* h, const slice_args& a_in, hipStrea
 #endif
     // pairs-only build where the window group is <= 2 (fewer VGPRs: every shape below
     // kFarGroupUnits), else the build for any group
-    const bool pairs = a.fK <= 2, raw = h->far_raw;
+    const bool pairs = a.fK <= 2, raw = h->sched.far_raw;
     if (part == 1) {
 #define NEO_BLK(OL, ST)                                                                                           \
     NEO_UPOLS_DISPATCH(h->B, if constexpr (BB <= 1024) hipLaunchKernelGGL((k_lvl_block<BB, OL, ST>), dim3(grid), \
@@ -2012,325 +1761,19 @@ static int launch_step_kernel(const upols_t* h, const slice_args& a_in, hipStrea
     return NEO_HIP_OK;
 }
 
-// The far level's units are cut into slices per window. G = 1: kFarT - 1 slices, slice q of
-// window W runs phase 1 and 2a at step q of window W - 1 (2a reads FDL rows up to the last block
-// before that window) and 2b at step q + 1 (<= the window's last: the far field is complete when
-// window W's first block runs). G > 1 (step groups, slice_part): kFarT / G - 2 slices, phase 1
-// of slice q at step group q + 1 of window W - 1 (its launch waits only for the blocks before the
-// previous group), phase 2 (far2c_role: 2a and 2b in one workgroup) at group q + 2.
-static int far_nslices(const upols_t* h) { return h->sg == 1 ? kFarT - 1 : kFarT / h->sg - 2; }
-
-static int far_u(int64_t U, int q, int ns) { return int(q * U / ns); }
-
-// the first unit of far slice q: step groups take the planned cuts (part_plan), G = 1 equal slices
-static int far_cut(const upols_t* h, int q)
+// a launch whose records the schedule filled: pointers bound, then launched
+static int launch_bound(const upols_t* h, slice_args& a, const level_sel& sel, hipStream_t s, int part = 0, int piece = 0,
+                        int pieces = 1)
 {
-    if (!h->fv_cut.empty()) return h->fv_cut[size_t(q)];
-    return far_u(int64_t(h->C) * (h->B / 16), q, h->sg == 1 ? kFarT - 1 : kFarT / h->sg - 2);
-}
-
-// far phase 1 for slice q of window W: the unit groups of class W mod K for the windows
-// W .. W + K - 1 (far1_mac); in the first windows after priming (W < K) the classes that have
-// not started, for window W alone
-static void far1_args(const upols_t* h, int64_t W, int q, slice_args& a)
-{
-    const int K = far_group(h);
-    a.f1wn = int(W);
-    far1_range(h, a, far_cut(h, q), far_cut(h, q + 1), K == 1 ? 0 : (W < K ? 2 : 1), int(W % K));
-}
-
-// the recomputed far level's slice q of window W (far2r_role), issued at step n (block t0 + n at
-// ring row w): every unit of the slice computes the window's field from rows before t_W - 128
-static void far_raw_args(const upols_t* h, int64_t W, int q, int w, int64_t n, slice_args& a)
-{
-    a.f3u0 = far_cut(h, q);
-    a.f3nwg = far_cut(h, q + 1) - a.f3u0;
-    a.f3wn = int(W);
-    a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
-    a.f2tw = ring_add(w, W * kFarT - n, h->ring);
-    a.f2comb = 2;
-}
-
-// Step groups: the background levels' window offsets and part sizes. A window's first group
-// carries none of its level's parts (they read the window's rows), so with every window starting at
-// a multiple of its length the groups at multiples of 8 (G = 4) had no Toeplitz work at all and
-// the odd ones all of the 8-block level's: background launches of 0.9 to 2.1 GB at c5full, and a
-// 20-step sample of the stream 5-8 % above or below the far window's mean. So a level of window
-// T >= 4 G (up to 32 blocks: its prime reads at most 16 rows further back) starts its windows half a
-// window later (phi = T / 2; still at even groups, which the events need), which puts the groups it
-// skips apart from every other level's (2 G: odd groups carry it, 4 G: skips 2 mod 4, 8 G: 4 mod 8,
-// the far level: 0 mod kFarT / G); and each window's units are cut into parts of unequal sizes so
-// that, over a cycle of groups (the far window, else the longest level window), every group's
-// background bytes come as close to equal as the slots allow: min-max water filling of one window
-// at a time against the rest (the far slices' bytes fixed), swept until it settles.
-static int part_phi(int T, int G, bool bg) { return bg && G > 1 && T >= 4 * G && T <= 32 ? T / 2 : 0; }
-
-struct part_level {
-    int T = 0, UPW = 1;
-    bool bg = false;
-    int64_t U = 0;
-    double wbytes = 0;  // bytes per window
-};
-
-// phi, cycle length (groups), cuts [k][j] (k < cyc / (T / G) windows of the cycle, j <= T / G - 1)
-// per level and the far slices' unit cuts fcut[0 .. ns] (ns > 0); loads: the predicted background
-// bytes per group of the cycle (null: not wanted). balance = false: equal parts, no offsets.
-static void part_plan(const part_level* lv, int nl, int G, int64_t FU, int ns, double c1, double c2, bool far_raw,
-                      bool balance, int* phi, int& cyc, std::vector<int>* cut, std::vector<int>& fcut,
-                      std::vector<double>* loads)
-{
-    cyc = 1;
-    for (int l = 0; l < nl; ++l) {
-        phi[l] = balance ? part_phi(lv[l].T, G, lv[l].bg) : 0;
-        cut[l].clear();
-        if (lv[l].bg) cyc = std::max(cyc, lv[l].T / G);
-    }
-    if (ns) cyc = std::max(cyc, kFarT / G);
-    // the far slices (slice_part): slice q's phase 1 at group q + 1, phase 2 at q + 2 (recomputed:
-    // all of it at q + 2), s[q] units each
-    std::vector<double> fs(size_t(ns), ns ? double(FU) / ns : 0.0), load(size_t(cyc), 0.0);
-    auto far_add = [&](std::vector<double>& L, const std::vector<double>& sq, double sign) {
-        for (int q = 0; q < ns; ++q) {
-            if (!far_raw) L[size_t(q + 1)] += sign * c1 * sq[size_t(q)];
-            L[size_t(q + 2)] += sign * c2 * sq[size_t(q)];
-        }
-    };
-    far_add(load, fs, 1.0);
-    struct win {
-        int l, np;
-        double c;
-        std::vector<int> grp;
-        std::vector<double> x;  // units per part
-    };
-    std::vector<win> ws;
-    for (int l = 0; l < nl; ++l) {
-        if (!lv[l].bg || lv[l].U <= 0) continue;
-        const int Tg = lv[l].T / G, np = Tg - 1, s0 = ((-phi[l] / G) % Tg + Tg) % Tg;
-        for (int k = 0; k < cyc / Tg; ++k) {
-            win w{l, np, lv[l].wbytes / double(lv[l].U), {}, std::vector<double>(size_t(np), double(lv[l].U) / np)};
-            for (int j = 1; j <= np; ++j) w.grp.push_back((s0 + k * Tg + j) % cyc);
-            for (int j = 0; j < np; ++j) load[size_t(w.grp[size_t(j)])] += w.c * w.x[size_t(j)];
-            ws.push_back(std::move(w));
-        }
-    }
-    std::vector<double> base, sb, grad, y;
-    for (int round = 0; round < (balance ? 4 : 0); ++round) {
-        // the Toeplitz windows, one at a time against the rest: min-max water filling
-        for (int sweep = 0; sweep < 32; ++sweep)
-            for (auto& w : ws) {
-                const int np = w.np;
-                base.assign(size_t(np), 0.0);
-                for (int j = 0; j < np; ++j) {
-                    load[size_t(w.grp[size_t(j)])] -= w.c * w.x[size_t(j)];
-                    base[size_t(j)] = load[size_t(w.grp[size_t(j)])];
-                }
-                sb = base;
-                std::sort(sb.begin(), sb.end());
-                const double total = w.c * double(lv[w.l].U);
-                double h = sb[0], acc = 0;  // water level: sum of max(0, h - base) = the window's bytes
-                for (int i = 0; i < np; ++i) {
-                    const double next = i + 1 < np ? sb[size_t(i + 1)] : 1e300;
-                    const double need = (next - sb[size_t(i)]) * (i + 1);
-                    if (acc + need >= total) {
-                        h = sb[size_t(i)] + (total - acc) / (i + 1);
-                        break;
-                    }
-                    acc += need;
-                }
-                for (int j = 0; j < np; ++j) {
-                    w.x[size_t(j)] = std::max(0.0, h - base[size_t(j)]) / w.c;
-                    load[size_t(w.grp[size_t(j)])] += w.c * w.x[size_t(j)];
-                }
-            }
-        if (!ns) break;
-        // the far slices against the rest: least squares around the mean, projected gradient on
-        // {s >= 0, sum s = FU} (the min-max recurrence is unstable: phase 2 bytes > phase 1's)
-        double mean = 0;
-        for (double v : load) mean += v;
-        mean /= cyc;
-        const double eta = 1.0 / (2.0 * (c1 + c2) * (c1 + c2));
-        for (int it = 0; it < 400; ++it) {
-            grad.assign(size_t(ns), 0.0);
-            for (int q = 0; q < ns; ++q) {
-                if (!far_raw) grad[size_t(q)] += 2 * c1 * (load[size_t(q + 1)] - mean);
-                grad[size_t(q)] += 2 * c2 * (load[size_t(q + 2)] - mean);
-            }
-            far_add(load, fs, -1.0);
-            y.resize(size_t(ns));
-            for (int q = 0; q < ns; ++q) y[size_t(q)] = fs[size_t(q)] - eta * grad[size_t(q)];
-            sb = y;  // projection onto the simplex: subtract tau, clip at 0
-            std::sort(sb.begin(), sb.end(), std::greater<double>());
-            double cs = 0, tau = 0;
-            for (int i = 0; i < ns; ++i) {
-                cs += sb[size_t(i)];
-                const double t = (cs - double(FU)) / (i + 1);
-                if (sb[size_t(i)] - t > 0) tau = t;
-            }
-            for (int q = 0; q < ns; ++q) fs[size_t(q)] = std::max(0.0, y[size_t(q)] - tau);
-            far_add(load, fs, 1.0);
-        }
-    }
-    for (int l = 0; l < nl; ++l)
-        if (lv[l].bg) cut[l].assign(size_t(cyc / (lv[l].T / G) * (lv[l].T / G)), 0);
-    std::vector<int> kcount(size_t(nl), 0);
-    for (const auto& w : ws) {  // cuts on workgroup multiples, the last at U
-        const int64_t U = lv[w.l].U, q = lv[w.l].UPW;
-        int* c = cut[w.l].data() + size_t(kcount[size_t(w.l)]++) * size_t(w.np + 1);
-        double cum = 0;
-        c[0] = 0;
-        for (int j = 1; j <= w.np; ++j) {
-            cum += w.x[size_t(j - 1)];
-            const int64_t r = j == w.np ? U : std::min<int64_t>(U, std::llround(cum / double(q)) * q);
-            c[j] = int(std::max<int64_t>(c[j - 1], r));
-        }
-    }
-    fcut.assign(ns ? size_t(ns + 1) : 0, 0);
-    if (ns) {
-        double cum = 0;
-        for (int q = 1; q <= ns; ++q) {
-            cum += fs[size_t(q - 1)];
-            const int64_t r = q == ns ? FU : std::min<int64_t>(FU, std::llround(cum));
-            fcut[size_t(q)] = int(std::max<int64_t>(fcut[size_t(q - 1)], r));
-        }
-    }
-    if (loads) {  // from the integer cuts
-        loads->assign(size_t(cyc), 0.0);
-        std::vector<double> fi(static_cast<size_t>(ns));
-        for (int q = 0; q < ns; ++q) fi[size_t(q)] = double(fcut[size_t(q + 1)] - fcut[size_t(q)]);
-        far_add(*loads, fi, 1.0);
-        std::fill(kcount.begin(), kcount.end(), 0);
-        for (const auto& w : ws) {
-            const int* c = cut[w.l].data() + size_t(kcount[size_t(w.l)]++) * size_t(w.np + 1);
-            for (int j = 1; j <= w.np; ++j) (*loads)[size_t(w.grp[size_t(j - 1)])] += w.c * double(c[j] - c[j - 1]);
-        }
-    }
-}
-
-static int64_t toep_units(const upols_t* h, int T);
-static bool block_level(const upols_t* h, int T);
-static int far_group(const upols_t* h);
-
-// staggered windows: level l has classes of its own (plan_levels_stag)
-static bool stag_level(const level_plan& lp, int l) { return lp.stag && lp.T[l] >= 4 * lp.stag; }
-static bool stag_far(const level_plan& lp) { return lp.stag && lp.nseg; }
-static int log2i(int v) { return v <= 1 ? 0 : 1 + log2i(v >> 1); }
-static unsigned long long stag_mul(const upols_t* h) { return ((64ull / unsigned(h->lv.stag)) << 30) / unsigned(h->C); }
-
-// The staggered levels' classes: every background launch carries one class of every staggered
-// level, phase 2 of one far class and phase 1 of the next, the same work in every group -- but the
-// aligned levels of window 2 G ride on the odd groups alone (X bytes per two groups). Classes come
-// in pairs of an even and an odd one (class parity = group parity of its Toeplitz slice and both
-// its far phases), so the even classes take the share e / 2 of every pair with e = 1 + X / (2 D),
-// D the staggered bytes per group: both parities then carry the same bytes. Classes are whole
-// channels, so the far level (the most classes) takes its share first and every level after it
-// the rest that the rounding of those before it left.
-static void stag_classes(upols_t* h, std::vector<double>* loads)
-{
-    const level_plan& lp = h->lv;
-    const int G = lp.stag, C = h->C;
-    const double col = double(h->B) * 8;  // bytes of one row of one channel
-    double X = 0, St = 0, c1 = 0, c2 = 0;
-    for (int l = 0; l < lp.n; ++l) {
-        const double wb = col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);  // per channel and window
-        if (stag_level(lp, l)) St += wb * G / lp.T[l];
-        else if (!block_level(h, lp.T[l]) && lp.T[l] == 2 * G) X += wb;
-    }
-    if (lp.nseg) {
-        const int K = far_group(h);
-        c1 = col * (256.0 * 2 * (lp.nseg - 1) / K + 256) * G / kFarT;
-        c2 = col * (256.0 * (3 + K - 1) + 128 + 256) * G / kFarT;
-    }
-    double Drest = St + c2 + c1, Xrest = X;  // what the levels not yet cut can still move
-    const unsigned long long M = stag_mul(h);
-    auto cuts = [&](int T, double Dl, std::vector<int>& cut) {
-        const int ncls = T / G, sh = log2i(kFarT / T);
-        const double e = Drest > 0 ? std::max(0.5, std::min(1.5, 1.0 + Xrest / (2.0 * Drest))) : 1.0;
-        const int ef = int(std::lround(512.0 * e));
-        cut.assign(size_t(ncls) + 1, C);
-        cut[0] = 0;
-        for (int c = C - 1; c >= 0; --c) {
-            const int k = stag_class(M, ef, c, sh);
-            for (int j = k; j >= 1 && cut[size_t(j)] > c; --j) cut[size_t(j)] = c;  // first channel of class >= j
-        }
-        int even = 0;
-        for (int k = 0; k < ncls; k += 2) even += cut[size_t(k) + 1] - cut[size_t(k)];
-        Xrest -= (4.0 * even / C - 2.0) * Dl;  // the share the whole channels gave
-        Drest -= Dl;
-        return ef;
-    };
-    h->st_fcut.clear();
-    h->st_fef = 512;
-    if (lp.nseg) h->st_fef = cuts(kFarT, c1 + c2, h->st_fcut);
-    for (int l = lp.n - 1; l >= 0; --l) {
-        h->st_cut[l].clear();
-        h->st_ef[l] = 512;
-        if (stag_level(lp, l))
-            h->st_ef[l] = cuts(lp.T[l], col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1) * G / lp.T[l], h->st_cut[l]);
-    }
-    if (loads) {  // predicted background bytes per group over the far window, from the integer cuts
-        const int cyc = kFarT / G;
-        loads->assign(size_t(cyc), 0.0);
-        for (int g = 0; g < cyc; ++g) {
-            double& L = (*loads)[size_t(g)];
-            for (int l = 0; l < lp.n; ++l) {
-                const double wb = col * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);
-                if (stag_level(lp, l)) {
-                    const int k = g % (lp.T[l] / G);
-                    L += wb * (h->st_cut[l][size_t(k) + 1] - h->st_cut[l][size_t(k)]);
-                } else if (!block_level(h, lp.T[l])) {  // aligned: equal parts at the window's groups 1 .. T / G - 1
-                    const int Tg = lp.T[l] / G, j = ((g * G + part_phi(lp.T[l], G, true)) % lp.T[l]) / G;
-                    if (j >= 1) L += wb * C / (Tg - 1);
-                }
-            }
-            if (lp.nseg) {
-                const int k2 = g % cyc, k1 = (g + 2) % cyc;
-                L += c2 * kFarT / G * (h->st_fcut[size_t(k2) + 1] - h->st_fcut[size_t(k2)]);
-                L += c1 * kFarT / G * (h->st_fcut[size_t(k1) + 1] - h->st_fcut[size_t(k1)]);
-            }
-        }
-    }
-}
-
-// the handle's plan (lvl_prime): levels, far slices and their bytes as bench.algorithmic_bytes
-// counts them
-static void plan_handle_parts(upols_t* h, std::vector<double>* loads = nullptr, bool balance = true)
-{
-    const level_plan& lp = h->lv;
-    part_level pl[kLvToep];
-    const double CB = double(h->C) * h->B;
-    for (int l = 0; l < lp.n; ++l) {
-        int JH, UPW;
-        toep_geom(h, lp.T[l], JH, UPW);
-        pl[l].T = lp.T[l];
-        pl[l].UPW = UPW;
-        pl[l].bg = h->sg > 1 && !h->persist && !block_level(h, lp.T[l]) && !stag_level(lp, l);  // latency mode: its own schedule
-        pl[l].U = toep_units(h, lp.T[l]);
-        pl[l].wbytes = CB * 8 * (2.0 * (lp.b[l] - lp.a[l]) + 2 * lp.T[l] - 1);
-    }
-    const int ns = h->sg > 1 && !h->persist && lp.nseg && !lp.stag ? far_nslices(h) : 0;
-    const int64_t FU = far_units(h);
-    double c1 = 0, c2 = 0;  // bytes per far unit (16 columns) of phase 1 and 2 per window
-    if (ns) {
-        const int K = far_group(h), nseg = lp.nseg;
-        if (h->far_raw) {
-            c2 = 16.0 * 8 * ((nseg + 1) * 128.0 + (h->P - 256) + 128);
-        } else {
-            c1 = 16.0 * 8 * (256.0 * 2 * (nseg - 1) / K + 256);     // stored spectra, partial sums out
-            c2 = 16.0 * 8 * (256.0 * (3 + K - 1) + 128 + 256);       // fresh pair, products, field, sums in
-        }
-    }
-    part_plan(pl, lp.n, h->sg, FU, ns, c1, c2, h->far_raw, balance, h->lv_phi, h->lv_cyc, h->lv_cut, h->fv_cut,
-              lp.stag ? nullptr : loads);
-    if (lp.stag) stag_classes(h, loads);
+    bind(h, sel, a);
+    return launch_step_kernel(h, a, s, part, piece, pieces);
 }
 
 // The block role of step n (block t0 + n at FDL ring row w) for the channels [c0, c0 + nc): its
-// slab row of every Toeplitz level and its far-field row (windows finished in earlier launches)
+// blocks, and its slab and far-field rows (block_rows)
 static void block_part(const upols_t* h, int64_t n, int w, int c0, int nc, const float* in, int64_t ld_in, float* out,
-                       int64_t ld_out, slice_args& a)
+                       int64_t ld_out, slice_args& a, level_sel& sel)
 {
-    const level_plan& lp = h->lv;
-    const int B = h->B, C = h->C;
     a.nblk = nc;
     a.blk_c0 = c0;
     a.in = in;
@@ -2340,201 +1783,7 @@ static void block_part(const upols_t* h, int64_t n, int w, int c0, int nc, const
     a.prev = h->prev;
     a.twg = h->tw;
     a.w = w;
-    a.a0 = lp.a0;
-    if (lp.stag) {  // the block role picks the row by the channel's class
-        a.stag = lp.stag;
-        a.sM = stag_mul(h);
-        a.fef = h->st_fef;
-        a.snm = int(n % (2 * kFarT));
-    }
-    for (int l = 0; l < lp.n; ++l) {
-        const int T = lp.T[l];
-        const int64_t m = n + h->lv_phi[l];  // window m / T, its row m mod T
-        a.ssh[a.nsl] = stag_level(lp, l) ? log2i(kFarT / T) : -1;
-        a.sef[a.nsl] = h->st_ef[l];
-        a.sl[a.nsl] = stag_level(lp, l) ? h->lv_slab[l] : h->lv_slab[l] + (m / T & 1) * C * slab_cs(T, B) + (m % T) * B;
-        a.scs[a.nsl++] = slab_cs(T, B);
-    }
-    if (lp.nseg) {
-        a.fsh = lp.stag ? 0 : -1;
-        a.ff = lp.stag ? h->fv_ff : h->fv_ff + (n / kFarT & 1) * C * ff_cs(B) + (n % kFarT) * B;
-        a.fcs = ff_cs(B);
-    }
-}
-
-// A Toeplitz level's slice: units [u0, u1) of window W (first block t0 + W T) into its slab buffer
-static void toep_slice(const upols_t* h, int l, int64_t W, int64_t u0, int64_t u1, int64_t n, int w, slice_args& a)
-{
-    const int T = h->lv.T[l];
-    int JH, UPW;
-    toep_geom(h, T, JH, UPW);
-    toep_arg& ta = a.tp[l];  // slot l = level l (the kernel dispatches on it), empty slices allowed
-    ta.u0 = int(u0);
-    ta.u1 = int(u1);
-    ta.slab = h->lv_slab[l] + (W & 1) * h->C * slab_cs(T, h->B);
-    ta.cs = slab_cs(T, h->B);
-    ta.T = T;
-    ta.a = h->lv.a[l];
-    ta.b = h->lv.b[l];
-    ta.tw = ring_add(w, W * T - n, h->ring);  // block t0 + n at row w
-    ta.nwg = ta.u1 > ta.u0 ? (ta.u1 - ta.u0 + UPW - 1) / UPW : 0;
-    ta.jh = JH;
-    a.ntp = std::max(a.ntp, l + 1);
-}
-
-// Far phase 2 at G = 1 in one workgroup per unit (far2c_role, one step after phase 1) or in
-// two (2a: the fresh transform -> its slot, beside phase 1; 2b: the products and the inverse one
-// step later). One workgroup reads the fresh spectrum back from registers instead of its slot,
-// fewer bytes; two halve the chain, which bounds the step where a step has few far units.
-// Step groups always run one (their background launches have a group of slack).
-constexpr int64_t kFarWholeUnits = 32768;  // 256 units per step
-
-static bool far2_whole(const upols_t* h)
-{
-    if (h->sg > 1) return true;
-    if (h->f2mode) return h->f2mode == 1;  // neo_hip_upols_opts.far_phase2
-    return far_units(h) >= kFarWholeUnits;
-}
-
-static int64_t toep_units(const upols_t* h, int T)
-{
-    int JH, UPW;
-    toep_geom(h, T, JH, UPW);
-    return int64_t(h->C) * (h->B / 16) * JH;
-}
-
-// Step groups: the Toeplitz levels stepped in the block launches, 1/T of the next window per step
-// (the others in the background launches, T / G - 1 parts per window). T < 2 G must (a background
-// launch may not read the blocks of its own group); larger windows may (diagnostic builds).
-#ifndef NEO_BLOCK_TMAX
-#define NEO_BLOCK_TMAX 0
-#endif
-static bool block_level(const upols_t* h, int T) { return T < 2 * h->sg || T <= NEO_BLOCK_TMAX; }
-
-// The slices the launch of step n (block t0 + n at ring row w) carries. G = 1: slice n mod T of
-// window n / T + 1 of every Toeplitz level (its rows end before the window in progress, so every
-// window's slabs are complete when its first block runs) and, with q = n mod 128 and W = n / 128 + 1,
-// far phase 1 and 2a of slice q (q < 127) and far phase 2b of slice q - 1 (q >= 1) of window W.
-// G > 1, block launches: the levels with T < 2 G, as for G = 1.
-static void block_levels(const upols_t* h, int64_t n, int w, slice_args& a)
-{
-    for (int l = 0; l < h->lv.n; ++l) {
-        const int T = h->lv.T[l];
-        if (h->sg > 1 && !block_level(h, T)) break;
-        const int64_t U = toep_units(h, T), st = n % T;
-        toep_slice(h, l, n / T + 1, st * U / T, (st + 1) * U / T, n, w, a);
-    }
-    if (h->sg > 1 || !h->lv.nseg) return;
-    const int64_t U = far_units(h), W = n / kFarT + 1;
-    const int q = int(n % kFarT), ns = far_nslices(h);
-    if (h->far_raw) {  // recomputed: slice q - 1 of window W whole (far2r_role)
-        if (q >= 1 && q <= ns) far_raw_args(h, W, q - 1, w, n, a);
-        return;
-    }
-    if (far2_whole(h)) {  // phase 1 of slice q, phase 2 (far2c_role) of slice q - 1
-        if (q < ns) far1_args(h, W, q, a);
-        if (q >= 1 && q <= ns) {
-            a.f3u0 = far_u(U, q - 1, ns);
-            a.f3nwg = far_u(U, q, ns) - a.f3u0;
-            a.f3wn = int(W);
-            a.f2grp = far_group(h) > 1;
-            a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
-            a.f2tw = ring_add(w, W * kFarT - n, h->ring);
-            a.f2comb = 1;
-        }
-        return;
-    }
-    if (q < ns) {
-        a.f2u0 = far_u(U, q, ns);
-        a.f2nwg = far_u(U, q + 1, ns) - a.f2u0;
-        a.f2tw = ring_add(w, W * kFarT - n, h->ring);
-        a.f2wn = int(W);
-        far1_args(h, W, q, a);
-    }
-    if (q >= 1) {
-        a.f3u0 = far_u(U, q - 1, ns);
-        a.f3nwg = far_u(U, q, ns) - a.f3u0;
-        a.f3wn = int(W);
-        a.f2grp = far_group(h) > 1;
-        a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
-    }
-}
-
-// G > 1: the background launch issued at step n0 (a multiple of G; block t0 + n0 at ring row w0).
-// It may read only the blocks before n0 - G (it waits for those, not for the group before it), and
-// the block launch of step n0 + G waits for it. So a level of window T >= 2 G computes window W + 1
-// in T / G - 1 parts at the steps t_W + G j, j = 1 .. T / G - 1 (part j - 1; its rows end at t_W - 1),
-// the last due one group before t_{W+1}; the far level's slice q (kFarT / G - 2 of them) runs
-// phase 1 at group q + 1 and phase 2 (2a and 2b in one workgroup) at group q + 2 of the window before.
-// Staggered windows (plan_levels_stag): the launch of group g = n0 / G carries class g mod T / G of
-// every staggered level, whole, for the window starting at s = n0 + 2 G; of the far level phase 2
-// of class g mod 128 / G for its window starting at s and phase 1 of the class after the next, whose
-// window starts two groups later (a class's two phases in groups of one parity). n0 < 0: the launches before step 0 that priming replays (lvl_prime) --
-// only the staggered roles, and only windows that start after step 0.
-static void slice_part(const upols_t* h, int64_t n0, int w0, slice_args& a)
-{
-    const level_plan& lp = h->lv;
-    const int G = h->sg;
-    const int64_t g = n0 / G;  // n0 is a multiple of G
-    for (int l = 0; l < lp.n; ++l) {
-        const int T = lp.T[l], Tg = T / G;
-        if (block_level(h, T)) continue;  // in the block launches
-        if (stag_level(lp, l)) {
-            const int64_t s = n0 + 2 * G;
-            if (s <= 0) continue;
-            const int k = int((g % Tg + Tg) % Tg), phi = stag_phi(T, G, k);
-            int JH, UPW;
-            toep_geom(h, T, JH, UPW);
-            const int64_t upc = int64_t(h->B / 16) * JH;  // units per channel
-            toep_slice(h, l, (s + phi) / T, h->st_cut[l][size_t(k)] * upc, h->st_cut[l][size_t(k) + 1] * upc, n0 + phi, w0, a);
-            continue;
-        }
-        if (n0 < 0) continue;
-        const int64_t m0 = n0 + h->lv_phi[l], j = (m0 % T) / G, W = m0 / T;  // group j of window W
-        if (j < 1) continue;
-        const int64_t gw = (W * T - h->lv_phi[l]) / G, cyc = h->lv_cyc;  // window W's first group
-        const int k = int((gw % cyc + cyc) % cyc / Tg);
-        const int* cut = h->lv_cut[l].data() + size_t(k) * size_t(Tg);  // the window's cuts [0, Tg)
-        toep_slice(h, l, W + 1, cut[j - 1], cut[j], m0, w0, a);  // tw from m0: block t_{W+1} = (W + 1) T - phi
-    }
-    if (stag_far(lp)) {
-        const int nc = kFarT / G, gpc = h->B / 16, K = far_group(h);
-        const int64_t s2 = n0 + 2 * G, s1 = n0 + 4 * G;
-        if (s1 > 0) {  // phase 1 of the class whose phase 2 runs two launches later (the same group parity)
-            const int k = int(((g + 2) % nc + nc) % nc);
-            const int64_t W = (s1 + stag_phi(kFarT, G, k)) / kFarT;
-            a.f1wn = int(W);
-            far1_range(h, a, h->st_fcut[size_t(k)] * gpc, h->st_fcut[size_t(k) + 1] * gpc, K == 1 ? 0 : (W < K ? 2 : 1),
-                       int(W % K));
-        }
-        if (s2 > 0) {  // phase 2, 2a and 2b in one workgroup per unit (far2c_role)
-            const int k = int((g % nc + nc) % nc);
-            const int64_t W = (s2 + stag_phi(kFarT, G, k)) / kFarT;
-            a.f3u0 = h->st_fcut[size_t(k)] * gpc;
-            a.f3nwg = h->st_fcut[size_t(k) + 1] * gpc - a.f3u0;
-            a.f3wn = int(W);
-            a.f2grp = K > 1;
-            a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
-            a.f2tw = ring_add(w0, 2 * G, h->ring);
-            a.f2comb = 1;
-        }
-    } else if (lp.nseg && h->far_raw) {  // recomputed: slice q - 2 of window W whole, at phase 2's time
-        const int q = int(n0 % kFarT) / G;
-        if (q >= 2 && q - 2 < far_nslices(h)) far_raw_args(h, n0 / kFarT + 1, q - 2, w0, n0, a);
-    } else if (lp.nseg) {
-        const int64_t W = n0 / kFarT + 1;
-        const int q = int(n0 % kFarT) / G, ns = far_nslices(h);
-        if (q >= 1 && q <= ns) far1_args(h, W, q - 1, a);  // phase 1 of slice q - 1
-        if (q >= 2) {  // phase 2 of slice q - 2, 2a and 2b in one workgroup per unit (far2c_role)
-            a.f3u0 = far_cut(h, q - 2);
-            a.f3nwg = far_cut(h, q - 1) - a.f3u0;
-            a.f3wn = int(W);
-            a.f2grp = far_group(h) > 1;
-            a.f3ff = h->fv_ff + (W & 1) * h->C * ff_cs(h->B);
-            a.f2tw = ring_add(w0, W * kFarT - n0, h->ring);
-            a.f2comb = 1;
-        }
-    }
+    block_rows(h->sched, n, a, sel);
 }
 
 // The block role of step n (FDL ring row w) for channel c alone: the same slabs and far-field
@@ -2544,8 +1793,9 @@ int launch_block_only(upols_t* h, int64_t n, int w, int c, const float* in, floa
 {
     if (c < 0 || c >= h->C || n < 0) return fail(NEO_HIP_EINVAL, "block redo: channel %d / step %lld", c, (long long)n);
     slice_args a = base_args(h);
-    block_part(h, n, w, c, 1, in, 0, out, 0, a);
-    return launch_step_kernel(h, a, s, h->sg > 1 ? 1 : 0);
+    level_sel sel;
+    block_part(h, n, w, c, 1, in, 0, out, 0, a, sel);
+    return launch_bound(h, a, sel, s, h->sched.sg > 1 ? 1 : 0);
 }
 
 int lvl_join(upols_t* h, hipStream_t s)
@@ -2557,157 +1807,56 @@ int lvl_join(upols_t* h, hipStream_t s)
     return NEO_HIP_OK;
 }
 
-// First streaming step after a reset / filter change / batched pass (block t0 at ring row w):
-// window 0 of every level, starting at t0, computed whole (all units; the far level
-// transforms every segment: phase 1 and 2a in the levels' launch, 2b in a second one).
+// First streaming step after a reset / filter change / batched pass (block t0 at ring row
+// h->wpos): the far segment spectra if the filter changed, the plan of the background parts, then
+// window 0 of every level (prime_round, levels_plan.hpp), all on s.
 // After a reset or a filter change (fdl_zero) every FDL row before t0 is zero, and so is every
 // value the prime computes from them: Toeplitz windows 0 and 1 (slab[j] = sum over the band,
 // p >= 2T, of H[p] X[t_W + j - p]: rows before t0), the far window's row-pair spectra, partial
 // sums and field (rows t_W - 128 (q + 1) ... + 255 < t0). Then priming is zeroing the level
-// buffers (all of them: a superset of what the two launches write), a fraction of their time.
-// Staggered windows: class k's window 0 (the one that holds step 0) began phi_k steps ago, so the
-// classes prime one by one -- launch pair i takes class i of every staggered level and of the far
-// level (every segment transformed, 2b in the second launch) -- and then the background launches of
-// the groups -3 .. -1 run as they would have (slice_part: the windows that start at steps G .. 3 G,
-// far phase 1 two groups before phase 2), on the caller's stream: every row they read is before
-// step 0.
-static int lvl_prime_stag(upols_t* h, hipStream_t s)
-{
-    const level_plan& lp = h->lv;
-    const int B = h->B, w = h->wpos, G = lp.stag, gpc = B / 16;
-    const int nc = lp.nseg ? kFarT / G : (lp.n ? lp.T[lp.n - 1] / G : 0);
-    for (int i = 0; i < nc; ++i) {
-        slice_args a = base_args(h), f = base_args(h);
-        for (int l = 0; l < lp.n; ++l) {
-            if (!stag_level(lp, l) || i >= lp.T[l] / G) continue;
-            int JH, UPW;
-            toep_geom(h, lp.T[l], JH, UPW);
-            toep_arg& ta = a.tp[l];
-            ta.jh = JH;
-            ta.slab = h->lv_slab[l];
-            ta.cs = slab_cs(lp.T[l], B);
-            ta.T = lp.T[l];
-            ta.a = lp.a[l];
-            ta.b = lp.b[l];
-            ta.tw = ring_add(w, -stag_phi(lp.T[l], G, i), h->ring);
-            ta.u0 = h->st_cut[l][size_t(i)] * gpc * JH;
-            ta.u1 = h->st_cut[l][size_t(i) + 1] * gpc * JH;
-            ta.nwg = (ta.u1 - ta.u0 + UPW - 1) / UPW;
-            a.ntp = l + 1;
-        }
-        const int u0 = lp.nseg ? h->st_fcut[size_t(i)] * gpc : 0, u1 = lp.nseg ? h->st_fcut[size_t(i) + 1] * gpc : 0;
-        if (u1 > u0) {
-            a.fnfresh = lp.nseg;  // every segment transformed
-            a.f1wn = 0;
-            far1_range(h, a, u0, u1, 0, 0);  // zero partial sums (no stored segments)
-            a.f2u0 = u0;
-            a.f2nwg = u1 - u0;
-            a.f2tw = ring_add(w, -stag_phi(kFarT, G, i), h->ring);
-            a.f2wn = 0;
-            f.fnfresh = lp.nseg;
-            f.f3u0 = u0;
-            f.f3nwg = u1 - u0;
-            f.f3wn = 0;
-            f.f3ff = h->fv_ff;
-        }
-        if (int rc = launch_step_kernel(h, a, s)) return rc;
-        if (int rc = launch_step_kernel(h, f, s)) return rc;
-    }
-    for (int g = -3; g < 0; ++g) {
-        slice_args b = base_args(h);
-        slice_part(h, int64_t(g) * G, ring_add(w, int64_t(g) * G, h->ring), b);
-        if (int rc = launch_step_kernel(h, b, s, 2)) return rc;
-    }
-    return NEO_HIP_OK;
-}
-
+// buffers (all of them: a superset of what the launches write), a fraction of their time.
 static int lvl_prime(upols_t* h, hipStream_t s)
 {
-    const level_plan& lp = h->lv;
+    level_sched& sc = h->sched;
+    const level_plan& lp = sc.lv;
     const int B = h->B, C = h->C, w = h->wpos;
     if (int rc = lvl_join(h, s)) return rc;  // slices of an earlier run still in flight on bg
-    if (lp.nseg && h->fv_dirty && !h->far_raw) {
+    if (lp.nseg && h->fv_dirty && !sc.far_raw) {
         const unsigned grid = unsigned(C) * unsigned(lp.nseg) * unsigned(B / 16);
         hipLaunchKernelGGL(k_lvf_filter, dim3(grid), dim3(256), 0, s, h->H, h->fv_hf, h->fv_tw, B, h->P, lp.nseg,
                            h->cstride, h->pstride, 0, spec_cs(lp.nseg, B), lp.farA);
         NEO_HIP_LAUNCH_CHECK();
         h->fv_dirty = false;
     }
-    plan_handle_parts(h);  // window offsets and background part sizes (step groups)
+    plan_parts(sc);  // window offsets and background part sizes (step groups), classes (staggered windows)
     if (h->fdl_zero) {
         for (int l = 0; l < lp.n; ++l)
             NEO_HIP_CHECK(hipMemsetAsync(h->lv_slab[l], 0, 2 * size_t(C) * slab_cs(lp.T[l], B) * sizeof(cf), s));
         if (lp.nseg) {
-            if (!h->far_raw) {
+            if (!sc.far_raw) {
                 const size_t spec = size_t(C) * size_t(spec_cs(lp.nseg, B)) * sizeof(cf);
                 NEO_HIP_CHECK(hipMemsetAsync(h->fv_xf, 0, spec, s));
-                const size_t accb = size_t(far_group(h)) * size_t(far_units(h)) * kFN * 16 * sizeof(cf);
+                const size_t accb = size_t(far_group(sc)) * size_t(far_units(sc)) * kFN * 16 * sizeof(cf);
                 NEO_HIP_CHECK(hipMemsetAsync(h->fv_acc, 0, accb, s));
             }
             NEO_HIP_CHECK(hipMemsetAsync(h->fv_ff, 0, 2 * size_t(C) * ff_cs(B) * sizeof(cf), s));
         }
         return NEO_HIP_OK;
     }
-    slice_args a = base_args(h), f = base_args(h);  // f: the second launch (far 2b, offset windows 1)
-    bool f_any = false;
-    for (int l = 0; l < lp.n; ++l) {
-        int JH, UPW;
-        toep_geom(h, lp.T[l], JH, UPW);
-        toep_arg& ta = a.tp[a.ntp++];
-        if (stag_level(lp, l)) continue;  // class by class (lvl_prime_stag)
-        ta.jh = JH;
-        ta.slab = h->lv_slab[l];
-        ta.cs = slab_cs(lp.T[l], B);
-        ta.T = lp.T[l];
-        ta.a = lp.a[l];
-        ta.b = lp.b[l];
-        ta.tw = ring_add(w, -h->lv_phi[l], h->ring);  // window 0 holds step 0: it began phi steps ago
-        ta.u0 = 0;
-        ta.u1 = C * (B / 16) * JH;
-        ta.nwg = (ta.u1 + UPW - 1) / UPW;
-        if (h->lv_phi[l]) {  // and window 1 whole: its parts before step 0 never ran (the rest run again)
-            toep_arg& t1 = f.tp[l];
-            t1 = ta;
-            t1.slab = h->lv_slab[l] + size_t(C) * slab_cs(lp.T[l], B);
-            t1.tw = ring_add(w, lp.T[l] - h->lv_phi[l], h->ring);
-            f.ntp = l + 1;
-            f_any = true;
-        }
+    for (int r = 0; r < prime_rounds(sc); ++r) {  // two launches per round (an empty one is none)
+        slice_args a = base_args(h), f = base_args(h);
+        level_sel sa, sf;
+        prime_round(sc, r, w, a, sa, f, sf);
+        if (int rc = launch_bound(h, a, sa, s)) return rc;
+        if (int rc = launch_bound(h, f, sf, s)) return rc;
     }
-    if (lp.nseg && h->far_raw) {  // recomputed: window 0's field whole, every unit in the same launch
-        a.f3u0 = 0;
-        a.f3nwg = int(far_units(h));
-        a.f3wn = 0;
-        a.f3ff = h->fv_ff;
-        a.f2tw = w;
-        a.f2comb = 2;
+    for (int g = -3; lp.stag && g < 0; ++g) {  // staggered windows: on the caller's stream, every row before step 0
+        slice_args b = base_args(h);
+        level_sel sb;
+        slice_part(sc, int64_t(g) * lp.stag, ring_add(w, int64_t(g) * lp.stag, h->ring), b, sb);
+        if (int rc = launch_bound(h, b, sb, s, 2)) return rc;
     }
-    if (lp.stag) {
-        if (int rc = launch_step_kernel(h, a, s)) return rc;
-        if (f_any)
-            if (int rc = launch_step_kernel(h, f, s)) return rc;
-        return lvl_prime_stag(h, s);
-    }
-    if (lp.nseg && !h->far_raw) {  // far window 0: phase 1 and 2a of every unit beside the levels
-        const int U = int(far_units(h));
-        a.fnfresh = lp.nseg;  // every segment transformed
-        a.f1wn = 0;
-        far1_range(h, a, 0, U, 0, 0);  // zero partial sums (no stored segments)
-        a.f2u0 = 0;
-        a.f2nwg = U;
-        a.f2tw = w;
-        a.f2wn = 0;
-    }
-    if (int rc = launch_step_kernel(h, a, s)) return rc;
-    if (lp.nseg && !h->far_raw) {  // and 2b of every unit: two launches whatever the shape
-        f.fnfresh = lp.nseg;
-        f.f3u0 = 0;
-        f.f3nwg = int(far_units(h));
-        f.f3wn = 0;
-        f.f3ff = h->fv_ff;
-        f_any = true;
-    }
-    return f_any ? launch_step_kernel(h, f, s) : NEO_HIP_OK;
+    return NEO_HIP_OK;
 }
 
 // background stream and events of the step groups (created on the first grouped step)
@@ -2736,7 +1885,7 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
 {
     int rc = lvl_buffers(h);
     if (rc) return rc;
-    if (h->sg > 1 && (rc = group_streams(h))) return rc;
+    if (h->sched.sg > 1 && (rc = group_streams(h))) return rc;
     const bool primed = h->lv_n < 0;
     if (primed) {
         if ((rc = lvl_prime(h, s))) return rc;
@@ -2745,11 +1894,13 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
         h->pace_seq = 0;
     }
     const int64_t n = h->lv_n;
-    const int G = h->sg;
+    const int G = h->sched.sg;
     slice_args a = base_args(h);
-    block_part(h, n, h->wpos, 0, h->C, in, ld_in, out, ld_out, a);
+    level_sel sel;
+    block_part(h, n, h->wpos, 0, h->C, in, ld_in, out, ld_out, a, sel);
     a.snap = snap;
-    block_levels(h, n, h->wpos, a);
+    block_levels(h->sched, n, h->wpos, a, sel);
+    bind(h, sel, a);
     if (G > 1 && h->paced) {
         // Paced (neo_hip_upols_set_paced): the group's background launch in np pieces (np = G:
         // one per call; np = 2: at the group's calls 0 and G / 2), piece j covering workgroups
@@ -2772,8 +1923,9 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
         if (k % per == 0) {
             const int j = k / per;
             slice_args b = base_args(h);
-            slice_part(h, n0, w0, b);
-            if ((rc = launch_step_kernel(h, b, h->bg, 2, j, np))) return rc;
+            level_sel sb;
+            slice_part(h->sched, n0, w0, b, sb);
+            if ((rc = launch_bound(h, b, sb, h->bg, 2, j, np))) return rc;
             h->bg_busy = true;
             if (j == np - 1) ++h->bg_launches;
             NEO_HIP_CHECK(hipEventRecord(h->ev_pc[h->pace_seq & 1], h->bg));
@@ -2795,7 +1947,9 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
         if (primed) NEO_HIP_CHECK(hipEventRecord(h->ev_blk, s));  // the priming launches
         if ((odd && !NEO_NO_XWAIT) || primed) NEO_HIP_CHECK(hipStreamWaitEvent(h->bg, h->ev_blk, 0));
         slice_args b = base_args(h);
-        slice_part(h, n, h->wpos, b);
+        level_sel sb;
+        slice_part(h->sched, n, h->wpos, b, sb);
+        bind(h, sb, b);
         upols_t::ev_group* eb = nullptr;  // timed when it launches (the first group after a window start may be empty)
         if (launch_grid(b) && ((rc = timing_begin(h, 2, &eb)) || (rc = timing_mark(eb, 0, h->bg)))) return rc;
         if (eb) eb->part = 1;
@@ -3088,10 +2242,10 @@ const char* persist_ineligible(const upols_t* h)
     if (h->C > 16) return "more than 16 channels (the latency mode is for latency-bound shapes)";
     if (!h->ahead)  // the plain step's workgroups, all resident (one per CU at B = 4096)
         return h->C * h->S > 256 ? "the plain step's channels x splits above 256 workgroups" : nullptr;
-    if (h->lv.n && h->lv.T[h->lv.n - 1] == kBigT) return "the 128-block Toeplitz form of the far band (far_level 0)";
-    if (h->lv.nseg && h->far_raw) return "the recomputed far level (far_level 2)";
-    if (h->lv.stag) return "staggered level windows (neo_hip_upols_opts.windows)";
-    if (h->lv.nseg && far_group(h) > 2) return "a far window group above 2 (neo_hip_upols_opts.far_group)";
+    if (h->sched.lv.n && h->sched.lv.T[h->sched.lv.n - 1] == kBigT) return "the 128-block Toeplitz form of the far band (far_level 0)";
+    if (h->sched.lv.nseg && h->sched.far_raw) return "the recomputed far level (far_level 2)";
+    if (h->sched.lv.stag) return "staggered level windows (neo_hip_upols_opts.windows)";
+    if (h->sched.lv.nseg && far_group(h->sched) > 2) return "a far window group above 2 (neo_hip_upols_opts.far_group)";
     if (h->B > 512) return "blocks above 512 samples with the streaming levels";
     return nullptr;
 }
@@ -3099,9 +2253,9 @@ const char* persist_ineligible(const upols_t* h)
 // the slice workgroups of level l: the most any part of its T - 1 needs
 static int persist_level_wgs(const upols_t* h, int l, int& U, int& UPW, int& JH)
 {
-    const int T = h->lv.T[l];
-    toep_geom(h, T, JH, UPW);
-    U = int(toep_units(h, T));
+    const int T = h->sched.lv.T[l];
+    toep_geom(h->sched, T, JH, UPW);
+    U = int(toep_units(h->sched, T));
     int most = 0;
     for (int j = 0; j + 1 < T; ++j) {
         const int u0 = int(int64_t(j) * U / (T - 1)), u1 = int(int64_t(j + 1) * U / (T - 1));
@@ -3127,26 +2281,26 @@ static int persist_levels(upols_t* h, persist_args& pa, int64_t ld_in, int64_t l
     pa.base = base_args(h);
     pa.base.prev = h->prev;
     pa.base.twg = h->tw;
-    pa.base.a0 = h->lv.a0;
+    pa.base.a0 = h->sched.lv.a0;
     pa.base.ld_in = ld_in;
     pa.base.ld_out = ld_out;
-    pa.nlev = h->lv.n;
+    pa.nlev = h->sched.lv.n;
     pa.nblk = h->C;
     pa.wg0[0] = 0;
-    for (int l = 0; l < h->lv.n; ++l) {
+    for (int l = 0; l < h->sched.lv.n; ++l) {
         pa.slab[l] = h->lv_slab[l];
-        pa.T[l] = h->lv.T[l];
-        pa.LT[l] = __builtin_ctz(unsigned(h->lv.T[l]));
-        pa.A[l] = h->lv.a[l];
-        pa.Bd[l] = h->lv.b[l];
+        pa.T[l] = h->sched.lv.T[l];
+        pa.LT[l] = __builtin_ctz(unsigned(h->sched.lv.T[l]));
+        pa.A[l] = h->sched.lv.a[l];
+        pa.Bd[l] = h->sched.lv.b[l];
         pa.wg0[l + 1] = pa.wg0[l] + persist_level_wgs(h, l, pa.U[l], pa.UPW[l], pa.JH[l]);
     }
-    pa.wgf0 = pa.wgf1 = pa.wg0[h->lv.n];
-    if (h->lv.nseg) {  // the far level: as many workgroups as its busiest step needs (any window, any slice)
+    pa.wgf0 = pa.wgf1 = pa.wg0[h->sched.lv.n];
+    if (h->sched.lv.nseg) {  // the far level: as many workgroups as its busiest step needs (any window, any slice)
         pa.far = 1;
-        pa.fU = int(far_units(h));
-        pa.fK = far_group(h);
-        pa.ffpl = far1_fpl(h);
+        pa.fU = int(far_units(h->sched));
+        pa.fK = far_group(h->sched);
+        pa.ffpl = far1_fpl(h->sched);
         pa.ff = h->fv_ff;
         int most = 1;
         for (int64_t W = 1; W <= 2 * pa.fK + 1; ++W)
@@ -3367,6 +2521,21 @@ int persist_process(upols_t* h, const float* in, int64_t ld_in, float* out, int6
     return NEO_HIP_OK;
 }
 
+// the schedule a plan export describes: default options but the step group, the windows (1 aligned,
+// 2 staggered) and the far window group; no device
+static int export_sched(int C, int B, int P, int step_group, int windows, int far_group, level_sched& s)
+{
+    if (const char* why = make_level_sched(C, B, P, P + kMaxBatch - 1, plan_opts(step_group, windows, far_group), false, false, s))
+        return fail(NEO_HIP_EINVAL, "%s", why);
+    return NEO_HIP_OK;
+}
+
+static void export_loads(const std::vector<double>& ld, double* loads, int loads_cap)
+{
+    if (loads)
+        for (int g = 0; g < std::min(loads_cap, int(ld.size())); ++g) loads[g] = ld[size_t(g)];
+}
+
 }  // namespace neo_hip
 
 // The level plan of a (block, partitions) convolver, for tests of the schedule: a0 = the
@@ -3375,8 +2544,9 @@ extern "C" NEO_HIP_API int neo_hip_upols_level_plan(int partitions, int* a0, int
                                                     int* nseg)
 {
     if (partitions < 1) return neo_hip::fail(NEO_HIP_EINVAL, "partitions must be >= 1");
-    neo_hip::level_plan lp;
-    neo_hip::plan_levels(partitions, lp);
+    neo_hip::level_sched s;
+    if (int rc = neo_hip::export_sched(1, 16, partitions, 1, 1, 0, s)) return rc;
+    const neo_hip::level_plan& lp = s.lv;
     if (a0) *a0 = lp.a0;
     if (nlevels) *nlevels = lp.n;
     for (int l = 0; l < lp.n; ++l) {
@@ -3400,26 +2570,21 @@ extern "C" NEO_HIP_API int neo_hip_upols_part_plan(int channels, int block, int 
 {
     if (channels < 1 || block < 16 || partitions < 1 || step_group < 0)
         return neo_hip::fail(NEO_HIP_EINVAL, "part plan: bad shape");
-    neo_hip_upols h{};
-    h.C = channels;
-    h.B = block;
-    h.P = partitions;
-    neo_hip::plan_levels(partitions, h.lv);
-    h.sg = step_group ? step_group : neo_hip::step_group_for(channels, block, partitions);
+    neo_hip::level_sched s;
+    if (int rc = neo_hip::export_sched(channels, block, partitions, step_group, 1, 0, s)) return rc;
     std::vector<double> ld;
-    neo_hip::plan_handle_parts(&h, &ld, !uniform);
+    neo_hip::plan_parts(s, &ld, !uniform);
     if (phi)
-        for (int l = 0; l < h.lv.n; ++l) phi[l] = h.lv_phi[l];
-    if (cycle) *cycle = h.lv_cyc;
+        for (int l = 0; l < s.lv.n; ++l) phi[l] = s.lv_phi[l];
+    if (cycle) *cycle = s.lv_cyc;
     int n = 0;
-    for (int l = 0; l < h.lv.n; ++l)
-        for (int v : h.lv_cut[l]) {
+    for (int l = 0; l < s.lv.n; ++l)
+        for (int v : s.lv_cut[l]) {
             if (cuts && n < cuts_cap) cuts[n] = v;
             ++n;
         }
     if (ncuts) *ncuts = n;
-    if (loads)
-        for (int g = 0; g < std::min(loads_cap, int(ld.size())); ++g) loads[g] = ld[size_t(g)];
+    neo_hip::export_loads(ld, loads, loads_cap);
     return NEO_HIP_OK;
 }
 
@@ -3440,17 +2605,13 @@ extern "C" NEO_HIP_API int neo_hip_upols_stagger_plan(int channels, int block, i
 {
     if (channels < 1 || block < 16 || block > 1024 || partitions < 1 || step_group < 0 || far_group < 0 || far_group > 4)
         return neo_hip::fail(NEO_HIP_EINVAL, "stagger plan: bad shape");
-    neo_hip_upols h{};
-    h.C = channels;
-    h.B = block;
-    h.P = partitions;
-    h.far_k = far_group;
-    h.sg = step_group ? step_group : neo_hip::step_group_for(channels, block, partitions);
-    if (h.sg != 2 && h.sg != 4 && h.sg != 8) return neo_hip::fail(NEO_HIP_EINVAL, "stagger plan: step groups of 2, 4 or 8");
-    neo_hip::plan_levels_stag(partitions, channels, block, h.sg, far_group, h.lv);
+    const int G = step_group ? step_group : neo_hip::step_group_for(channels, block, partitions);
+    if (G != 2 && G != 4 && G != 8) return neo_hip::fail(NEO_HIP_EINVAL, "stagger plan: step groups of 2, 4 or 8");
+    neo_hip::level_sched s;
+    if (int rc = neo_hip::export_sched(channels, block, partitions, G, 2, far_group, s)) return rc;
     std::vector<double> ld;
-    neo_hip::plan_handle_parts(&h, &ld, true);
-    const neo_hip::level_plan& lp = h.lv;
+    neo_hip::plan_parts(s, &ld, true);
+    const neo_hip::level_plan& lp = s.lv;
     if (nlevels) *nlevels = lp.n;
     for (int l = 0; l < lp.n; ++l) {
         if (T) T[l] = lp.T[l];
@@ -3460,21 +2621,20 @@ extern "C" NEO_HIP_API int neo_hip_upols_stagger_plan(int channels, int block, i
     }
     if (far_a) *far_a = lp.farA;
     if (nseg) *nseg = lp.nseg;
-    if (even_share) *even_share = h.lv.nseg ? h.st_fef : (h.lv.n ? h.st_ef[h.lv.n - 1] : 512);
+    if (even_share) *even_share = lp.nseg ? s.st_fef : (lp.n ? s.st_ef[lp.n - 1] : 512);
     int n = 0;
     auto put = [&](const std::vector<int>& c, int Tl) {
         for (size_t k = 0; k < c.size(); ++k, ++n)
             if (n < cuts_cap) {
                 if (cuts) cuts[n] = c[k];
-                if (offs) offs[n] = k + 1 < c.size() ? (Tl - neo_hip::stag_phi(Tl, h.sg, int(k))) % Tl : 0;
+                if (offs) offs[n] = k + 1 < c.size() ? (Tl - neo_hip::stag_phi(Tl, G, int(k))) % Tl : 0;
             }
     };
-    for (int l = 0; l < lp.n; ++l) put(h.st_cut[l], lp.T[l]);
-    put(h.st_fcut, neo_hip::kFarT);
+    for (int l = 0; l < lp.n; ++l) put(s.st_cut[l], lp.T[l]);
+    put(s.st_fcut, neo_hip::kFarT);
     if (ncuts) *ncuts = n;
     if (nloads) *nloads = int(ld.size());
-    if (loads)
-        for (int g = 0; g < std::min(loads_cap, int(ld.size())); ++g) loads[g] = ld[size_t(g)];
+    neo_hip::export_loads(ld, loads, loads_cap);
     return NEO_HIP_OK;
 }
 
@@ -3483,14 +2643,14 @@ extern "C" NEO_HIP_API int neo_hip_upols_stagger_plan(int channels, int block, i
 extern "C" NEO_HIP_API int neo_hip_upols_get_far_group(neo_hip_upols* h, int* windows)
 {
     if (!h || !windows) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *windows = h->lv.nseg ? neo_hip::far_group(h) : 0;
+    *windows = h->sched.lv.nseg ? neo_hip::far_group(h->sched) : 0;
     return NEO_HIP_OK;
 }
 
 extern "C" NEO_HIP_API int neo_hip_upols_get_far_form(neo_hip_upols* h, int* form)
 {
     if (!h || !form) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *form = h->lv.nseg ? (h->far_raw ? 2 : 1) : (h->lv.n && h->lv.T[h->lv.n - 1] == neo_hip::kBigT ? 3 : 0);
+    *form = h->sched.lv.nseg ? (h->sched.far_raw ? 2 : 1) : (h->sched.lv.n && h->sched.lv.T[h->sched.lv.n - 1] == neo_hip::kBigT ? 3 : 0);
     return NEO_HIP_OK;
 }
 
@@ -3499,14 +2659,14 @@ extern "C" NEO_HIP_API int neo_hip_upols_get_far_form(neo_hip_upols* h, int* for
 extern "C" NEO_HIP_API int neo_hip_upols_get_windows(neo_hip_upols* h, int* windows)
 {
     if (!h || !windows) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *windows = h->lv.stag && h->ahead ? 2 : 1;
+    *windows = h->sched.lv.stag && h->ahead ? 2 : 1;
     return NEO_HIP_OK;
 }
 
 extern "C" NEO_HIP_API int neo_hip_upols_get_step_group(neo_hip_upols* h, int* steps)
 {
     if (!h || !steps) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *steps = h->sg;
+    *steps = h->sched.sg;
     return NEO_HIP_OK;
 }
 
@@ -3524,7 +2684,7 @@ extern "C" NEO_HIP_API int neo_hip_upols_join_background(neo_hip_upols* h, void*
 extern "C" NEO_HIP_API int neo_hip_upols_get_background_stream(neo_hip_upols* h, void** stream)
 {
     if (!h || !stream) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *stream = h->sg > 1 && !h->persist ? static_cast<void*>(h->bg) : nullptr;
+    *stream = h->sched.sg > 1 && !h->sched.persist ? static_cast<void*>(h->bg) : nullptr;
     return NEO_HIP_OK;
 }
 

@@ -1,4 +1,5 @@
-"""The streaming level schedule (neo-dsp_amd/csrc/upols_levels.hip), restated in float64
+"""The streaming level schedule (neo-dsp_amd/csrc/levels_plan.hpp: block_levels, slice_part,
+prime_round; the kernels in upols_levels.hip), restated in float64
 numpy and checked against the direct block-axis convolution — no GPU needed.
 
 Per bin the convolver output is Y[t] = sum_p H[p] X[t - p]
@@ -64,7 +65,7 @@ class Sim:
         ns = lp["nseg"]
         self.P, self.K = H.shape
         # windows per phase-1 pass: the kernel's automatic choice for this many 16-column units
-        # (bench.far_group restates upols_levels.hip far_group), or a forced value
+        # (bench.far_group restates levels_plan.hpp far_group), or a forced value
         # (neo_hip_upols_opts.far_group)
         if Kw is None:
             sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
@@ -493,7 +494,7 @@ def test_level_schedule_far_recomputed(P, sg):
 @pytest.mark.parametrize("C,B,P,G", [(2048, 512, 938, 4), (256, 512, 938, 4), (256, 256, 1875, 4), (64, 256, 700, 8),
                                      (16, 64, 300, 2), (4, 256, 300, 4), (1, 512, 188, 4)])
 def test_part_plan_valid_and_balanced(C, B, P, G):
-    """The library's background plan (part_plan, upols_levels.hip): window offsets phi = T / 2 for
+    """The library's background plan (part_plan, levels_plan.hpp): window offsets phi = T / 2 for
     the background levels of 4 G <= T <= 32 (the replay above runs the same offsets with arbitrary
     cuts); every window's cuts run 0 .. U in order; at the 256- and 2048-channel shapes every step
     group of the far window carries 0.99-1.01 of the mean background bytes (before: an empty group
@@ -520,6 +521,132 @@ def test_part_plan_valid_and_balanced(C, B, P, G):
         assert 0.99 <= min(w5) and max(w5) <= 1.01, (min(w5), max(w5))
         u = np.array(neo.convolution.part_plan(C, B, P, G, uniform=True)["loads"])
         assert u.min() < 0.1 * u.mean()  # the plan before: empty groups
+
+
+# -- golden plans --------------------------------------------------------------------------------
+
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "level_plans.json")
+PLAN_P = [1, 8, 9, 16, 17, 33, 60, 65, 150, 256, 257, 300, 450, 700, 938, 1875, 4000]
+PLAN_CB = [(1, 64), (4, 256), (24, 64), (256, 256), (2048, 512)]
+
+
+def _hex(v):
+    return [float(x).hex() for x in v]
+
+
+def _part_plan_auto(C, B, P, uniform):
+    """neo_hip_upols_part_plan with the automatic step group (0), which neo.convolution.part_plan
+    does not pass on: phi per level, the cycle, the cuts as the export lays them out, the loads"""
+    import ctypes
+
+    from neo import _native
+
+    L = _native.load()
+    phi, cyc, nc = (ctypes.c_int * 8)(), ctypes.c_int(), ctypes.c_int()
+    loads, cuts = (ctypes.c_double * 512)(), (ctypes.c_int * 4096)()
+    _native.check(L.neo_hip_upols_part_plan(C, B, P, 0, int(uniform), phi, ctypes.byref(cyc), cuts, 4096,
+                                            ctypes.byref(nc), loads, 512))
+    assert nc.value <= 4096
+    return {"phi": list(phi[:len(plan(P)["T"])]), "cycle": cyc.value, "cuts": list(cuts[:nc.value]),
+            "loads": list(loads[:cyc.value])}
+
+
+def level_plans():
+    """Every plan export over the golden grid, doubles as float.hex(); None where an export rejects
+    the combination."""
+    import neo
+    from neo._native import NeoHipError
+
+    out = {"level": {str(P): plan(P) for P in PLAN_P}, "part": {}, "stagger": {}}
+    for C, B in PLAN_CB:
+        for P in PLAN_P:
+            for G in (0, 2, 4, 8):
+                for uniform in (0, 1):
+                    pp = (neo.convolution.part_plan(C, B, P, G, bool(uniform)) if G else _part_plan_auto(C, B, P, uniform))
+                    if G:
+                        pp["cuts"] = {str(l): c for l, c in pp["cuts"].items()}
+                    pp["loads"] = _hex(pp["loads"])
+                    out["part"][f"{C},{B},{P},{G},{uniform}"] = pp
+                for Kw in (0, 1, 3):
+                    try:
+                        sp = neo.convolution.stagger_plan(C, B, P, G, Kw)
+                        sp["loads"] = _hex(sp["loads"])
+                        sp["classes"] = {str(k): [list(c) for c in cl] for k, cl in sp["classes"].items()}
+                    except NeoHipError:
+                        sp = None
+                    out["stagger"][f"{C},{B},{P},{G},{Kw}"] = sp
+    return out
+
+
+def plan_digests(plans):
+    """What the golden file holds: the level plans in full; of the part and stagger plans, per
+    (C, B, P), the SHA-256 of the canonical JSON of all its combinations (doubles as float.hex(),
+    so bit-exact) and how many of them the export accepts -- the full values of the grid would be
+    3 MB"""
+    import hashlib
+    import json
+
+    out = {"level": plans["level"], "part": {}, "stagger": {}}
+    for kind in ("part", "stagger"):
+        groups = {}
+        for key, v in plans[kind].items():
+            groups.setdefault(",".join(key.split(",")[:3]), {})[key] = v
+        for g, sub in groups.items():
+            text = json.dumps(sub, sort_keys=True, separators=(",", ":"))
+            out[kind][g] = {"sha256": hashlib.sha256(text.encode()).hexdigest(),
+                            "accepted": sum(v is not None for v in sub.values()), "of": len(sub)}
+    return out
+
+
+def test_plan_exports_match_golden():
+    """level_plan, part_plan and stagger_plan over P x (C, B) x G x uniform / far_group return
+    exactly what the library returned when tests/golden/level_plans.json was recorded (before the
+    plan moved to levels_plan.hpp; `python tests/test_levels.py` rewrites the file), the predicted
+    loads bit for bit, and reject the same combinations."""
+    import json
+
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = plan_digests(level_plans())
+    for kind in ("level", "part", "stagger"):
+        assert got[kind].keys() == want[kind].keys(), kind
+        for key in want[kind]:
+            assert got[kind][key] == want[kind][key], (kind, key)
+    assert len(want["level"]) == 17 and len(want["part"]) == 85 and len(want["stagger"]) == 85
+    assert sum(v["accepted"] for v in want["stagger"].values()) >= 400
+
+
+def test_level_schedule_host_program_under_sanitizers():
+    """csrc/levels_plan.hpp alone (it includes no HIP header), in a program of its own built with the
+    address and undefined-behaviour sanitizers and run directly (tests/cpp/levels_plan_main.cpp): the
+    library's own schedule functions walked over 2 P + 3 * 128 + 60 blocks per configuration (C, B, P,
+    step group, aligned / staggered, far level form, far window group, T = 32 split, far phase 2; the
+    option values that change nothing of a schedule run once), every read against its launch's
+    guarantee, every window's units computed exactly once by a launch its first block is ordered
+    after, every buffer rewritten only when its window is over, every role's workgroups; and
+    persist_far_args over five far windows. Each of the three mutations (a staggered band one
+    partition earlier, the even groups' classes one group sooner, a part's last unit dropped) must
+    fail: every mutated case does."""
+    import re
+    import shutil
+    import subprocess
+
+    if not shutil.which("g++"):
+        pytest.skip("no g++")
+    cpp = os.path.join(os.path.dirname(__file__), "cpp")
+    os.makedirs(os.path.join(cpp, "bin"), exist_ok=True)
+    out = os.path.join(cpp, "bin", "levels_plan_main")
+    subprocess.check_call(["g++", "-std=c++20", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-o", out,
+                           os.path.join(cpp, "levels_plan_main.cpp")])
+    r = subprocess.run([out], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert "2943 cases, 0 failed" in r.stdout
+    for mutation in ("band", "early", "cut"):
+        r = subprocess.run([out, "--mutate", mutation], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 1, (mutation, r.stdout[-2000:] + r.stderr[-2000:])
+        m = re.search(r"(\d+) cases, (\d+) failed", r.stdout)
+        assert m and int(m.group(1)) >= 800 and m.group(1) == m.group(2), (mutation, r.stdout[-200:])
 
 
 def _offline_replay(H, X, R, wp, w0, ring0):
@@ -590,3 +717,14 @@ def test_offline_windows_match_direct(P, wp):
         ring_hist[t % R] = Xall[t]
     got = _offline_replay(H, Xall[hist:], R, wp, w0, ring_hist)
     np.testing.assert_allclose(got, Y[hist:hist + got.shape[0]], rtol=0, atol=1e-9 * np.abs(Y).max())
+
+
+if __name__ == "__main__":
+    import json
+
+    os.makedirs(os.path.dirname(GOLDEN), exist_ok=True)
+    with open(GOLDEN, "w") as f:
+        d = plan_digests(level_plans())  # one entry a line
+        kinds = [",\n".join(f'{json.dumps(k)}:{json.dumps(v, sort_keys=True, separators=(",", ":"))}' for k, v in d[kind].items())
+                 for kind in ("level", "part", "stagger")]
+        f.write('{"level":{\n%s},\n"part":{\n%s},\n"stagger":{\n%s}}\n' % tuple(kinds))

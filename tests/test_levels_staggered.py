@@ -1,5 +1,5 @@
-"""Staggered level windows (neo_hip_upols_opts.windows = 2; upols_levels.hip plan_levels_stag,
-slice_part, lvl_prime_stag), restated in float64 numpy from the plan export
+"""Staggered level windows (neo_hip_upols_opts.windows = 2; levels_plan.hpp plan_levels_stag,
+slice_part, prime_round), restated in float64 numpy from the plan export
 (neo_hip_upols_stagger_plan) and checked against the direct block-axis convolution -- no GPU.
 
 A level of window T >= 4 G, and the far level, is cut into T / G classes of channels. Class k is
@@ -211,7 +211,7 @@ class StagSim:
         return y
 
     def prime(self):
-        """lvl_prime / lvl_prime_stag: window 0 of every class began phi steps ago; then the
+        """prime_round (levels_plan.hpp): window 0 of every class began phi steps ago; then the
         launches of the groups -3 .. -1 as they would have run"""
         self.join()
         sp, G, t0 = self.sp, self.G, self.t
