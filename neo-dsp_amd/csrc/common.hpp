@@ -131,6 +131,20 @@ inline int dalloc(T** out, size_t bytes)
     *out = static_cast<T*>(v);
     return rc;
 }
+// A host-or-device array of `bytes` bytes as a device pointer (*dev) for work on s. A device array
+// is used where it lies, unless the caller will write to it (own); otherwise it is copied on s into
+// pooled scratch (*tmp; stays null when unused), which the caller gives back (dfree) once s is joined.
+template<class T>
+inline int stage_in(const T* src, size_t bytes, bool is_device, bool own, hipStream_t s, T** tmp, const T** dev)
+{
+    *dev = src;
+    if (is_device && !own) return NEO_HIP_OK;
+    if (dalloc(tmp, bytes)) return fail(NEO_HIP_ENOMEM, "allocation of %zu bytes failed", bytes);
+    if (hipMemcpyAsync(*tmp, src, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
+        return fail(NEO_HIP_ERUNTIME, "copy to the device failed");
+    *dev = *tmp;
+    return NEO_HIP_OK;
+}
 int halloc(void** host, void** dev, size_t bytes);  // mapped page-locked host memory, pooled
 void hfree(void* host);
 int shared_stream(hipStream_t* out);  // one of four blocking streams per device, never destroyed

@@ -220,17 +220,14 @@ NEO_HIP_API int neo_hip_perceptual_mask(const void* filter, int C, int B, int P,
     std::vector<float> w(size_t(B) + 1);
     perceptual_weights(B, pp, w.data());
     const size_t n = size_t(C) * size_t(P) * (size_t(B) + 1);
-    const cf* src = static_cast<const cf*>(filter);
+    const cf* src = nullptr;
     uint8_t* d_mask = mask;
     cf* tmpf = nullptr;
     uint8_t* tmpm = nullptr;
     float* tmp = nullptr;
-    int rc = NEO_HIP_OK;
-    if (!is_device) {
-        if (dalloc(&tmpf, n * sizeof(cf)) || dalloc(&tmpm, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-        else if (hipMemcpyAsync(tmpf, filter, n * sizeof(cf), hipMemcpyHostToDevice, s) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmpf;
+    int rc = stage_in(static_cast<const cf*>(filter), n * sizeof(cf), is_device != 0, false, s, &tmpf, &src);
+    if (!rc && !is_device) {
+        if (dalloc(&tmpm, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
         d_mask = tmpm;
     }
     if (!rc) rc = perceptual_mask_device(src, C, B, P, pp, w.data(), d_mask, &tmp, s);
@@ -257,19 +254,14 @@ NEO_HIP_API int neo_hip_perceptual_histogram(const void* filter, int C, int B, i
     perceptual_weights(B, pp, w.data());
     const size_t n = size_t(C) * size_t(P) * (size_t(B) + 1);
     const size_t hbytes = size_t(C) * kPercBuckets * sizeof(int64_t);
-    const cf* src = static_cast<const cf*>(filter);
+    const cf* src = nullptr;
     cf* tmpf = nullptr;
     unsigned long long* hist = nullptr;  // [2][C][144]
     float* tmp = nullptr;
     int rc = NEO_HIP_OK;
     if (dalloc(&hist, 2 * hbytes)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
     else if (hipMemsetAsync(hist, 0, 2 * hbytes, s) != hipSuccess) rc = fail(NEO_HIP_ERUNTIME, "memset failed");
-    if (!rc && !is_device) {
-        if (dalloc(&tmpf, n * sizeof(cf))) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-        else if (hipMemcpyAsync(tmpf, filter, n * sizeof(cf), hipMemcpyHostToDevice, s) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmpf;
-    }
+    if (!rc) rc = stage_in(static_cast<const cf*>(filter), n * sizeof(cf), is_device != 0, false, s, &tmpf, &src);
     if (!rc) rc = perc_levels_begin(src, C, B, P, w.data(), &tmp, s);
     if (!rc) {
         const int GP = (P + kPercHistRows - 1) / kPercHistRows;

@@ -19,16 +19,20 @@
 // Device layout (HBM), all packed rows of B complex with bin 0 = {DC, Nyquist}
 // (both purely real for real signals, so the fold is exact):
 //   H    [C][R][B]   filter partitions (uniform_partition.hpp layout, packed; rows >= P unused)
-//   FDL  [C][R][B]   frequency-domain delay line, a ring of R = P + kMaxBatch - 1 rows
+//   FDL  [C][R][B]   frequency-domain delay line, a ring of at least R = P + kMaxBatch - 1 rows
 //                    (write position w; the extra rows let a batch of T <= kMaxBatch
-//                    new blocks be inserted before any of them is consumed)
+//                    new blocks be inserted before any of them is consumed; the far level and
+//                    the offline windows ask for more: upols_plan.hpp)
 //   prev [C][B]      previous input block (first half of the overlap-save window)
 //   part [C][S][B]   per-split partial spectra; arrivals [C] split counters
 //
-// This file: the single-block step (MAC + finish, or one launch with the last-arriver
-// tail), the upola_convolver_v2 piece kernel, the handle and the neo_hip_upols_* C-ABI.
-// upols_batch.hip: T blocks per pass (process_blocks). upols_setup.hip: partitioning
-// and normalization. upols_device.hpp / upols_handle.hpp: what they share.
+// This file: the single-block step (MAC + finish, or one launch with the last-arriver tail; one
+// frame for dense and sparse handles), the upola_convolver_v2 piece kernel, the one create function
+// (every kind of handle from its plan: upols_plan.hpp, all checks and shape rules, host only), the
+// filter calls (set_begin, a body, set_end) and the rest of the neo_hip_upols_* C-ABI.
+// upols_batch.hip: T blocks per pass (process_blocks). upols_sparse.hip: the sparse handle's
+// buffers, filter and MAC. upols_setup.hip: partitioning and normalization. upols_device.hpp /
+// upols_handle.hpp: what they share.
 #include "upols_device.hpp"
 #include "upols_handle.hpp"
 #include "perceptual_plan.hpp"
@@ -36,9 +40,8 @@
 #include "upols_step.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cstring>
-#include <string>
+#include <initializer_list>
 #include <utility>
 #include <vector>
 
@@ -132,7 +135,7 @@ __global__ __launch_bounds__(256) void k_plain_persist(plain_persist_args pa)
 int plain_persist_launch(upols_t* h, const persist_ctl& ctl, int64_t ld_in, int64_t ld_out, bool* launched)
 {
     *launched = false;
-    if (h->C * h->S > 256) return fail(NEO_HIP_EINVAL, "latency mode: %d x %d plain step workgroups", h->C, h->S);
+    if (h->C * h->shape.S > 256) return fail(NEO_HIP_EINVAL, "latency mode: %d x %d plain step workgroups", h->C, h->shape.S);
     plain_persist_args pa{};
     static_cast<persist_ctl&>(pa) = ctl;
     pa.H = h->H;
@@ -143,15 +146,15 @@ int plain_persist_launch(upols_t* h, const persist_ctl& ctl, int64_t ld_in, int6
     pa.twg = h->tw;
     pa.ld_in = ld_in;
     pa.ld_out = ld_out;
-    pa.cstride = h->cstride;
-    pa.pstride = h->pstride;
+    pa.cstride = h->shape.cstride;
+    pa.pstride = h->shape.pstride;
     pa.C = h->C;
     pa.P = h->P;
     pa.ring = h->ring;
-    pa.S = h->S;
-    pa.rows = h->rows;
-    pa.pc = h->pc;
-    const unsigned grid = unsigned(h->C) * unsigned(h->S);
+    pa.S = h->shape.S;
+    pa.rows = h->shape.rows;
+    pa.pc = h->shape.pc;
+    const unsigned grid = unsigned(h->C) * unsigned(h->shape.S);
     bool room = false;
     if (h->ola) {
         NEO_UPOLS_DISPATCH(h->B, room = persist_room(h, reinterpret_cast<const void*>(&k_plain_persist<BB, true>), int(grid));
@@ -378,7 +381,7 @@ int launch_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t 
 
 int neo_hip::launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s)
 {
-    return launch_finish_slabs(h->C, h->B, h->S, h->ola, h->part, out, ld_out, h->prev, h->tw, s);
+    return launch_finish_slabs(h->C, h->B, h->shape.S, h->ola, h->part, out, ld_out, h->prev, h->tw, s);
 }
 
 int neo_hip::launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, float* out, int64_t ld_out, float* ovl,
@@ -395,32 +398,45 @@ int neo_hip::launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, 
     return NEO_HIP_OK;
 }
 
+namespace {
+
+// the one k_upols_step launch (grid C x S): the plain step's MAC in its one-launch (FUSED) or
+// MAC + finish form, or (TAIL) the v2 piece's MAC over partitions p >= 1
+template<bool FUSED, bool OLA, bool TAIL>
+int launch_upols_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    const upols_shape& sh = h->shape;
+    const unsigned grid = unsigned(h->C) * unsigned(sh.S);
+    NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_step<BB, FUSED, OLA, TAIL>), dim3(grid), dim3(256), 0, s, in, ld_in,
+                                                out, ld_out, h->prev, h->H, h->fdl, h->part, h->arrivals, h->tw, h->P,
+                                                h->ring, sh.S, sh.rows, h->wpos, sh.cstride, sh.pstride, sh.pc))
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+}  // namespace
+
+// One block without the streaming levels, dense or sparse: the MAC launch between the timing marks,
+// the finish launch of the two-launch form, the write position one row on.
 int neo_hip::launch_step_normal(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
-    if (h->sparse) return launch_sparse_step(h, in, ld_in, out, ld_out, s);
-    if (h->ahead) return launch_levels(h, in, ld_in, out, ld_out, s);
+    if (h->shape.ahead) return launch_levels(h, in, ld_in, out, ld_out, s);
     if (int rc = lvl_join(h, s)) return rc;
     upols_t::ev_group* ev = nullptr;
     if (int rc = timing_begin(h, 2, &ev)) return rc;
     if (int rc = timing_mark(ev, 0, s)) return rc;
-    const unsigned grid = unsigned(h->C) * unsigned(h->S);
-#define NEO_STEP(FU, OL)                                                                                      \
-    NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_step<BB, FU, OL>), dim3(grid), dim3(256), 0, s, in, ld_in, \
-                                                out, ld_out, h->prev, h->H, h->fdl, h->part, h->arrivals, h->tw,   \
-                                                h->P, h->ring, h->S, h->rows, h->wpos, h->cstride, h->pstride,  \
-                                                h->pc))
-    if (h->fused) {
-        if (h->ola) NEO_STEP(true, true) else NEO_STEP(true, false)
-    } else {
-        if (h->ola) NEO_STEP(false, true) else NEO_STEP(false, false)
-    }
-#undef NEO_STEP
-    NEO_HIP_LAUNCH_CHECK();
+    const bool fu = h->shape.fused, ol = h->ola;
+    if (int rc = h->sparse  ? launch_sparse_mac(h, in, ld_in, out, ld_out, s)
+                 : fu && ol ? launch_upols_step<true, true, false>(h, in, ld_in, out, ld_out, s)
+                 : fu       ? launch_upols_step<true, false, false>(h, in, ld_in, out, ld_out, s)
+                 : ol       ? launch_upols_step<false, true, false>(h, in, ld_in, out, ld_out, s)
+                            : launch_upols_step<false, false, false>(h, in, ld_in, out, ld_out, s))
+        return rc;
     h->fdl_zero = false;
     if (int rc = timing_mark(ev, 1, s)) return rc;
-    if (!h->fused)
+    if (!h->shape.fused)
         if (int rc = launch_finish(h, out, ld_out, s)) return rc;
-    h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;  // fdl_index.hpp:35-37
+    advance(h, 1);
     h->lv_n = -1;
     return NEO_HIP_OK;
 }
@@ -434,22 +450,17 @@ int launch_piece(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t
     if (int rc = lvl_join(h, s)) return rc;
     h->lv_n = -1;
     h->fdl_zero = false;
-    if (sum_first) {  // tail MAC over partitions p >= 1 into the split slabs
-        const unsigned grid = unsigned(h->C) * unsigned(h->S);
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_step<BB, false, true, true>), dim3(grid), dim3(256), 0, s,
-                                                    in, ld_in, out, ld_out, h->prev, h->H, h->fdl, h->part,
-                                                    h->arrivals, h->tw, h->P, h->ring, h->S, h->rows, h->wpos,
-                                                    h->cstride, h->pstride, h->pc))
-        NEO_HIP_LAUNCH_CHECK();
-    }
+    if (sum_first)  // tail MAC over partitions p >= 1 into the split slabs
+        if (int rc = launch_upols_step<false, true, true>(h, in, ld_in, out, ld_out, s)) return rc;
     NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upola2_piece<BB>), dim3(unsigned(h->C)), dim3(256), 0, s, in, ld_in,
-                                                out, ld_out, n, h->in_pos, h->window, h->prev, h->tmp, h->part, h->S,
-                                                sum_first, h->H, h->fdl, h->wpos, h->tw, h->cstride, h->pstride))
+                                                out, ld_out, n, h->in_pos, h->window, h->prev, h->tmp, h->part,
+                                                h->shape.S, sum_first, h->H, h->fdl, h->wpos, h->tw, h->shape.cstride,
+                                                h->shape.pstride))
     NEO_HIP_LAUNCH_CHECK();
     h->in_pos += n;
     if (h->in_pos == h->B) {  // block complete: next FDL row (overlap_add_convolver.hpp:131)
         h->in_pos = 0;
-        h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;
+        advance(h, 1);
     }
     return NEO_HIP_OK;
 }
@@ -461,9 +472,8 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
 {
     if (int rc = note_stream(h, s)) return rc;
     const int B = h->B;
-    const int T = h->batch ? batch_blocks(h) : 1;
-    const bool a16 = !((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) &&
-                     !((ld_in | ld_out) & 3);
+    const int T = h->shape.batch ? batch_blocks(h) : 1;
+    const bool a16 = io_aligned(in, out, ld_in, ld_out);
     if (h->sched.persist) {  // latency mode: every block through the persistent kernel, complete on return
         if (n % B || !a16) return fail(NEO_HIP_EINVAL, "latency mode: whole 16-byte aligned blocks");
         return persist_process(h, in, ld_in, out, ld_out, n / B);
@@ -478,7 +488,7 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
     // only whole T-block batches run (the rest stream, one prime per call at most), and a
     // call of fewer than kStreamKeep batches' blocks on primed levels streams them all.
     constexpr int kStreamKeep = 4;
-    const bool stream_all = h->ahead && h->lv_n >= 0 && n < int64_t(kStreamKeep) * T * B;
+    const bool stream_all = h->shape.ahead && h->lv_n >= 0 && n < int64_t(kStreamKeep) * T * B;
     int64_t done = 0;
     while (done < n) {
         const float* ip = in + done;
@@ -486,7 +496,7 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
         int rc;
         // offline windows: 256 or 128 whole blocks left, every block known (batching on)
         const int64_t left = (n - done) / B;
-        if (h->off && h->batch && !stream_all && h->in_pos == 0 && a16 && done % 4 == 0 && left >= kFarT) {
+        if (h->shape.off && h->shape.batch && !stream_all && h->in_pos == 0 && a16 && done % 4 == 0 && left >= kFarT) {
             const int wp = left >= int64_t(kFarT) * kOffMaxWP ? kOffMaxWP : 1;
             if ((rc = launch_offline(h, ip, ld_in, op, ld_out, wp, s))) return rc;
             done += int64_t(wp) * kFarT * B;
@@ -495,7 +505,7 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
         // the largest power-of-two batch (<= T) of whole blocks left, one pass over H + FDL
         int tb = 1;
         while (!stream_all && tb * 2 <= T && n - done >= int64_t(tb) * 2 * B) tb *= 2;
-        if (h->ahead && tb < T) tb = 1;
+        if (h->shape.ahead && tb < T) tb = 1;
         if (h->in_pos == 0 && tb > 1 && a16 && done % 4 == 0) {
             rc = launch_batch(h, ip, ld_in, op, ld_out, tb, s);
             done += int64_t(tb) * B;
@@ -519,99 +529,37 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
 }  // namespace
 
 
-// The offline windows' ring, 128 (nseg + 2) rows, is a multiple of 256 rows: a channel stride of
-// 5 x 2^20 bytes at B = 512 made the streaming step 4 % slower at c5full (same-box A/B: 9.29-9.49
-// vs 9.68-9.74 Gsamples/s at 20 steps, as with the ring of P + 31 rows); one more row keeps it odd
-// and restores it (9.58-9.83). profiles/r6_ab_ring.json
-#ifndef NEO_OFF_RING_PAD
-#define NEO_OFF_RING_PAD 1  // diagnostic builds (A/B): 0 = the even ring
-#endif
 namespace {
-int create_convolver(int channels, int block, int partitions, int device, bool ola, bool v2,
+
+// Every kind of handle: the plan (upols_plan.hpp: checks and shape rules), the device, the stream,
+// the buffers of its kind, twiddles, stream-ordered zeroing, one wait. Dense / v2: filter and FDL in
+// ONE allocation (FDL = rows [nrows, 2 nrows)): the LDS-DMA batched MAC reaches both of a channel
+// through a single buffer descriptor; v2 adds its window and tail accumulator. Sparse
+// (sparse_convolver.hpp:12-17): the FDL ring, the step state and the bitmaps / offsets; the tiles come
+// with the filter (sparse_set_filter); no dense filter, level or offline buffers. The batch
+// buffers come with the first batched pass (launch_batch).
+int create_convolver(int channels, int block, int partitions, int device, upols_kind kind, bool ola,
                      const neo_hip_upols_opts* opt, neo_hip_upols** out, hipStream_t borrow = nullptr)
 {
     if (!out) return fail(NEO_HIP_EINVAL, "handle pointer is null");
-    const neo_hip_upols_opts o = opt ? *opt : neo_hip_upols_opts{-1, 0, 0, 0, -1, -1, 0, 0, 0, 0, 0};
-    if (o.fused < -1 || o.fused > 1 || o.levels < -1 || o.levels > 1 || o.far_level < -1 || o.far_level > 2 ||
-        o.split_workgroups < 0 ||
-        (o.batch_blocks && (o.batch_blocks < 2 || o.batch_blocks > kMaxBatch || (o.batch_blocks & (o.batch_blocks - 1)))) ||
-        o.batch_bins < 0 || o.batch_bins > 2 || o.far_group < 0 || o.far_group > 4 || o.toep_split < 0 || o.toep_split > 2 ||
-        (o.step_group != 0 && o.step_group != 1 && o.step_group != 2 && o.step_group != 4 && o.step_group != 8) ||
-        o.far_phase2 < 0 || o.far_phase2 > 2 || o.windows < 0 || o.windows > 2)
-        return fail(NEO_HIP_EINVAL, "invalid convolver options");
     *out = nullptr;
-    if (channels < 1) return fail(NEO_HIP_EINVAL, "channels must be >= 1");
-    if (!valid_block(block)) return fail(NEO_HIP_EINVAL, "block must be a power of two in [16, 4096], got %d", block);
-    if (partitions < 1) return fail(NEO_HIP_EINVAL, "partitions must be >= 1");
+    upols_shape shape;
+    if (const char* why = make_upols_shape(channels, block, partitions, opt, kind, borrow != nullptr, shape))
+        return fail(NEO_HIP_EINVAL, "%s", why);
+    const bool sparse = kind == upols_kind::sparse, v2 = kind == upols_kind::v2;
     device_guard g(device);
     if (g.rc) return g.rc;
     auto* h = new upols_t{};
-    (void)hipGetDevice(&h->device);
-    // the shape, the level plan and schedule options, the FDL ring's rows (levels_plan.hpp)
-    if (const char* why = make_level_sched(channels, block, partitions, partitions + kMaxBatch - 1, o, borrow != nullptr, v2,
-                                           h->sched)) {
-        delete h;
-        return fail(NEO_HIP_EINVAL, "%s", why);
-    }
-    h->bg_pad = bg_pad_for(channels, block);
-    // offline windows (k_off_mac): a pass of 128 wp blocks reads rows back to t_W - 128 nseg while
-    // writing rows t_W .. t_W + 128 wp - 1
-    h->off = !v2 && partitions >= kOffMinP;
-    h->off_nseg = (partitions + kFarT - 1) / kFarT;
-    if (h->off) h->ring = std::max(h->ring, kFarT * (h->off_nseg + kOffMaxWP) + NEO_OFF_RING_PAD);
-    h->ola = ola || v2;
-    h->v2 = v2;
-    h->fused = 2.0 * 8.0 * double(channels) * double(partitions) * double(block) < double(kFusedMaxBytes);
-    if (o.fused >= 0) h->fused = o.fused != 0;
-    if (o.batch_blocks) h->bT = o.batch_blocks;
-    if (o.batch_bins) h->bNB = o.batch_bins;
-    // filter rows kept resident in the Infinity Cache across steps: the first pc rows of
-    // every channel are read with the default policy, ~216 MiB in all (A/B on MI355X: C5
-    // 0.302 -> 0.286 ms per MAC at 220 rows, C4 0.295 -> 0.282 at 400; past ~250 MiB
-    // the cached rows start evicting each other)
-    h->pc = int(std::min<double>(partitions, kCacheBudgetBytes / (double(channels) * block * sizeof(cf))));
-    h->cstride = int64_t(h->ring) * block;
-    h->pstride = block;
-    // splits per channel: aim for ~1024 workgroups (4 per CU, all resident at 8 waves/SIMD;
-    // A/B on MI355X: 1024 beat 512/768/2048/4096 at C4 and C5), <= 64 partial slabs
-    const int target = o.split_workgroups ? o.split_workgroups : 1024;
-    // >= 8 rows per split keeps the slab sum short at small C; the one-launch (latency) form
-    // takes >= 16 (C3: 12 splits, 9.6 vs 10.6 us per block with 24)
-    // (an explicit workgroup target is taken as given)
-    // (an explicit workgroup target is taken as given); above B = 512 the one-launch form takes
-    // >= 8 rows: a split's rows stream through one CU (~130 GB/s), the tail sums the slabs alone.
-    // One channel, P = 32, us per step with 2 / 4 / 8 splits (normal; latency mode): B = 4096
-    // 25.1 / 22.6 / 22.3 (22.5 / 21.2 / 23.4), B = 2048 16.3 / 15.2 / 15.2 (12.8 / 11.9 / 12.4),
-    // B = 1024 12.5 / 12.2 / 12.7 (10.0 / 9.3 / 9.6) (tools/plain_split_sweep.py)
-    const int min_rows = o.split_workgroups ? 1 : h->fused ? (block > 512 ? 8 : 16) : 8;
-    int S = std::max(1, std::min({(target + channels - 1) / channels, (partitions + min_rows - 1) / min_rows, 64}));
-    h->rows = (partitions + S - 1) / S;
-    h->S = (partitions + h->rows - 1) / h->rows;
-    // batched passes: same workgroup target, >= 2T partitions per split so the sliding FDL
-    // window's warm-up (T - 1 extra rows per split) stays under half the split's rows
-    h->bufload = (int64_t(h->ring - 1) * h->pstride + block) * int64_t(sizeof(cf)) < (int64_t(1) << 31);
-    h->pcb = int(std::min<double>(partitions, kBatchCacheBudgetBytes / (double(channels) * block * sizeof(cf))));
-    // batched MAC: 256-lane workgroups at 2 waves/SIMD -> 2 resident per CU, so 512 fills the
-    // chip once with no second round (A/B, bmac_var 3: C5 0.409 -> 0.367 ms per pass, C4 0.369
-    // -> 0.379 ms, within run-to-run spread)
-    const int btarget = 512;
-    const int bt = batch_t(block, h->bNB, h->bT);
-    // workgroups per (channel, split): the batched MAC has one lane per bin, <= 256 lanes
-    const int bgroups = std::max(1, block / h->bNB / 256);
-    int Sb = std::max(1, std::min({(btarget + channels * bgroups - 1) / (channels * bgroups), partitions / (2 * bt), 64}));
-    if (h->ring - partitions < bt - 1) h->batch = false;  // ring too short for a batch
-    // streaming levels (upols_levels.hip) instead of one pass over filter + FDL per block,
-    // from 64 partitions, blocks up to 1024; short filters keep the plain step, whose one pass
-    // is already small (its working set sits in the Infinity Cache)
-    h->ahead = !v2 && block <= 1024 && (o.levels >= 0 ? o.levels != 0 : partitions >= 64);
-    h->rows_b = ((partitions + Sb - 1) / Sb + kMaxBatch - 1) / kMaxBatch * kMaxBatch;  // whole chunks of any T
-    h->Sb = (partitions + h->rows_b - 1) / h->rows_b;
-    const size_t rowbytes = size_t(block) * sizeof(cf);
-    const size_t nrows = size_t(channels) * size_t(h->ring);  // H uses the first P rows of each channel
+    h->shape = std::move(shape);
     auto bail = [&](int code) {
         destroy(h);
         return code;
     };
+    (void)hipGetDevice(&h->device);
+    h->sparse = sparse;
+    h->v2 = v2;
+    h->ola = ola || v2;
+    if (!sparse) h->bg_pad = bg_pad_for(channels, block);
     // a group member runs its setup and host-I/O work on its group's stream (upols_group.hip),
     // every other handle on one of its device's four shared streams (dmem.hip shared_stream: a
     // stream of its own would cost ~4 ms to create and ~3 ms to destroy; the first four handles on
@@ -625,20 +573,21 @@ int create_convolver(int channels, int block, int partitions, int device, bool o
         if (int rc = shared_stream(&h->stream)) return bail(rc);
 #endif
     }
-    // filter and FDL in ONE allocation (FDL = rows [nrows, 2 nrows)): the LDS-DMA batched MAC
-    // reaches both of a channel through a single buffer descriptor
-    if (dalloc(&h->H, 2 * nrows * rowbytes) || dalloc(&h->part, size_t(channels) * h->S * rowbytes) ||
+    const size_t rowbytes = size_t(block) * sizeof(cf);
+    const size_t nrows = size_t(channels) * size_t(h->ring);  // H uses the first P rows of each channel
+    const size_t ringbytes = (sparse ? 1 : 2) * nrows * rowbytes;
+    if (dalloc(sparse ? &h->fdl : &h->H, ringbytes) || dalloc(&h->part, size_t(channels) * h->shape.S * rowbytes) ||
         dalloc(&h->prev, size_t(channels) * block * sizeof(float)) || dalloc(&h->arrivals, size_t(channels) * sizeof(int)) ||
         (v2 && (dalloc(&h->window, size_t(channels) * 2 * block * sizeof(float)) ||
-                dalloc(&h->tmp, size_t(channels) * rowbytes))))
-        return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", 2 * nrows * rowbytes));
-    h->fdl = h->H + nrows * size_t(block);
-    int rc = shared_tw(&h->tw, block);
-    if (rc) return bail(rc);
+                dalloc(&h->tmp, size_t(channels) * rowbytes))) ||
+        (sparse && sparse_alloc(h)))
+        return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", ringbytes));
+    if (!sparse) h->fdl = h->H + nrows * size_t(block);
+    if (int rc = shared_tw(&h->tw, block)) return bail(rc);
     // stream-ordered zeroing, one wait at the end (the caller's later work may run on any stream)
-    if (hipMemsetAsync(h->H, 0, nrows * rowbytes, h->stream) != hipSuccess)
+    if (!sparse && hipMemsetAsync(h->H, 0, nrows * rowbytes, h->stream) != hipSuccess)
         return bail(fail(NEO_HIP_ERUNTIME, "memset failed"));
-    if ((rc = reset_state(h, h->stream))) return bail(rc);
+    if (int rc = reset_state(h, h->stream)) return bail(rc);
     if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(NEO_HIP_ERUNTIME, "sync failed"));
     *out = h;
     return NEO_HIP_OK;
@@ -648,82 +597,89 @@ int create_convolver(int channels, int block, int partitions, int device, bool o
 int neo_hip::create_handle(int channels, int block, int partitions, int device, int method, hipStream_t stream,
                            neo_hip_upols** out)
 {
-    const int rc = create_convolver(channels, block, partitions, device, method >= 1, method == 2, nullptr, out, stream);
+    const int rc = create_convolver(channels, block, partitions, device, method == 2 ? upols_kind::v2 : upols_kind::dense,
+                                    method >= 1, nullptr, out, stream);
     if (!rc) (*out)->grouped = true;
     return rc;
 }
 
+// -- the filter calls: checks, set_begin, a body that names what differs (pack, or normalize +
+// partition; the caller's mask or the perceptual one; the dense or the sparse store), set_end. Every
+// temporary is pooled scratch that set_end gives back once the handle's stream is joined. ----------
 namespace {
-// A sparse handle (sparse_upols_convolver / sparse_upola_convolver, src/neo/convolution/
-// sparse_convolver.hpp:12-17): the FDL ring, the step state and the bitmaps / offsets; the
-// compacted tiles come with the filter (sparse_set_filter). No dense filter buffer, no level or
-// offline buffers; the batch buffers come with the first batched pass.
-int create_sparse(int channels, int block, int partitions, int device, bool ola, const neo_hip_upols_opts* opt,
-                  neo_hip_upols** out)
+
+// after this handle's steps on any stream (and a device input's producer); a resident
+// latency-mode kernel leaves first
+int set_begin(upols_t* h, bool device_input)
 {
-    if (!out) return fail(NEO_HIP_EINVAL, "handle pointer is null");
-    *out = nullptr;
-    const int o_fused = opt ? opt->fused : -1, o_split = opt ? opt->split_workgroups : 0;
-    if (o_fused < -1 || o_fused > 1 || o_split < 0) return fail(NEO_HIP_EINVAL, "invalid convolver options");
-    if (channels < 1) return fail(NEO_HIP_EINVAL, "channels must be >= 1");
-    if (!valid_block(block)) return fail(NEO_HIP_EINVAL, "block must be a power of two in [16, 4096], got %d", block);
-    if (partitions < 1) return fail(NEO_HIP_EINVAL, "partitions must be >= 1");
-    // the step reads a channel's FDL ring (and its tiles, never more bytes than P rows) through one
-    // buffer descriptor each
-    if ((int64_t(partitions) + kMaxBatch - 1) * block * int64_t(sizeof(cf)) >= (int64_t(1) << 31))
-        return fail(NEO_HIP_EINVAL, "sparse convolvers take channels whose FDL ring spans < 2 GiB (%d partitions of %d)",
-                    partitions, block);
-    device_guard g(device);
-    if (g.rc) return g.rc;
-    auto* h = new upols_t{};
-    (void)hipGetDevice(&h->device);
-    h->sparse = true;
-    h->C = channels;
-    h->B = block;
-    h->P = partitions;
-    h->ring = partitions + kMaxBatch - 1;
-    h->ola = ola;
-    // process_blocks: one block per pass through the sparse step unless neo_hip_upols_set_batch
-    // turns the batched passes on (upols_sparse_batch.hip); their splits follow create_convolver's
-    // rule on the dense shape (one lane per bin, 512 workgroups, >= 2 T partitions per split, whole
-    // chunks of kMaxBatch); part_b and tail come with the first batched pass (launch_batch)
-    h->batch = false;
-    {
-        const int bgroups = std::max(1, block / 256);
-        const int Sb = std::max(1, std::min({(512 + channels * bgroups - 1) / (channels * bgroups),
-                                             partitions / (2 * batch_blocks(h)), 64}));
-        h->rows_b = ((partitions + Sb - 1) / Sb + kMaxBatch - 1) / kMaxBatch * kMaxBatch;
-        h->Sb = (partitions + h->rows_b - 1) / h->rows_b;
-    }
-    // one launch or two, and the splits: the dense plain step's rules (create_convolver) on the
-    // dense shape, so a sparse handle and a dense one of the same shape and options cut the
-    // partitions alike (equal row counts; the order per bin is the dense order)
-    h->fused = 2.0 * 8.0 * double(channels) * double(partitions) * double(block) < double(kFusedMaxBytes);
-    if (o_fused >= 0) h->fused = o_fused != 0;
-    h->cstride = int64_t(h->ring) * block;
-    h->pstride = block;
-    const int target = o_split ? o_split : 1024;
-    const int min_rows = o_split ? 1 : h->fused ? (block > 512 ? 8 : 16) : 8;
-    const int S = std::max(1, std::min({(target + channels - 1) / channels, (partitions + min_rows - 1) / min_rows, 64}));
-    h->rows = (partitions + S - 1) / S;
-    h->S = (partitions + h->rows - 1) / h->rows;
-    const size_t rowbytes = size_t(block) * sizeof(cf);
-    auto bail = [&](int code) {
-        destroy(h);
-        return code;
-    };
-    if (int rc = shared_stream(&h->stream)) return bail(rc);
-    if (dalloc(&h->fdl, size_t(channels) * size_t(h->ring) * rowbytes) ||
-        dalloc(&h->part, size_t(channels) * h->S * rowbytes) || dalloc(&h->prev, size_t(channels) * block * sizeof(float)) ||
-        dalloc(&h->arrivals, size_t(channels) * sizeof(int)) || sparse_alloc(h))
-        return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", size_t(channels) * size_t(h->ring) * rowbytes));
-    int rc = shared_tw(&h->tw, block);
-    if (rc) return bail(rc);
-    if ((rc = reset_state(h, h->stream))) return bail(rc);
-    if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(fail(NEO_HIP_ERUNTIME, "sync failed"));
-    *out = h;
+    if (int rc = persist_stop(h)) return rc;
+    return setup_join(h, device_input);
+}
+
+// A filter call's last steps, rc its body's result: the levels' and the offline windows' spectra
+// are stale, the state is rebuilt as the reference's filter() does
+// (uniform_partitioned_convolver.hpp:37-45) and, its next call being an ordinary block step
+// (:47-65), the levels' setup runs here, not there; then the stream is joined and the scratch goes
+// back, whatever rc is. (A sparse handle has no levels: both level calls change nothing.)
+int set_end(upols_t* h, int rc, std::initializer_list<void*> scratch)
+{
+    lvl_filter_changed(h);
+    if (!rc) rc = reset_state(h, h->stream);
+    if (!rc) rc = lvl_setup_prime(h);
+    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    for (void* p : scratch) dfree(p);
+    return rc;
+}
+
+int check_impulse(const upols_t* h, int64_t length)
+{
+    if (partitions_for(length, h->B) != h->P)
+        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
+                    (long long)partitions_for(length, h->B), h->P);
     return NEO_HIP_OK;
 }
+
+// impulse [C][length], host or device -> a copy of it (*tmp), normalized on request, partitioned:
+// packed into the handle's filter rows (out null) or as [C][P][B + 1] into out
+int load_impulse(upols_t* h, const float* ir, int64_t length, int normalize, int is_device, cf* out, float** tmp)
+{
+    const float* d = nullptr;
+    int rc = stage_in(ir, size_t(h->C) * size_t(length) * sizeof(float), is_device != 0, true, h->stream, tmp, &d);
+    if (!rc && normalize) rc = normalize_device(*tmp, h->C, length, h->stream);
+    if (!rc)
+        rc = out ? partition_device(d, h->C, length, h->B, false, out, h->tw, h->stream)
+                 : partition_device(d, h->C, length, h->B, true, h->H, h->tw, h->stream, h->shape.cstride, h->shape.pstride);
+    return rc;
+}
+
+// a sparse handle's perceptual calls: their checks, and the store of a device filter [C][P][B + 1]
+// under the mask the predicate gives it (perceptual.hip; w: the host weights [B + 1], alive until
+// the stream is joined)
+int check_perceptual(const char* who, const upols_t* h, const void* src, const neo_hip_perceptual* pp)
+{
+    if (!h || !src || !pp) return fail(NEO_HIP_EINVAL, "%s: null handle, input or parameters", who);
+    if (!h->sparse) return fail(NEO_HIP_EINVAL, "%s: not a sparse handle (neo_hip_upols_create_sparse)", who);
+    if (const char* why = perceptual_check(h->B, pp)) return fail(NEO_HIP_EINVAL, "%s: %s", who, why);
+    return NEO_HIP_OK;
+}
+
+size_t filter_elems(const upols_t* h) { return size_t(h->C) * size_t(h->P) * size_t(h->B + 1); }
+
+int store_perceptual(upols_t* h, const cf* filter, const neo_hip_perceptual* pp, const std::vector<float>& w,
+                     uint8_t** mask, float** tmp)
+{
+    if (dalloc(mask, filter_elems(h))) return fail(NEO_HIP_ENOMEM, "allocation failed");
+    if (int rc = perceptual_mask_device(filter, h->C, h->B, h->P, pp, w.data(), *mask, tmp, h->stream)) return rc;
+    return sparse_set_filter(h, filter, *mask, h->stream);
+}
+
+std::vector<float> weights_for(const upols_t* h, const neo_hip_perceptual* pp)
+{
+    std::vector<float> w(size_t(h->B) + 1);
+    perceptual_weights(h->B, pp, w.data());
+    return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -733,7 +689,7 @@ NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partiti
 {
     if (method < 0 || method > 1)
         return fail(NEO_HIP_EINVAL, "sparse convolvers: method must be 0 (upols) or 1 (upola); whole blocks only");
-    return create_sparse(channels, block, partitions, device, method == 1, opts, out);
+    return create_convolver(channels, block, partitions, device, upols_kind::sparse, method == 1, opts, out);
 }
 
 NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device)
@@ -742,105 +698,55 @@ NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* fi
     if (!h->sparse) return fail(NEO_HIP_EINVAL, "set_filter_sparse: not a sparse handle (neo_hip_upols_create_sparse)");
     device_guard g(h->device);
     if (g.rc) return g.rc;
-    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device filter's producer)
-    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
-    const cf* src = static_cast<const cf*>(filter);
-    const uint8_t* msk = mask;
-    cf* tmp = nullptr;
+    if (int rc = set_begin(h, is_device != 0)) return rc;
+    const size_t n = filter_elems(h);
+    cf* tmpf = nullptr;
+    const cf* src = nullptr;
     uint8_t* tmpm = nullptr;
-    int rc = NEO_HIP_OK;
-    if (!is_device) {
-        if (dalloc(&tmp, n * sizeof(cf)) || dalloc(&tmpm, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-        else if (hipMemcpyAsync(tmp, filter, n * sizeof(cf), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-                 hipMemcpyAsync(tmpm, mask, n, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmp;
-        msk = tmpm;
-    }
+    const uint8_t* msk = nullptr;
+    int rc = stage_in(static_cast<const cf*>(filter), n * sizeof(cf), is_device != 0, false, h->stream, &tmpf, &src);
+    if (!rc) rc = stage_in(mask, n, is_device != 0, false, h->stream, &tmpm, &msk);
     if (!rc) rc = sparse_set_filter(h, src, msk, h->stream);
-    if (!rc) rc = reset_state(h, h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(tmp);  // the stream was joined above
-    dfree(tmpm);
-    return rc;
+    return set_end(h, rc, {tmpf, tmpm});
 }
 
 // The perceptual forms: the mask is made on the device (perceptual.hip) from spectra that are
-// already there, then sparse_set_filter runs unchanged. Temporaries are pooled and go back before
-// the call returns; every wait is on the handle's stream.
+// already there, then sparse_set_filter runs unchanged.
 NEO_HIP_API int neo_hip_upols_set_filter_perceptual(neo_hip_upols* h, const void* filter, const neo_hip_perceptual* pp,
                                                     int is_device)
 {
-    if (!h || !filter || !pp) return fail(NEO_HIP_EINVAL, "set_filter_perceptual: null handle, filter or parameters");
-    if (!h->sparse)
-        return fail(NEO_HIP_EINVAL, "set_filter_perceptual: not a sparse handle (neo_hip_upols_create_sparse)");
-    if (const char* why = perceptual_check(h->B, pp)) return fail(NEO_HIP_EINVAL, "set_filter_perceptual: %s", why);
+    if (int rc = check_perceptual("set_filter_perceptual", h, filter, pp)) return rc;
     device_guard g(h->device);
     if (g.rc) return g.rc;
-    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device filter's producer)
-    std::vector<float> w(size_t(h->B) + 1);
-    perceptual_weights(h->B, pp, w.data());
-    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
-    const cf* src = static_cast<const cf*>(filter);
+    if (int rc = set_begin(h, is_device != 0)) return rc;
+    const std::vector<float> w = weights_for(h, pp);
     cf* tmpf = nullptr;
     uint8_t* mask = nullptr;
     float* tmp = nullptr;
-    int rc = NEO_HIP_OK;
-    if (dalloc(&mask, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-    if (!rc && !is_device) {
-        if (dalloc(&tmpf, n * sizeof(cf))) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-        else if (hipMemcpyAsync(tmpf, filter, n * sizeof(cf), hipMemcpyHostToDevice, h->stream) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "filter copy failed");
-        src = tmpf;
-    }
-    if (!rc) rc = perceptual_mask_device(src, h->C, h->B, h->P, pp, w.data(), mask, &tmp, h->stream);
-    if (!rc) rc = sparse_set_filter(h, src, mask, h->stream);
-    if (!rc) rc = reset_state(h, h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(tmp);  // the stream was joined above
-    dfree(tmpf);
-    dfree(mask);
-    return rc;
+    const cf* src = nullptr;
+    int rc = stage_in(static_cast<const cf*>(filter), filter_elems(h) * sizeof(cf), is_device != 0, false, h->stream, &tmpf, &src);
+    if (!rc) rc = store_perceptual(h, src, pp, w, &mask, &tmp);
+    return set_end(h, rc, {tmp, tmpf, mask});
 }
 
 NEO_HIP_API int neo_hip_upols_set_impulse_perceptual(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
                                                      const neo_hip_perceptual* pp, int is_device)
 {
-    if (!h || !ir || !pp || length < 1)
-        return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: null handle, ir or parameters, or empty impulse");
-    if (!h->sparse)
-        return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: not a sparse handle (neo_hip_upols_create_sparse)");
-    if (const char* why = perceptual_check(h->B, pp)) return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: %s", why);
-    if (partitions_for(length, h->B) != h->P)
-        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
-                    (long long)partitions_for(length, h->B), h->P);
+    if (length < 1) return fail(NEO_HIP_EINVAL, "set_impulse_perceptual: empty impulse");
+    if (int rc = check_perceptual("set_impulse_perceptual", h, ir, pp)) return rc;
+    if (int rc = check_impulse(h, length)) return rc;
     device_guard g(h->device);
     if (g.rc) return g.rc;
-    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device IR's producer)
-    std::vector<float> w(size_t(h->B) + 1);
-    perceptual_weights(h->B, pp, w.data());
-    const size_t bytes = size_t(h->C) * size_t(length) * sizeof(float);
-    const size_t n = size_t(h->C) * size_t(h->P) * size_t(h->B + 1);
+    if (int rc = set_begin(h, is_device != 0)) return rc;
+    const std::vector<float> w = weights_for(h, pp);
     float* d = nullptr;
     cf* parts = nullptr;
     uint8_t* mask = nullptr;
     float* tmp = nullptr;
-    int rc = NEO_HIP_OK;
-    if (dalloc(&d, bytes) || dalloc(&parts, n * sizeof(cf)) || dalloc(&mask, n)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-    else if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream) !=
-             hipSuccess)
-        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
-    if (!rc && normalize) rc = normalize_device(d, h->C, length, h->stream);
-    if (!rc) rc = partition_device(d, h->C, length, h->B, false, parts, h->tw, h->stream);
-    if (!rc) rc = perceptual_mask_device(parts, h->C, h->B, h->P, pp, w.data(), mask, &tmp, h->stream);
-    if (!rc) rc = sparse_set_filter(h, parts, mask, h->stream);
-    if (!rc) rc = reset_state(h, h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(tmp);  // the stream was joined above
-    dfree(d);
-    dfree(parts);
-    dfree(mask);
-    return rc;
+    int rc = dalloc(&parts, filter_elems(h) * sizeof(cf)) ? fail(NEO_HIP_ENOMEM, "allocation failed") : NEO_HIP_OK;
+    if (!rc) rc = load_impulse(h, ir, length, normalize, is_device, parts, &d);
+    if (!rc) rc = store_perceptual(h, parts, pp, w, &mask, &tmp);
+    return set_end(h, rc, {tmp, d, parts, mask});
 }
 
 NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, int64_t* kept_tiles, int64_t* filter_bytes)
@@ -869,7 +775,7 @@ NEO_HIP_API int neo_hip_upols_sparse_batch_info(neo_hip_upols* h, int* blocks_pe
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     if (!h->sparse) return fail(NEO_HIP_EINVAL, "sparse_batch_info: not a sparse handle");
     if (blocks_per_pass) *blocks_per_pass = batch_blocks(h);
-    if (splits) *splits = h->Sb;
+    if (splits) *splits = h->shape.Sb;
     if (window_tiles) *window_tiles = h->sp_wtiles;
     return NEO_HIP_OK;
 }
@@ -885,24 +791,25 @@ NEO_HIP_API int neo_hip_upols_sparse_plan(const uint8_t* mask, int channels, int
 
 NEO_HIP_API int neo_hip_upols_create(int channels, int block, int partitions, int device, neo_hip_upols** out)
 {
-    return create_convolver(channels, block, partitions, device, false, false, nullptr, out);
+    return create_convolver(channels, block, partitions, device, upols_kind::dense, false, nullptr, out);
 }
 
 NEO_HIP_API int neo_hip_upola_create(int channels, int block, int partitions, int device, neo_hip_upols** out)
 {
-    return create_convolver(channels, block, partitions, device, true, false, nullptr, out);
+    return create_convolver(channels, block, partitions, device, upols_kind::dense, true, nullptr, out);
 }
 
 NEO_HIP_API int neo_hip_upola2_create(int channels, int block, int partitions, int device, neo_hip_upols** out)
 {
-    return create_convolver(channels, block, partitions, device, true, true, nullptr, out);
+    return create_convolver(channels, block, partitions, device, upols_kind::v2, true, nullptr, out);
 }
 
 NEO_HIP_API int neo_hip_upols_create_ex(int channels, int block, int partitions, int device, int method,
                                         const neo_hip_upols_opts* opts, neo_hip_upols** out)
 {
     if (method < 0 || method > 2) return fail(NEO_HIP_EINVAL, "method must be 0 (upols), 1 (upola) or 2 (upola v2)");
-    return create_convolver(channels, block, partitions, device, method >= 1, method == 2, opts, out);
+    return create_convolver(channels, block, partitions, device, method == 2 ? upols_kind::v2 : upols_kind::dense,
+                            method >= 1, opts, out);
 }
 
 NEO_HIP_API int neo_hip_upols_destroy(neo_hip_upols* h)
@@ -921,7 +828,7 @@ NEO_HIP_API int neo_hip_upols_info(neo_hip_upols* h, int* channels, int* block, 
     if (channels) *channels = h->C;
     if (block) *block = h->B;
     if (partitions) *partitions = h->P;
-    if (splits) *splits = h->S;
+    if (splits) *splits = h->shape.S;
     return NEO_HIP_OK;
 }
 
@@ -929,8 +836,7 @@ NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     device_guard g(h->device);
-    if (int rc = persist_stop(h)) return rc;
-    if (int rc = setup_join(h)) return rc;  // after this handle's steps on any stream
+    if (int rc = set_begin(h, false)) return rc;  // after this handle's steps on any stream
     int rc = reset_state(h, h->stream);
     if (!rc) rc = lvl_setup_prime(h);  // the next call is an ordinary streaming step
     if (rc) return rc;
@@ -945,26 +851,12 @@ NEO_HIP_API int neo_hip_upols_set_filter(neo_hip_upols* h, const void* filter, i
         return fail(NEO_HIP_EINVAL, "set_filter: a sparse handle keeps no dense filter (neo_hip_upols_set_filter_sparse)");
     device_guard g(h->device);
     if (g.rc) return g.rc;
-    if (int rc = persist_stop(h)) return rc;
-    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device filter's producer)
-    const int64_t rows = int64_t(h->C) * h->P;
-    const size_t bytes = size_t(rows) * size_t(h->B + 1) * sizeof(cf);
-    const cf* src = static_cast<const cf*>(filter);
+    if (int rc = set_begin(h, is_device != 0)) return rc;
     cf* tmp = nullptr;
-    if (!is_device) {
-        if (int rc = dalloc(&tmp, bytes)) return rc;
-        NEO_HIP_CHECK(hipMemcpyAsync(tmp, filter, bytes, hipMemcpyHostToDevice, h->stream));
-        src = tmp;
-    }
-    int rc = pack_filter(h, src, h->stream);
-    lvl_filter_changed(h);
-    if (!rc) rc = reset_state(h, h->stream);
-    // the reference's filter() rebuilds the convolver's state (uniform_partitioned_convolver.hpp:37-45)
-    // and its next call is an ordinary block step (:47-65): the levels' setup runs here, not there
-    if (!rc) rc = lvl_setup_prime(h);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(tmp);  // the stream was joined above
-    return rc;
+    const cf* src = nullptr;
+    int rc = stage_in(static_cast<const cf*>(filter), filter_elems(h) * sizeof(cf), is_device != 0, false, h->stream, &tmp, &src);
+    if (!rc) rc = pack_filter(h, src, h->stream);
+    return set_end(h, rc, {tmp});
 }
 
 NEO_HIP_API int neo_hip_upols_set_impulse(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
@@ -974,30 +866,13 @@ NEO_HIP_API int neo_hip_upols_set_impulse(neo_hip_upols* h, const float* ir, int
     if (h->sparse)
         return fail(NEO_HIP_EINVAL, "set_impulse: a sparse handle takes a partitioned filter and its mask "
                                     "(neo_hip_upols_set_filter_sparse)");
-    if (partitions_for(length, h->B) != h->P)
-        return fail(NEO_HIP_EINVAL, "impulse of %lld taps gives %lld partitions, convolver has %d", (long long)length,
-                    (long long)partitions_for(length, h->B), h->P);
+    if (int rc = check_impulse(h, length)) return rc;
     device_guard g(h->device);
     if (g.rc) return g.rc;
-    if (int rc = persist_stop(h)) return rc;
-    if (int rc = setup_join(h, is_device != 0)) return rc;  // after this handle's steps (and a device IR's producer)
-    const size_t bytes = size_t(h->C) * size_t(length) * sizeof(float);
+    if (int rc = set_begin(h, is_device != 0)) return rc;
     float* d = nullptr;
-    if (int rc = dalloc(&d, bytes)) return rc;
-    int rc = NEO_HIP_OK;
-    if (hipMemcpyAsync(d, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream) !=
-        hipSuccess)
-        rc = fail(NEO_HIP_ERUNTIME, "impulse copy failed");
-    if (!rc && normalize) rc = normalize_device(d, h->C, length, h->stream);
-    if (!rc) rc = partition_device(d, h->C, length, h->B, true, h->H, h->tw, h->stream, h->cstride, h->pstride);
-    lvl_filter_changed(h);
-    if (!rc) rc = reset_state(h, h->stream);
-    // the reference's filter() rebuilds the convolver's state (uniform_partitioned_convolver.hpp:37-45)
-    // and its next call is an ordinary block step (:47-65): the levels' setup runs here, not there
-    if (!rc) rc = lvl_setup_prime(h);
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    dfree(d);
-    return rc;
+    const int rc = load_impulse(h, ir, length, normalize, is_device, nullptr, &d);
+    return set_end(h, rc, {d});
 }
 
 NEO_HIP_API int neo_hip_upols_process_device(neo_hip_upols* h, const float* in, int64_t ld_in, float* out,
@@ -1005,7 +880,7 @@ NEO_HIP_API int neo_hip_upols_process_device(neo_hip_upols* h, const float* in, 
 {
     if (!h || !in || !out) return fail(NEO_HIP_EINVAL, "null handle or buffer");
     if (ld_in < h->B || ld_out < h->B) return fail(NEO_HIP_EINVAL, "leading dimension smaller than the block");
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15 || (ld_in | ld_out) & 3)
+    if (!io_aligned(in, out, ld_in, ld_out))
         return fail(NEO_HIP_EINVAL, "device I/O must be 16-byte aligned (ld multiple of 4)");
     device_guard g(h->device);
     if (g.rc) return g.rc;
@@ -1018,7 +893,7 @@ NEO_HIP_API int neo_hip_upols_process_blocks(neo_hip_upols* h, const float* in, 
 {
     if (!h || !in || !out) return fail(NEO_HIP_EINVAL, "null handle or buffer");
     if (nblocks < 0 || ld < nblocks * h->B) return fail(NEO_HIP_EINVAL, "ld < nblocks * block");
-    if ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15 || ld & 3)
+    if (!io_aligned(in, out, ld, ld))
         return fail(NEO_HIP_EINVAL, "device I/O must be 16-byte aligned (ld multiple of 4)");
     device_guard g(h->device);
     if (g.rc) return g.rc;
@@ -1095,8 +970,8 @@ NEO_HIP_API int neo_hip_upols_process_samples(neo_hip_upols* h, const float* in,
 NEO_HIP_API int neo_hip_upols_batch_info(neo_hip_upols* h, int* blocks_per_pass, int* splits)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
-    if (blocks_per_pass) *blocks_per_pass = h->batch ? batch_blocks(h) : 1;
-    if (splits) *splits = h->batch ? h->Sb : h->S;
+    if (blocks_per_pass) *blocks_per_pass = h->shape.batch ? batch_blocks(h) : 1;
+    if (splits) *splits = h->shape.batch ? h->shape.Sb : h->shape.S;
     return NEO_HIP_OK;
 }
 
@@ -1105,7 +980,7 @@ NEO_HIP_API int neo_hip_upols_set_batch(neo_hip_upols* h, int enable)
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     if (enable && h->ring - h->P < batch_blocks(h) - 1)
         return fail(NEO_HIP_EINVAL, "the FDL ring is too short for a batch of %d blocks", batch_blocks(h));
-    h->batch = enable != 0;  // (a sparse handle: off until asked for; its batched MAC is k_sparse_batch_mac)
+    h->shape.batch = enable != 0;  // (a sparse handle: off until asked for; its batched MAC is k_sparse_batch_mac)
     return NEO_HIP_OK;
 }
 
@@ -1115,15 +990,15 @@ NEO_HIP_API int neo_hip_upols_set_offline(neo_hip_upols* h, int enable)
     if (enable && h->sparse) return fail(NEO_HIP_EINVAL, "a sparse handle has no offline windows (no dense filter spectra)");
     if (enable && (h->v2 || h->P < kOffMinP))
         return fail(NEO_HIP_EINVAL, "offline windows take whole-block handles of >= %d partitions", kOffMinP);
-    h->off = enable != 0;
+    h->shape.off = enable != 0;
     return NEO_HIP_OK;
 }
 
 NEO_HIP_API int neo_hip_upols_get_offline(neo_hip_upols* h, int* enabled, int* segments)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
-    if (enabled) *enabled = h->off;
-    if (segments) *segments = h->off_nseg;
+    if (enabled) *enabled = h->shape.off;
+    if (segments) *segments = h->shape.off_nseg;
     return NEO_HIP_OK;
 }
 
@@ -1136,7 +1011,7 @@ NEO_HIP_API int neo_hip_upols_set_ahead(neo_hip_upols* h, int enable)
     device_guard g(h->device);
     if (int rc = persist_stop(h)) return rc;
     if (!enable) h->sched.persist = false;  // the latency mode runs the levels
-    h->ahead = enable != 0;
+    h->shape.ahead = enable != 0;
     h->lv_n = -1;  // the FDL is complete at any block boundary: the next step primes the levels
     return NEO_HIP_OK;
 }
@@ -1207,7 +1082,7 @@ NEO_HIP_API int neo_hip_upols_persist_step_times(neo_hip_upols* h, double* us, i
 NEO_HIP_API int neo_hip_upols_get_ahead(neo_hip_upols* h, int* enabled, int* phase, int* window, int* splits)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
-    if (enabled) *enabled = h->ahead;
+    if (enabled) *enabled = h->shape.ahead;
     if (phase) *phase = int(h->lv_n < 0 ? 0 : h->lv_n % kFarT);
     if (window) *window = h->sched.lv.nseg ? kFarT : (h->sched.lv.n ? h->sched.lv.T[h->sched.lv.n - 1] : 1);
     if (splits) *splits = h->sched.lv.n + (h->sched.lv.nseg ? 1 : 0);
@@ -1247,18 +1122,26 @@ static int drain_events(upols_t* h)
     return NEO_HIP_OK;
 }
 
+// forget the drained times: the per-part sums and the per-group totals
+static void clear_timing(upols_t* h)
+{
+    h->group_ms.clear();
+    for (int k = 0; k < 4; ++k) {
+        h->part_ms[k] = 0.0;
+        h->part_n[k] = 0;
+    }
+}
+
 NEO_HIP_API int neo_hip_upols_timing_detail(neo_hip_upols* h, double* ms, int64_t* launches)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     device_guard g(h->device);
     if (int rc = drain_events(h)) return rc;
-    h->group_ms.clear();
     for (int k = 0; k < 4; ++k) {
         if (ms) ms[k] = h->part_ms[k];
         if (launches) launches[k] = h->part_n[k];
-        h->part_ms[k] = 0.0;
-        h->part_n[k] = 0;
     }
+    clear_timing(h);
     return NEO_HIP_OK;
 }
 
@@ -1270,11 +1153,7 @@ NEO_HIP_API int neo_hip_upols_step_times(neo_hip_upols* h, double* ms, int64_t c
     const int64_t n = int64_t(h->group_ms.size());
     for (int64_t i = 0; i < std::min(n, cap); ++i) ms[i] = h->group_ms[size_t(i)];
     if (count) *count = n;
-    h->group_ms.clear();
-    for (int k = 0; k < 4; ++k) {
-        h->part_ms[k] = 0.0;
-        h->part_n[k] = 0;
-    }
+    clear_timing(h);
     return NEO_HIP_OK;
 }
 

@@ -396,20 +396,20 @@ template<int BB, int NB>
 int launch_batch_mac(const upols_t* h, int T, hipStream_t s)
 {
     constexpr int L = batch_cfg<BB, NB>::L;
-    const unsigned grid = unsigned(h->C) * unsigned(h->Sb) * unsigned(batch_cfg<BB, NB>::G);
+    const unsigned grid = unsigned(h->C) * unsigned(h->shape.Sb) * unsigned(batch_cfg<BB, NB>::G);
 #define NEO_BATCH_T(TT)                                                                                          \
     case TT:                                                                                                     \
         if constexpr (batch_t(BB, NB, TT) == TT) {                                                               \
             if constexpr ((TT == 32 || TT == 16 || TT == 8) && NB == 1 && (BB == 256 || BB == 512)) {            \
-                if (h->bufload) {                                                                                \
+                if (h->shape.bufload) {                                                                                \
                     hipLaunchKernelGGL((k_batch_mac<BB, TT, NB, 3>), dim3(grid), dim3(L), 0, s, h->H, h->fdl,    \
-                                       h->part_b, h->P, h->ring, h->Sb, h->rows_b, h->wpos, h->cstride,          \
-                                       h->pstride, h->pcb);                                                      \
+                                       h->part_b, h->P, h->ring, h->shape.Sb, h->shape.rows_b, h->wpos, h->shape.cstride,          \
+                                       h->shape.pstride, h->shape.pcb);                                                      \
                     break;                                                                                       \
                 }                                                                                                \
             }                                                                                                    \
             hipLaunchKernelGGL((k_batch_mac<BB, TT, NB, 0>), dim3(grid), dim3(L), 0, s, h->H, h->fdl, h->part_b,  \
-                               h->P, h->ring, h->Sb, h->rows_b, h->wpos, h->cstride, h->pstride, h->pcb);        \
+                               h->P, h->ring, h->shape.Sb, h->shape.rows_b, h->wpos, h->shape.cstride, h->shape.pstride, h->shape.pcb);        \
             break;                                                                                               \
         }                                                                                                        \
         return fail(NEO_HIP_EINVAL, "batch of %d blocks not available at block %d", TT, BB);
@@ -429,58 +429,13 @@ int launch_batch_mac(const upols_t* h, int T, hipStream_t s)
 static int batch_buffers(upols_t* h)
 {
     if (!h->part_b) {
-        if (int rc = dalloc(&h->part_b, size_t(h->C) * h->Sb * kMaxBatch * h->B * sizeof(cf))) return rc;
+        if (int rc = dalloc(&h->part_b, size_t(h->C) * h->shape.Sb * kMaxBatch * h->B * sizeof(cf))) return rc;
         if (h->ola && dalloc(&h->tail, size_t(h->C) * kMaxBatch * h->B * sizeof(float))) {
             dfree(h->part_b);
             h->part_b = nullptr;
             return fail(NEO_HIP_ENOMEM, "batched OLA tail allocation failed");
         }
     }
-    return NEO_HIP_OK;
-}
-
-int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s)
-{
-    const int B = h->B;
-    int rc0 = batch_buffers(h);
-    if (rc0) return rc0;
-    const unsigned gCT = unsigned(h->C) * unsigned(T);
-    if (int rc = lvl_join(h, s)) return rc;  // step-group slices still reading the FDL ring
-    h->lv_n = -1;  // a streaming step after this re-primes its level windows
-    h->fdl_zero = false;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, true>), dim3(gCT), dim3(256), 0, s, in, ld_in,
-                                                 h->prev, h->fdl, h->tw, T, h->ring, h->wpos, h->cstride, h->pstride))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, false>), dim3(gCT), dim3(256), 0, s, in, ld_in,
-                                                 h->prev, h->fdl, h->tw, T, h->ring, h->wpos, h->cstride, h->pstride))
-    }
-    NEO_HIP_LAUNCH_CHECK();
-    upols_t::ev_group* ev = nullptr;
-    int rc = timing_begin(h, 2, &ev);
-    if (!rc) rc = timing_mark(ev, 0, s);
-    if (rc) return rc;
-    if (h->sparse) {  // the kept tiles only (upols_sparse_batch.hip); everything around it as below
-        rc = launch_sparse_batch_mac(h, T, s);
-    } else if (h->bNB == 2) {
-        NEO_UPOLS_DISPATCH(B, rc = (launch_batch_mac<BB, 2>(h, T, s)))
-    } else {
-        NEO_UPOLS_DISPATCH(B, rc = (launch_batch_mac<BB, 1>(h, T, s)))
-    }
-    if (rc) return rc;
-    if ((rc = timing_mark(ev, 1, s))) return rc;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, true>), dim3(gCT), dim3(256), 0, s, h->part_b,
-                                                 h->Sb, T, in, ld_in, out, ld_out, h->prev, h->tail, h->tw))
-        NEO_HIP_LAUNCH_CHECK();
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_ola<BB>), dim3(unsigned(h->C)), dim3(256), 0, s, out, ld_out,
-                                                 h->tail, h->prev, T))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, false>), dim3(gCT), dim3(256), 0, s, h->part_b,
-                                                 h->Sb, T, in, ld_in, out, ld_out, h->prev, h->tail, h->tw))
-    }
-    NEO_HIP_LAUNCH_CHECK();
-    h->wpos = (h->wpos + T) % h->ring;
     return NEO_HIP_OK;
 }
 
@@ -500,35 +455,77 @@ int launch_batch_window(int C, int B, int T, bool ola, const float* in, int64_t 
     return NEO_HIP_OK;
 }
 
-int launch_batch_finish_nosave(int C, int B, int S, int T, bool ola, const cf* part, float* out, int64_t ld_out,
-                               float* tail, float* ovl, const cf* tw, hipStream_t s)
+int launch_batch_finish(int C, int B, int S, int T, bool ola, const cf* part, const float* in, int64_t ld_in, float* out,
+                        int64_t ld_out, float* prev, float* tail, float* ovl, const cf* tw, hipStream_t s)
 {
     const unsigned grid = unsigned(C) * unsigned(T);
-    const float* no_in = nullptr;
-    float* no_prev = nullptr;
-    if (ola) {  // (overlap-add saves no previous block: the dense pass's own instantiation)
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, true>), dim3(grid), dim3(256), 0, s, part, S, T,
-                                                 no_in, int64_t(0), out, ld_out, no_prev, tail, tw))
+    if (ola) {  // (overlap-add saves no previous block: one instantiation for both forms)
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, true>), dim3(grid), dim3(256), 0, s, part, S, T, in,
+                                                 ld_in, out, ld_out, prev, tail, tw))
         NEO_HIP_LAUNCH_CHECK();
         NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_ola<BB>), dim3(unsigned(C)), dim3(256), 0, s, out, ld_out, tail,
                                                  ovl, T))
+    } else if (in) {
+        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, false>), dim3(grid), dim3(256), 0, s, part, S, T, in,
+                                                 ld_in, out, ld_out, prev, tail, tw))
     } else {
         NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, false, false>), dim3(grid), dim3(256), 0, s, part, S,
-                                                 T, no_in, int64_t(0), out, ld_out, no_prev, tail, tw))
+                                                 T, in, ld_in, out, ld_out, prev, tail, tw))
     }
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }
 
+namespace {
+
+// What a dense or sparse handle's batched passes share around their MAC (mac(ev): its launches
+// between the timing marks): the window r2c of T blocks into FDL rows wpos .. wpos + T - 1, the
+// per-block finish over S slabs of `part` (saving the last block; OLA's overlap chain through
+// `tail`), the write position T rows on.
+template<class MAC>
+int batch_pass(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, const cf* part, int S,
+               float* tail, hipStream_t s, MAC mac)
+{
+    if (int rc = lvl_join(h, s)) return rc;  // step-group slices still reading the FDL ring
+    h->lv_n = -1;  // a streaming step after this re-primes its level windows
+    h->fdl_zero = false;
+    if (int rc = launch_batch_window(h->C, h->B, T, h->ola, in, ld_in, h->prev, h->fdl, h->tw, h->ring, h->wpos, s)) return rc;
+    upols_t::ev_group* ev = nullptr;
+    int rc = timing_begin(h, 2, &ev);
+    if (!rc) rc = timing_mark(ev, 0, s);
+    if (!rc) rc = mac();
+    if (!rc) rc = timing_mark(ev, 1, s);
+    if (!rc) rc = launch_batch_finish(h->C, h->B, S, T, h->ola, part, in, ld_in, out, ld_out, h->prev, tail, h->prev, h->tw, s);
+    if (!rc) advance(h, T);
+    return rc;
+}
+
+}  // namespace
+
+int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int T, hipStream_t s)
+{
+    if (int rc = batch_buffers(h)) return rc;
+    return batch_pass(h, in, ld_in, out, ld_out, T, h->part_b, h->shape.Sb, h->tail, s, [&] {
+        int rc = NEO_HIP_OK;
+        if (h->sparse) {  // the kept tiles only (upols_sparse_batch.hip); everything around it as for a dense handle
+            rc = launch_sparse_batch_mac(h, T, s);
+        } else if (h->shape.bNB == 2) {
+            NEO_UPOLS_DISPATCH(h->B, rc = (launch_batch_mac<BB, 2>(h, T, s)))
+        } else {
+            NEO_UPOLS_DISPATCH(h->B, rc = (launch_batch_mac<BB, 1>(h, T, s)))
+        }
+        return rc;
+    });
+}
+
 // Offline windows (k_off_mac, upols_levels.hip): wp windows of 128 blocks -- the window r2c of
 // every block into FDL rows w .. w + 128 wp - 1, the partition-axis transforms of every segment,
 // the per-block finish (one slab: k_off_mac's output spectra), OLA's overlap chain. The ring
-// holds >= 128 (nseg + kOffMaxWP) rows (create), so the new rows overwrite none the pass reads.
+// holds >= 128 (nseg + kOffMaxWP) rows (upols_plan.hpp), so the new rows overwrite none the pass reads.
 int launch_offline(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, int wp, hipStream_t s)
 {
-    const int B = h->B, T = kFarT * wp;
     if (!h->off_y) {
-        const size_t rows = size_t(h->C) * kFarT * kOffMaxWP * B;
+        const size_t rows = size_t(h->C) * kFarT * kOffMaxWP * h->B;
         if (int rc = dalloc(&h->off_y, rows * sizeof(cf))) return rc;
         if (dalloc(&h->off_hf, off_hf_bytes(h)) ||
             (h->ola && dalloc(&h->off_tail, rows * sizeof(float)))) {
@@ -540,37 +537,8 @@ int launch_offline(upols_t* h, const float* in, int64_t ld_in, float* out, int64
         }
         h->off_dirty = true;
     }
-    const unsigned gCT = unsigned(h->C) * unsigned(T);
-    if (int rc = lvl_join(h, s)) return rc;  // step-group slices still reading the FDL ring
-    h->lv_n = -1;  // a streaming step after this re-primes its level windows
-    h->fdl_zero = false;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, true>), dim3(gCT), dim3(256), 0, s, in, ld_in,
-                                                 h->prev, h->fdl, h->tw, T, h->ring, h->wpos, h->cstride, h->pstride))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_window<BB, false>), dim3(gCT), dim3(256), 0, s, in, ld_in,
-                                                 h->prev, h->fdl, h->tw, T, h->ring, h->wpos, h->cstride, h->pstride))
-    }
-    NEO_HIP_LAUNCH_CHECK();
-    upols_t::ev_group* ev = nullptr;
-    int rc = timing_begin(h, 2, &ev);
-    if (!rc) rc = timing_mark(ev, 0, s);
-    if (!rc) rc = launch_off_mac(h, wp, s);
-    if (!rc) rc = timing_mark(ev, 1, s);
-    if (rc) return rc;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, true>), dim3(gCT), dim3(256), 0, s, h->off_y, 1, T,
-                                                 in, ld_in, out, ld_out, h->prev, h->off_tail, h->tw))
-        NEO_HIP_LAUNCH_CHECK();
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_ola<BB>), dim3(unsigned(h->C)), dim3(256), 0, s, out, ld_out,
-                                                 h->off_tail, h->prev, T))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_batch_finish<BB, false>), dim3(gCT), dim3(256), 0, s, h->off_y, 1,
-                                                 T, in, ld_in, out, ld_out, h->prev, nullptr, h->tw))
-    }
-    NEO_HIP_LAUNCH_CHECK();
-    h->wpos = (h->wpos + T) % h->ring;
-    return NEO_HIP_OK;
+    return batch_pass(h, in, ld_in, out, ld_out, kFarT * wp, h->off_y, 1, h->off_tail, s,
+                      [&] { return launch_off_mac(h, wp, s); });
 }
 
 }  // namespace neo_hip

@@ -137,9 +137,9 @@ int live_count(const group_t* g)
 int copy_channel(neo_hip_upols* dst, int cd, const neo_hip_upols* src, int cs, const float* prev_src, hipStream_t s)
 {
     const size_t rows = size_t(src->ring) * size_t(src->B) * sizeof(cf);
-    NEO_HIP_CHECK(hipMemcpyAsync(dst->H + int64_t(cd) * dst->cstride, src->H + int64_t(cs) * src->cstride,
+    NEO_HIP_CHECK(hipMemcpyAsync(dst->H + int64_t(cd) * dst->shape.cstride, src->H + int64_t(cs) * src->shape.cstride,
                                  size_t(src->P) * size_t(src->B) * sizeof(cf), hipMemcpyDeviceToDevice, s));
-    NEO_HIP_CHECK(hipMemcpyAsync(dst->fdl + int64_t(cd) * dst->cstride, src->fdl + int64_t(cs) * src->cstride, rows,
+    NEO_HIP_CHECK(hipMemcpyAsync(dst->fdl + int64_t(cd) * dst->shape.cstride, src->fdl + int64_t(cs) * src->shape.cstride, rows,
                                  hipMemcpyDeviceToDevice, s));
     NEO_HIP_CHECK(hipMemcpyAsync(dst->prev + int64_t(cd) * dst->B, prev_src + int64_t(cs) * src->B,
                                  size_t(src->B) * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -286,7 +286,7 @@ int coalesce(group_t* g)
     NEO_HIP_CHECK(hipStreamSynchronize(g->stream));
     sh->wpos = wpos;
     neo_hip::lvl_filter_changed(sh);  // far segment spectra of the copied filters; the levels re-prime
-    sh->batch = false;
+    sh->shape.batch = false;
     for (auto& x : g->m)
         if (x.live) {
             neo_hip_upols_destroy(x.own);
@@ -317,7 +317,7 @@ int split(group_t* g)
             if (back) --x.steps;
         }
         neo_hip::lvl_filter_changed(x.own);
-        x.own->batch = false;
+        x.own->shape.batch = false;
         x.pending = false;
         x.slot = -1;
         x.seen = false;
@@ -366,7 +366,7 @@ int call_independent(group_t* g, int i, float* io)
     if (++g->nseen < live_count(g)) return NEO_HIP_OK;
     // a complete frame: equal block counts, distinct buffers, each the member's buffer of the
     // frame before (the leader of a coalesced frame reads them)
-    bool ok = live_count(g) >= 2 && x.own->ahead;
+    bool ok = live_count(g) >= 2 && x.own->shape.ahead;
     std::vector<const float*> ptrs;
     for (auto& y : g->m) {
         if (!y.live) continue;
@@ -620,7 +620,7 @@ NEO_HIP_API int neo_hip_upols_group_set_filter(neo_hip_upols_group* g, int id, c
         if (int rc = split(g)) return rc;
     member& x = g->m[size_t(id)];
     if (int rc = neo_hip_upols_set_filter(x.own, filter, is_device)) return rc;  // resets its state
-    x.own->batch = false;
+    x.own->shape.batch = false;
     x.filtered = true;
     x.steps = 0;
     x.seen = false;

@@ -1,14 +1,15 @@
 // upols_handle.hpp — the UPOLS convolver handle (neo_hip_upols) and the host helpers
 // shared by the translation units that implement it (upols.hip, upols_batch.hip,
 // upols_setup.hip, upols_levels.hip).
-//   constants, the latency mode's mailbox and device helpers
-//   neo_hip_upols: the handle; its level schedule is a level_sched (levels_plan.hpp: the level
-//       constants, level_plan, the plan and the schedule of the streaming levels, host only)
+//   the latency mode's mailbox and device helpers
+//   neo_hip_upols: the handle. Its shape plan is an upols_shape (upols_plan.hpp, host only: the
+//       create calls' checks, the split, cache and ring rules and their constants), which holds
+//       the level schedule (level_sched, levels_plan.hpp); the handle adds buffers and state
 //   what the translation units share: launches, setup helpers, the streaming levels' entry points
 #pragma once
 
 #include "common.hpp"
-#include "levels_plan.hpp"
+#include "upols_plan.hpp"
 
 #include <cstdint>
 #include <deque>
@@ -16,20 +17,6 @@
 #include <vector>
 
 namespace neo_hip {
-constexpr int kMaxBatch = 32;                          // most blocks one batched MAC pass consumes
-constexpr double kFusedMaxBytes = 64.0 * 1024 * 1024;  // filter + FDL bytes below which a step is one launch
-constexpr double kCacheBudgetBytes = 216.0 * 1024 * 1024;  // filter bytes read cacheable (256 MiB Infinity Cache)
-// the batched passes leave more of the Infinity Cache to the slabs (same-box A/B at C5, 4 runs
-// each: 168 MiB 17.8 us/step, 216 MiB 18.3, 126 MiB 18.1)
-constexpr double kBatchCacheBudgetBytes = 168.0 * 1024 * 1024;
-// offline windows (k_off_mac): batched calls of >= 128 blocks take windows of kFarT blocks through
-// partition-axis transforms of every 128-partition segment, from this many partitions
-#ifndef NEO_OFF_MIN_P
-#define NEO_OFF_MIN_P 128  // diagnostic builds (A/B)
-#endif
-constexpr int kOffMinP = NEO_OFF_MIN_P;
-constexpr int kOffMaxWP = 2;  // windows per pass
-
 // Latency mode (neo_hip_upols_set_persistent, upols_levels.hip): one persistent kernel per handle
 // polls a mailbox in mapped host memory. Step n's record (device addresses of its input and
 // output blocks) goes to slot n mod kPsRing; both words carry the slot's lap tag in their low 4
@@ -146,14 +133,15 @@ __device__ __forceinline__ bool ps_record(const persist_ctl& pc, int64_t n, bool
 }  // namespace neo_hip
 
 struct neo_hip_upols {
-    // the shape, the FDL ring's rows and everything the streaming levels' plan and schedule read
-    // (levels_plan.hpp); C, B, P and ring live there
-    neo_hip::level_sched sched;
+    // the plan (upols_plan.hpp): splits, cache rows, strides, which paths are on, and in its level
+    // schedule (levels_plan.hpp) the shape C, B, P and the FDL ring's rows
+    neo_hip::upols_shape shape;
+    neo_hip::level_sched& sched = shape.sched;
     int &C = sched.C, &B = sched.B, &P = sched.P, &ring = sched.ring;
     neo_hip_upols() = default;
     neo_hip_upols(const neo_hip_upols&) = delete;  // the references above
     neo_hip_upols& operator=(const neo_hip_upols&) = delete;
-    int device = 0, S = 1, rows = 1;
+    int device = 0;
     hipStream_t stream = nullptr;
     neo_hip::cf* H = nullptr;
     neo_hip::cf* fdl = nullptr;
@@ -164,14 +152,8 @@ struct neo_hip_upols {
     neo_hip::cf* tw = nullptr;
     float* io = nullptr;       // device staging for host-pointer process()
     float* io_host = nullptr;  // pinned staging
-    bool batch = true;      // process_blocks runs T blocks per MAC pass (neo_hip_upols_set_batch)
-    int Sb = 1, rows_b = 1; // batched-pass splits per channel and partitions per split
-    int bT = 32, bNB = 1;   // batched pass: blocks per pass (capped by batch_t), bins per lane-vector
-    int pcb = 0;            // filter rows per channel the batched MAC loads cacheable (kBatchCacheBudgetBytes)
-    bool bufload = true;    // batched MAC with buffer loads (one channel's rows span < 2 GiB)
     neo_hip::cf* part_b = nullptr;   // batched partial spectra [C][Sb][T][B]
-    // streaming levels (upols_levels.hip): on for HBM-bound shapes (neo_hip_upols_set_ahead)
-    bool ahead = false;
+    // streaming levels (upols_levels.hip; on: shape.ahead)
     int64_t lv_n = -1;              // blocks since the levels were primed (-1: prime at the next step)
     bool fdl_zero = false;          // FDL ring all zero, nothing stepped since (reset_state): every level
                                     // window the prime computes is zero, so priming is zeroing
@@ -197,10 +179,8 @@ struct neo_hip_upols {
     bool bg_busy = false;  // slices enqueued on bg since the last join
     int64_t bg_launches = 0;
     float* tail = nullptr;  // batched OLA tails [C][T][B]
-    // offline windows (k_off_mac, launch_offline): batched calls take 128 or 256 blocks per pass
-    bool off = false;                // eligible (P >= kOffMinP, whole-block handles) and on (neo_hip_upols_set_offline)
-    int off_nseg = 0;                // 128-partition segments from p = 0
-    neo_hip::cf* off_hf = nullptr;   // the filter's segment spectra [C][off_nseg][256][B]
+    // offline windows (k_off_mac, launch_offline; on: shape.off)
+    neo_hip::cf* off_hf = nullptr;   // the filter's segment spectra [C][shape.off_nseg][256][B]
     bool off_dirty = true;           // off_hf to recompute (filter changed)
     neo_hip::cf* off_y = nullptr;    // a pass's output spectra [C][128 kOffMaxWP][B]
     float* off_tail = nullptr;       // OLA: a pass's tails [C][128 kOffMaxWP][B]
@@ -214,14 +194,6 @@ struct neo_hip_upols {
     int in_pos = 0;    // v2: samples of the current block already consumed (_input_pos)
     float* window = nullptr;  // v2: real window [C][2B]
     neo_hip::cf* tmp = nullptr;        // v2: tail accumulator [C][B] packed (_tmp_accumulator)
-    // one launch per block (last-arriver tail) instead of MAC + finish: on for small filter
-    // + FDL working sets, where the step is launch-bound (C3: 10.6 vs 12.4 us per block),
-    // off for HBM-bound ones (C5: 0.342 vs 0.303 ms); NEO_HIP_FUSED=0/1 overrides
-    bool fused = false;
-    // H / FDL layout: row p of channel c at c * cstride + p * pstride (complex units).
-    // Default [C][P][B]; NEO_HIP_LAYOUT=pcb selects partition-major [P][C][B] (A/B).
-    int64_t cstride = 0, pstride = 0;
-    int pc = 0;  // filter rows per channel read with the cacheable policy (kCacheBudgetBytes; NEO_HIP_CACHE_ROWS)
     // sparse handle (neo_hip_upols_create_sparse, upols_sparse.hip; format: sparse_plan.hpp): no
     // dense filter (H stays null, the FDL is an allocation of its own), no levels or offline
     // windows; a block is one k_upols_sparse_step, or with batching on (off by default) T blocks
@@ -277,8 +249,6 @@ inline int note_stream(upols_t* h, hipStream_t s) { return h->used.note(s); }
 // after work on the null stream (a device-resident filter or impulse produced there)
 int setup_join(upols_t* h, bool device_input = false);
 
-inline bool valid_block(int b) { return b >= 16 && b <= 4096 && (b & (b - 1)) == 0; }
-
 #define NEO_UPOLS_DISPATCH(B_, BODY) \
     switch (B_) {                    \
         case 16: { constexpr int BB = 16; BODY; break; }     \
@@ -301,18 +271,14 @@ inline int64_t partitions_for(int64_t L, int B)
     return (L - B + B - 1) / B + 1;
 }
 
-// blocks per batched pass for block B and NB bins per lane-vector: the requested T,
-// capped so one lane's accumulators (T * NB * VPT * 4 floats) stay <= 128 registers
-constexpr int batch_t(int B, int NB, int want)
+inline int batch_blocks(const upols_t* h) { return batch_blocks(h->shape); }
+// the FDL write position T blocks on (fdl_index.hpp:35-37)
+inline void advance(upols_t* h, int T) { h->wpos = (h->wpos + T) % h->ring; }
+// device I/O the kernels' 16-byte accesses can take: both bases aligned, strides multiples of 4 floats
+inline bool io_aligned(const float* in, const float* out, int64_t ld_in, int64_t ld_out)
 {
-    (void)B;
-    const int VPT = 1;
-    int t = want;
-    while (t > 2 && t * NB * VPT > 32) t /= 2;
-    return t;
+    return !((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) && !((ld_in | ld_out) & 3);
 }
-
-inline int batch_blocks(const upols_t* h) { return batch_t(h->B, h->bNB, h->bT); }
 
 // a handle with default options whose setup and host-I/O work runs on `stream` (a group's; not
 // destroyed with the handle) instead of one of the device's shared streams (upols.hip)
@@ -320,11 +286,12 @@ int create_handle(int channels, int block, int partitions, int device, int metho
                   neo_hip_upols** out);
 // upols_sparse.hip: the sparse handle's buffers (bitmaps, offsets; the FDL and the step state are
 // the creator's), its filter (filter and mask [C][P][B + 1] on the device -> bitmaps, offsets and
-// compacted tiles; one 16-byte copy back, h->stream joined) and its block step
+// compacted tiles; one 24-byte copy back, h->stream joined) and its block step's MAC launch
+// (k_upols_sparse_step; launch_step_normal runs the frame around it)
 int sparse_alloc(upols_t* h);
 void sparse_free(upols_t* h);
 int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s);
-int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
+int launch_sparse_mac(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
 // upols_sparse_batch.hip: the MAC of a batched pass of a sparse handle (launch_batch, upols_batch.hip):
 // T blocks at write position h->wpos into the slabs part_b [C][Sb][T][B], over the kept tiles
 int launch_sparse_batch_mac(const upols_t* h, int T, hipStream_t s);
@@ -343,12 +310,14 @@ int launch_batch(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t
 // the launches around a batched MAC on plain arguments (upols_matrix.hip: a matrix handle's window
 // transforms run per input, its finish per output). Window: blocks 0..T-1 of C inputs into FDL rows
 // (w + j) mod ring of [C][ring][B]; prev [C][B] is read (overlap-save), not written. Finish: slabs
-// part [C][S][T][B] summed in order, c2r; it never reads the caller's input and saves no previous
-// block. Overlap-add then chains tail [C][T][B] and ovl [C][B] into out.
+// part [C][S][T][B] summed in order, c2r. With `in` (a dense or sparse handle's pass) overlap-save
+// saves block T - 1 of it as prev [C][B]; without (a matrix handle's: the previous block is per
+// input, the finish per output) it reads no input and saves nothing. Overlap-add then chains tail
+// [C][T][B] and ovl [C][B] into out.
 int launch_batch_window(int C, int B, int T, bool ola, const float* in, int64_t ld_in, const float* prev, cf* fdl,
                         const cf* tw, int ring, int w, hipStream_t s);
-int launch_batch_finish_nosave(int C, int B, int S, int T, bool ola, const cf* part, float* out, int64_t ld_out,
-                               float* tail, float* ovl, const cf* tw, hipStream_t s);
+int launch_batch_finish(int C, int B, int S, int T, bool ola, const cf* part, const float* in, int64_t ld_in, float* out,
+                        int64_t ld_out, float* prev, float* tail, float* ovl, const cf* tw, hipStream_t s);
 // upols_matrix_batch.hip: the MAC of a batched pass of a matrix handle: T blocks at write position w
 // into the slabs part [O][Sb][T][B]; tab is the batch plan's run_off and runs (matrix_plan.hpp)
 int launch_matrix_batch_mac(const cf* H, const cf* fdl, cf* part, const int* tab, int B, int P, int ring, int O, int Sb,
@@ -364,7 +333,7 @@ int64_t lvf_spec_stride(int nseg, int B);
 // (matrix_offline_pair_row, matrix_plan.hpp) -> xf [I][npairs][256][B]. mac: per output its routes
 // (tab: the handle's route table, matrix_route_table in matrix_plan.hpp, uploaded once with the
 // filter) x segments against hf, the inverse transforms -> y [O][128 wp][B], one slab of
-// launch_batch_finish_nosave.
+// launch_batch_finish.
 int launch_matrix_off_fwd(const cf* fdl, cf* xf, const cf* twf, int I, int B, int ring, int npairs, int wp, int w,
                           hipStream_t s);
 int launch_matrix_off_mac(const cf* xf, const cf* hf, cf* y, const cf* twf, const int* tab, int O, int B, int nseg,

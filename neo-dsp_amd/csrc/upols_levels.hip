@@ -1648,8 +1648,8 @@ static slice_args base_args(const upols_t* h)
     a.ring = h->ring;
     a.C = h->C;
     a.B = h->B;
-    a.cstride = h->cstride;
-    a.pstride = h->pstride;
+    a.cstride = h->shape.cstride;
+    a.pstride = h->shape.pstride;
     if (h->sched.lv.nseg) {
         a.M = h->sched.lv.nseg;
         a.nseg = h->sched.lv.nseg;
@@ -1824,7 +1824,7 @@ static int lvl_prime(upols_t* h, hipStream_t s)
     if (lp.nseg && h->fv_dirty && !sc.far_raw) {
         const unsigned grid = unsigned(C) * unsigned(lp.nseg) * unsigned(B / 16);
         hipLaunchKernelGGL(k_lvf_filter, dim3(grid), dim3(256), 0, s, h->H, h->fv_hf, h->fv_tw, B, h->P, lp.nseg,
-                           h->cstride, h->pstride, 0, spec_cs(lp.nseg, B), lp.farA);
+                           h->shape.cstride, h->shape.pstride, 0, spec_cs(lp.nseg, B), lp.farA);
         NEO_HIP_LAUNCH_CHECK();
         h->fv_dirty = false;
     }
@@ -1969,7 +1969,7 @@ int launch_levels(upols_t* h, const float* in, int64_t ld_in, float* out, int64_
     if ((rc = launch_step_kernel(h, a, s, G > 1 ? 1 : 0))) return rc;
     h->fdl_zero = false;
     if ((rc = timing_mark(ev, 1, s))) return rc;
-    h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;
+    advance(h, 1);
     h->lv_n = n + 1;
     return NEO_HIP_OK;
 }
@@ -1986,21 +1986,21 @@ int launch_lvf_filter(const cf* H, cf* hf, const cf* tw, int C, int B, int P, in
 
 int64_t lvf_spec_stride(int nseg, int B) { return spec_cs(nseg, B); }
 
-size_t off_hf_bytes(const upols_t* h) { return size_t(h->C) * size_t(spec_cs(h->off_nseg, h->B)) * sizeof(cf); }
+size_t off_hf_bytes(const upols_t* h) { return size_t(h->C) * size_t(spec_cs(h->shape.off_nseg, h->B)) * sizeof(cf); }
 
 int launch_off_mac(upols_t* h, int wp, hipStream_t s)
 {
     if (!h->fv_tw)
         if (int rc = shared_far_tw(&h->fv_tw)) return rc;
     if (h->off_dirty) {
-        const unsigned grid = unsigned(h->C) * unsigned(h->off_nseg) * unsigned(h->B / 16);
+        const unsigned grid = unsigned(h->C) * unsigned(h->shape.off_nseg) * unsigned(h->B / 16);
         hipLaunchKernelGGL(k_lvf_filter, dim3(grid), dim3(256), 0, s, h->H, h->off_hf, h->fv_tw, h->B, h->P,
-                           h->off_nseg, h->cstride, h->pstride, 0, spec_cs(h->off_nseg, h->B));
+                           h->shape.off_nseg, h->shape.cstride, h->shape.pstride, 0, spec_cs(h->shape.off_nseg, h->B));
         NEO_HIP_LAUNCH_CHECK();
         h->off_dirty = false;
     }
-    off_args a{h->fdl, h->off_hf, h->fv_tw, h->off_y, h->cstride, h->pstride, spec_cs(h->off_nseg, h->B), h->ring, h->B,
-               h->off_nseg, h->wpos};
+    off_args a{h->fdl, h->off_hf, h->fv_tw, h->off_y, h->shape.cstride, h->shape.pstride, spec_cs(h->shape.off_nseg, h->B), h->ring, h->B,
+               h->shape.off_nseg, h->wpos};
     const unsigned grid = unsigned(h->C) * unsigned(h->B / 16);
     if (wp == 2) hipLaunchKernelGGL(k_off_mac<2>, dim3(grid), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_off_mac<1>, dim3(grid), dim3(256), 0, s, a);
@@ -2010,7 +2010,7 @@ int launch_off_mac(upols_t* h, int wp, hipStream_t s)
 
 int lvl_setup_prime(upols_t* h)
 {
-    if (!h->ahead || h->grouped || h->lv_n >= 0) return NEO_HIP_OK;
+    if (!h->shape.ahead || h->grouped || h->lv_n >= 0) return NEO_HIP_OK;
     if (int rc = lvl_buffers(h)) return rc;
     if (int rc = lvl_prime(h, h->stream)) return rc;
     h->lv_n = 0;
@@ -2240,8 +2240,8 @@ const char* persist_ineligible(const upols_t* h)
 {
     if (h->v2) return "upola_convolver_v2 takes sub-block input";
     if (h->C > 16) return "more than 16 channels (the latency mode is for latency-bound shapes)";
-    if (!h->ahead)  // the plain step's workgroups, all resident (one per CU at B = 4096)
-        return h->C * h->S > 256 ? "the plain step's channels x splits above 256 workgroups" : nullptr;
+    if (!h->shape.ahead)  // the plain step's workgroups, all resident (one per CU at B = 4096)
+        return h->C * h->shape.S > 256 ? "the plain step's channels x splits above 256 workgroups" : nullptr;
     if (h->sched.lv.n && h->sched.lv.T[h->sched.lv.n - 1] == kBigT) return "the 128-block Toeplitz form of the far band (far_level 0)";
     if (h->sched.lv.nseg && h->sched.far_raw) return "the recomputed far level (far_level 2)";
     if (h->sched.lv.stag) return "staggered level windows (neo_hip_upols_opts.windows)";
@@ -2345,13 +2345,13 @@ static int persist_launch(upols_t* h, int64_t ld_in, int64_t ld_out)
         NEO_HIP_CHECK(hipMemsetAsync(h->ps_tl, 0, 10 * kPsRing * sizeof(unsigned long long), h->ps_stream));
     }
     persist_args pa{};
-    if (h->ahead) {
+    if (h->shape.ahead) {
         if (int rc = persist_levels(h, pa, ld_in, ld_out)) return rc;
     } else if (!h->ps_valid || h->lv_n < 0) {  // the plain step continues from the FDL ring: nothing to prime
         h->lv_n = 0;
         h->ps_valid = true;
     }
-    const int nsl = h->ahead ? pa.wgf1 : 0;
+    const int nsl = h->shape.ahead ? pa.wgf1 : 0;
     if (h->ps_nslices < nsl || !h->ps_flags) {
         dfree(h->ps_flags);
         h->ps_flags = nullptr;
@@ -2388,7 +2388,7 @@ static int persist_launch(upols_t* h, int64_t ld_in, int64_t ld_out)
     h->ps_mb->alive = 1;
     const unsigned grid = unsigned(h->C + nsl);
     bool launched = false;
-    if (!h->ahead) {
+    if (!h->shape.ahead) {
         if (int rc = plain_persist_launch(h, pa, ld_in, ld_out, &launched)) return rc;
     } else if (h->ola) {
         NEO_UPOLS_DISPATCH(h->B, if constexpr (BB <= 512) {
@@ -2500,7 +2500,7 @@ int persist_process(upols_t* h, const float* in, int64_t ld_in, float* out, int6
         __atomic_store_n(&r.out, reinterpret_cast<uint64_t>(out + k * B) | tag, __ATOMIC_RELEASE);
         h->fdl_zero = false;
         h->lv_n = n + 1;
-        h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;
+        advance(h, 1);
     }
     // complete on return (the block's deadline: spin, do not yield); the kernel's own waits give
     // up 2 s past its idle limit (dead_ticks), so a host wait 3 s past it means the kernel is not
@@ -2659,7 +2659,7 @@ extern "C" NEO_HIP_API int neo_hip_upols_get_far_form(neo_hip_upols* h, int* for
 extern "C" NEO_HIP_API int neo_hip_upols_get_windows(neo_hip_upols* h, int* windows)
 {
     if (!h || !windows) return neo_hip::fail(NEO_HIP_EINVAL, "null handle or output");
-    *windows = h->sched.lv.stag && h->ahead ? 2 : 1;
+    *windows = h->sched.lv.stag && h->shape.ahead ? 2 : 1;
     return NEO_HIP_OK;
 }
 

@@ -570,7 +570,7 @@ int matrix_batch(matrix_t* m, const float* in, int64_t ld_in, float* out, int64_
     if (int rc = launch_matrix_batch_mac(m->H, m->fdl, m->part_b, m->btab, m->B, m->P, m->ring, m->O, m->bplan.Sb, T,
                                          m->wpos, s))
         return rc;
-    if (int rc = launch_batch_finish_nosave(m->O, m->B, m->bplan.Sb, T, m->ola, m->part_b, out, ld_out, m->tail, m->ovl,
+    if (int rc = launch_batch_finish(m->O, m->B, m->bplan.Sb, T, m->ola, m->part_b, nullptr, 0, out, ld_out, nullptr, m->tail, m->ovl,
                                             m->tw, s))
         return rc;
     m->wpos = matrix_row(m, T);
@@ -614,7 +614,8 @@ int matrix_offline(matrix_t* m, const float* in, int64_t ld_in, float* out, int6
     if (int rc = launch_matrix_off_mac(m->off_xf, m->off_hf, m->off_y, m->off_tw, m->rtab, m->O, m->B, op.nseg, op.WP,
                                        lvf_spec_stride(op.nseg, m->B), s))
         return rc;
-    if (int rc = launch_batch_finish_nosave(m->O, m->B, 1, op.T, m->ola, m->off_y, out, ld_out, m->off_tail, m->ovl, m->tw, s))
+    if (int rc = launch_batch_finish(m->O, m->B, 1, op.T, m->ola, m->off_y, nullptr, 0, out, ld_out, nullptr, m->off_tail, m->ovl,
+                                     m->tw, s))
         return rc;
     m->wpos = matrix_row(m, op.T);
     return NEO_HIP_OK;
@@ -1049,7 +1050,7 @@ NEO_HIP_API int neo_hip_matrix_process(neo_hip_matrix* m, const float* in, int64
     if (nblocks < 0 || nblocks > (int64_t(1) << 40) / m->B) return fail(NEO_HIP_EINVAL, "bad block count");
     const int64_t n = nblocks * m->B;
     if (ld_in < n || ld_out < n) return fail(NEO_HIP_EINVAL, "leading dimension smaller than nblocks * block");
-    if (is_device && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15 || (ld_in | ld_out) & 3))
+    if (is_device && !io_aligned(in, out, ld_in, ld_out))
         return fail(NEO_HIP_EINVAL, "device I/O must be 16-byte aligned (ld multiple of 4)");
     if (!nblocks) return NEO_HIP_OK;
     device_guard g(m->device);

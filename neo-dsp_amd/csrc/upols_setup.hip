@@ -194,7 +194,7 @@ int pack_filter(upols_t* h, const cf* src, hipStream_t s)
 {
     const int64_t rows = int64_t(h->C) * h->P, total = rows * h->B;
     hipLaunchKernelGGL(k_pack_filter, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, src, h->H, h->B, rows,
-                       h->P, h->cstride, h->pstride);
+                       h->P, h->shape.cstride, h->shape.pstride);
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }
@@ -228,25 +228,18 @@ NEO_HIP_API int neo_hip_uniform_partition(const float* ir, int channels, int64_t
         if (int rc = null_join()) return rc;  // after its producer (common.hpp: null_join)
     if (int rs = shared_stream(&s)) return rs;  // one of the device's four (dmem.hip)
     cf* tw = nullptr;
-    const float* d_ir = ir;
+    const float* d_ir = nullptr;
     float* tmp_in = nullptr;
     cf* d_out = static_cast<cf*>(out);
     int rc = shared_tw(&tw, block);
-    if (!rc && !is_device) {  // pooled (dmem.hip): no hipMalloc / hipFree, which wait for the device
-        if (dalloc(&tmp_in, in_bytes) || dalloc(&d_out, out_bytes))
-            rc = fail(NEO_HIP_ENOMEM, "allocation failed");
-        else if (hipMemcpyAsync(tmp_in, ir, in_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "copy failed");
-        d_ir = tmp_in;
-    }
+    if (!rc) rc = stage_in(ir, in_bytes, is_device != 0, false, s, &tmp_in, &d_ir);  // pooled (dmem.hip): no hipMalloc / hipFree, which wait for the device
+    if (!rc && !is_device && dalloc(&d_out, out_bytes)) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
     if (!rc) rc = partition_device(d_ir, channels, length, block, false, d_out, tw, s);
     if (!rc && !is_device && hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(NEO_HIP_ERUNTIME, "copy back failed");
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    if (!is_device) {  // the stream was joined above
-        dfree(tmp_in);
-        dfree(d_out);
-    }
+    dfree(tmp_in);  // the stream was joined above
+    if (!is_device) dfree(d_out);
     return rc;
 }
 
@@ -261,18 +254,15 @@ NEO_HIP_API int neo_hip_normalize_impulse(float* ir, int channels, int64_t lengt
         if (int rc = null_join()) return rc;  // after its producer (common.hpp: null_join)
     if (int rs = shared_stream(&s)) return rs;  // one of the device's four (dmem.hip)
     const size_t bytes = size_t(channels) * size_t(length) * sizeof(float);
-    float* d = ir;
-    int rc = NEO_HIP_OK;
-    if (!is_device) {
-        if (dalloc(&d, bytes)) rc = fail(NEO_HIP_ENOMEM, "alloc failed");
-        else if (hipMemcpyAsync(d, ir, bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-            rc = fail(NEO_HIP_ERUNTIME, "copy failed");
-    }
+    float* tmp = nullptr;
+    const float* src = nullptr;
+    int rc = stage_in(ir, bytes, is_device != 0, false, s, &tmp, &src);
+    float* d = is_device ? ir : tmp;
     if (!rc) rc = normalize_device(d, channels, length, s);
     if (!rc && !is_device && hipMemcpyAsync(ir, d, bytes, hipMemcpyDeviceToHost, s) != hipSuccess)
         rc = fail(NEO_HIP_ERUNTIME, "copy back failed");
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
-    if (!is_device) dfree(d);  // the stream was joined above
+    dfree(tmp);  // the stream was joined above
     return rc;
 }
 

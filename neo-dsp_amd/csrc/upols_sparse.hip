@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256, sparse_wgs<B>()) void k_upols_sparse_step(
     __shared__ step_lds<B> L;
     const int c = blockIdx.x / S, s = blockIdx.x - c * S;
     const uint32_t* off_c = off + int64_t(c) * (P + 1);
-    // the channel's tiles and its FDL ring, each < 2 GiB (create_sparse)
+    // the channel's tiles and its FDL ring, each < 2 GiB (make_upols_shape)
     const sparse_rows sp{bits + int64_t(c) * P * upols_cfg<B>::VPT, off_c,
                          __builtin_amdgcn_make_buffer_rsrc(const_cast<float4*>(val + base[c] * 8), 0,
                                                            int(off_c[P]) * 128, 0x00020000),
@@ -238,9 +238,8 @@ int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStre
     h->sp_bins = tot[1];
     h->sp_wtiles = tot[2];
     const double bytes = double(h->sp_tiles) * kSparseTile * sizeof(cf);
-    // filter rows read cacheable (the Infinity Cache budget of the dense step, in kept bytes)
-    h->pc = bytes <= kCacheBudgetBytes ? h->P : int(double(h->P) * kCacheBudgetBytes / bytes);
-    h->pcb = bytes <= kBatchCacheBudgetBytes ? h->P : int(double(h->P) * kBatchCacheBudgetBytes / bytes);
+    h->shape.pc = sparse_cache_rows(h->P, bytes, kCacheBudgetBytes);
+    h->shape.pcb = sparse_cache_rows(h->P, bytes, kBatchCacheBudgetBytes);
     if (!h->sp_tiles) return NEO_HIP_OK;
     if (int rc = dalloc(&h->sp_val, size_t(h->sp_tiles) * kSparseTile * sizeof(cf))) return rc;
     hipLaunchKernelGGL(k_sparse_pack, dim3(unsigned(rows)), dim3(256), 0, s, filter, mask, h->B, h->P, h->sp_bits,
@@ -249,30 +248,22 @@ int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStre
     return NEO_HIP_OK;
 }
 
-int launch_sparse_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+int launch_sparse_mac(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
-    upols_t::ev_group* ev = nullptr;
-    if (int rc = timing_begin(h, 2, &ev)) return rc;
-    if (int rc = timing_mark(ev, 0, s)) return rc;
-    const unsigned grid = unsigned(h->C) * unsigned(h->S);
+    const unsigned grid = unsigned(h->C) * unsigned(h->shape.S);
 #define NEO_SPARSE_STEP(FU, OL)                                                                                       \
     NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_sparse_step<BB, FU, OL>), dim3(grid), dim3(256), 0, s, in, ld_in, \
                                                 out, ld_out, h->prev, h->sp_bits, h->sp_off, h->sp_base,                 \
                                                 reinterpret_cast<const float4*>(h->sp_val), h->fdl, h->part,            \
-                                                h->arrivals, h->tw, h->P, h->ring, h->S, h->rows, h->wpos, h->cstride,  \
-                                                h->pstride, h->pc))
-    if (h->fused) {
+                                                h->arrivals, h->tw, h->P, h->ring, h->shape.S, h->shape.rows, h->wpos,  \
+                                                h->shape.cstride, h->shape.pstride, h->shape.pc))
+    if (h->shape.fused) {
         if (h->ola) NEO_SPARSE_STEP(true, true) else NEO_SPARSE_STEP(true, false)
     } else {
         if (h->ola) NEO_SPARSE_STEP(false, true) else NEO_SPARSE_STEP(false, false)
     }
 #undef NEO_SPARSE_STEP
     NEO_HIP_LAUNCH_CHECK();
-    h->fdl_zero = false;
-    if (int rc = timing_mark(ev, 1, s)) return rc;
-    if (!h->fused)
-        if (int rc = launch_finish(h, out, ld_out, s)) return rc;
-    h->wpos = h->wpos + 1 >= h->ring ? 0 : h->wpos + 1;  // fdl_index.hpp:35-37
     return NEO_HIP_OK;
 }
 

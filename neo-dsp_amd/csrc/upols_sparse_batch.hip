@@ -170,7 +170,7 @@ __global__ __launch_bounds__(L, 2) void k_sparse_batch_mac(const uint32_t* __res
     const int p0 = s * rows, p1 = min(P, p0 + rows);
     const int NW = sparse_words(B);
     const uint32_t* off_c = off + int64_t(c) * (P + 1);
-    // the channel's tiles and its FDL ring, each < 2 GiB (create_sparse)
+    // the channel's tiles and its FDL ring, each < 2 GiB (make_upols_shape)
     const sb_src sp{bits + int64_t(c) * P * NW, win + int64_t(c) * P * NW, off_c,
                     __builtin_amdgcn_make_buffer_rsrc(const_cast<cf*>(val + base[c] * kSparseTile), 0,
                                                       int(off_c[P]) * 128, 0x00020000),
@@ -254,11 +254,11 @@ __global__ __launch_bounds__(L, 2) void k_sparse_batch_mac(const uint32_t* __res
 int launch_sparse_batch_mac(const upols_t* h, int T, hipStream_t s)
 {
     const int B = h->B, L = B < 64 ? 64 : B > 256 ? 256 : B;
-    const unsigned grid = unsigned(h->C) * unsigned(h->Sb) * unsigned(B > L ? B / L : 1);
+    const unsigned grid = unsigned(h->C) * unsigned(h->shape.Sb) * unsigned(B > L ? B / L : 1);
 #define NEO_SB_LAUNCH(LL, TT)                                                                                    \
     hipLaunchKernelGGL((k_sparse_batch_mac<LL, TT>), dim3(grid), dim3(LL), 0, s, h->sp_bits, h->sp_win, h->sp_off, \
-                       h->sp_base, h->sp_val, h->fdl, h->part_b, B, h->P, h->ring, h->Sb, h->rows_b, h->wpos,      \
-                       h->cstride, h->pstride, h->pcb)
+                       h->sp_base, h->sp_val, h->fdl, h->part_b, B, h->P, h->ring, h->shape.Sb, h->shape.rows_b, h->wpos,      \
+                       h->shape.cstride, h->shape.pstride, h->shape.pcb)
 #define NEO_SB_T(TT)                                \
     case TT:                                        \
         if (L == 64) NEO_SB_LAUNCH(64, TT);         \
