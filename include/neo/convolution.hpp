@@ -183,6 +183,16 @@ struct upols_deleter {
 using upols_ptr = std::unique_ptr<neo_hip_upols, upols_deleter>;
 }  // namespace detail
 
+/// The gain curve of a live filter update (matrix and dense convolvers): linear g = t, cosine
+/// g = 0.5 - 0.5 cos(pi t), t = n / (fade_blocks B) (neo_hip_matrix_fade_gains).
+enum class fade_curve : int { linear = 0, cosine = 1 };
+
+/// What fade_info() of a convolver with live filter updates reports.
+struct fade_desc {
+    int remaining_blocks, fade_blocks;
+    std::int64_t bank_bytes;  ///< the second filter bank, 0 until the first update
+};
+
 /// C independent uniformly-partitioned convolvers (UPOLS, or UPOLA with method::upola)
 /// on one GPU, stepped together.
 struct upols_multichannel {
@@ -283,7 +293,31 @@ struct upols_multichannel {
         auto const n = std::int64_t(num_samples);
         neo::hip::check(neo_hip_upols_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
     }
+    /// clears all state; a running fade (update_filter) completes: the new filter is the filter
     auto reset() -> void { neo::hip::check(neo_hip_upols_reset(_h.get())); }
+    /// live update (neo_hip_upols_update_filter): crossfade to `partitions` ([C][P][B+1], host memory)
+    /// over the next fade_blocks blocks and KEEP ALL STATE -- delay line, previous block, overlap
+    /// tail; filter() remains the resetting call. Complete on return. Dense upols / upola handles
+    /// outside the latency mode; throws otherwise, and while a fade still runs.
+    auto update_filter(std::complex<float> const* partitions, int fade_blocks = 1, fade_curve curve = fade_curve::linear)
+        -> void
+    {
+        neo::hip::check(neo_hip_upols_update_filter(_h.get(), partitions, 0, fade_blocks, int(curve), nullptr));
+    }
+    /// the same from ir [C][length] (host memory): normalize_impulse over its channels if `normalize`,
+    /// then uniform_partition on the device into the second bank; keeps all state
+    auto update_impulse(float const* ir, std::size_t length, bool normalize = true, int fade_blocks = 1,
+                        fade_curve curve = fade_curve::linear) -> void
+    {
+        neo::hip::check(neo_hip_upols_update_impulse(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, 0, fade_blocks,
+                                                     int(curve), nullptr));
+    }
+    [[nodiscard]] auto fade_info() const -> fade_desc
+    {
+        fade_desc d{};
+        neo::hip::check(neo_hip_upols_fade_info(_h.get(), &d.remaining_blocks, &d.fade_blocks, &d.bank_bytes));
+        return d;
+    }
     /// latency mode (neo_hip_upols_set_persistent): one resident kernel steps every block; every
     /// call completes on return (shapes up to 16 channels, 256 partitions, B <= 512; throws otherwise)
     auto latency_mode(bool on, double idle_ms = 50.0) -> void
@@ -350,6 +384,33 @@ struct upols_multidevice {
         neo::hip::check(neo_hip_upols_multi_process_samples(_h.get(), io, n, io, n, n));
     }
     auto reset() -> void { neo::hip::check(neo_hip_upols_multi_reset(_h.get())); }
+    /// upols_multichannel::update_filter on every shard, host memory, complete on return
+    auto update_filter(std::complex<float> const* partitions, int fade_blocks = 1, fade_curve curve = fade_curve::linear)
+        -> void
+    {
+        neo::hip::check(neo_hip_upols_multi_update_filter(_h.get(), partitions, fade_blocks, int(curve)));
+    }
+    /// the same from ir [C][length]; the normalisation factor is taken once over all channels
+    auto update_impulse(float const* ir, std::size_t length, bool normalize = true, int fade_blocks = 1,
+                        fade_curve curve = fade_curve::linear) -> void
+    {
+        neo::hip::check(neo_hip_upols_multi_update_impulse(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0,
+                                                           fade_blocks, int(curve)));
+    }
+    /// the shards' fades run in step: shard 0's counts, the shards' bank bytes summed
+    [[nodiscard]] auto fade_info() const -> fade_desc
+    {
+        fade_desc d{};
+        for (int i = 0, n = shards(); i < n; ++i) {
+            neo_hip_upols* h = nullptr;
+            neo::hip::check(neo_hip_upols_multi_shard(_h.get(), i, &h, nullptr, nullptr, nullptr));
+            fade_desc s{};
+            neo::hip::check(neo_hip_upols_fade_info(h, &s.remaining_blocks, &s.fade_blocks, &s.bank_bytes));
+            if (i == 0) d = s;
+            else d.bank_bytes += s.bank_bytes;
+        }
+        return d;
+    }
     [[nodiscard]] auto shards() const -> int
     {
         int n = 0;
@@ -559,10 +620,6 @@ struct matrix_route {
     int in;
 };
 
-/// The gain curve of a matrix convolver's live filter update: linear g = t, cosine
-/// g = 0.5 - 0.5 cos(pi t), t = n / (fade_blocks B) (neo_hip_matrix_fade_gains).
-enum class fade_curve : int { linear = 0, cosine = 1 };
-
 /// Matrix (multi-input, multi-output) convolver over libneo_hip's neo_hip_matrix_* (include/neo_hip.h):
 /// output o = the sum over its routes (o, i) of what upols_convolver (M = method::upols) or
 /// upola_convolver (M = method::upola) gives for (input i, that route's filter). The reference has
@@ -639,10 +696,7 @@ struct hip_matrix_convolver {
                                                       int(curve), nullptr));
     }
 
-    struct fade_desc {
-        int remaining_blocks, fade_blocks;
-        std::int64_t bank_bytes;  ///< the second filter bank, 0 until the first update after a filter
-    };
+    using fade_desc = ::neo::convolution::fade_desc;  ///< (bank_bytes: 0 until the first update after a filter)
     [[nodiscard]] auto fade_info() const -> fade_desc
     {
         fade_desc d{};

@@ -90,8 +90,11 @@ typedef struct neo_hip_upols neo_hip_upols;
  *        neo_hip_matrix_levels_info, neo_hip_matrix_level_plan).
  * 0.11.0: staggered level windows (neo_hip_upols_opts gains windows at its end: 11 ints;
  *        neo_hip_upols_stagger_plan).
- * 0.12.0: the step groups' background stream is readable (neo_hip_upols_get_background_stream). */
-#define NEO_HIP_VERSION 1200 /* 0.12.0 */
+ * 0.12.0: the step groups' background stream is readable (neo_hip_upols_get_background_stream).
+ * 0.13.0: crossfaded live filter updates on dense upols / upola handles (neo_hip_upols_update_filter,
+ *        neo_hip_upols_update_impulse, neo_hip_upols_fade_info, neo_hip_upols_multi_update_filter,
+ *        neo_hip_upols_multi_update_impulse). */
+#define NEO_HIP_VERSION 1300 /* 0.13.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -339,6 +342,48 @@ NEO_HIP_API int neo_hip_upols_get_offline(neo_hip_upols* h, int* enabled, int* s
 NEO_HIP_API int neo_hip_upols_process_samples(neo_hip_upols* h, const float* in, int64_t ld_in, float* out,
                                               int64_t ld_out, int64_t num_samples, int is_device, void* stream);
 NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h);
+/* Live filter update of a dense upols / upola handle: crossfade from the handle's filter A to `filter`
+ * (B, [C][P][B+1] complex like set_filter) over the next fade_blocks blocks, keeping ALL state (the
+ * delay line, the previous block, the overlap-add tail); set_filter / set_impulse remain the
+ * resetting calls. With y_A, y_B the outputs of two convolvers with filters A and B fed the whole
+ * input from the start, sample n = 0 .. fade_blocks * B - 1 of the next fade_blocks blocks is
+ * y_A + g[n] (y_B - y_A), g as neo_hip_matrix_fade_gains gives it (curve 0 linear, 1 raised cosine);
+ * every block after them is y_B. On a handle that runs plain steps (no streaming levels) those are
+ * bit for bit what a handle that had B from the start gives (overlap-add: from the second block after
+ * the fade on; the first takes a tail summed in the fade kernel's order); a streaming handle primes
+ * its levels after the fade at another phase than such a handle, so there the sums differ in order.
+ * The new filter is packed into a second bank of the handle's own layout, allocated at the first
+ * update (neo_hip_upols_fade_info reports it; beside it the fade's slabs [C][splits][2][B] and,
+ * overlap-add, a second set of tails [C][B]) and kept until the handle is destroyed: no later update
+ * allocates. While a fade has blocks left every whole block of every process call runs as one fade
+ * step (two launches: both banks against the same delay-line rows; two inverse transforms and the
+ * mix per channel) whatever the handle's modes say (streaming levels, step groups, paced pieces,
+ * batched passes, offline windows); a longer call is cut at the fade's last block and goes on in its
+ * usual passes, and the streaming levels prime again from the stepped delay line. A fade block
+ * costs about one and a half plain steps, not a streaming step. Equal calls
+ * give equal bits.
+ * STREAM CONTRACT: `stream` must be the stream the caller's process calls run on, or be ordered
+ * with it (after every earlier process call, before every later one): the update reads the delay
+ * line those calls write (overlap-add) and writes the bank the later ones read. Device pointer:
+ * asynchronous on `stream` (NULL = the HIP null stream). Host pointer: staged on `stream` (NULL = the
+ * handle's stream, as host process calls) after the handle's earlier steps on any stream; returns
+ * when the bank is written.
+ * EINVAL, the handle unchanged: a null argument; before a filter is set; fade_blocks < 1 or > 2^20;
+ * curve not 0 or 1; while a fade has blocks left; a sparse handle; an upola_convolver_v2 handle; a
+ * handle owned by a convolver group; a handle in latency mode (neo_hip_upols_set_persistent, which
+ * in turn refuses to switch on while a fade has blocks left). set_filter / set_impulse cancel a
+ * running fade; reset completes it (B is the filter) and clears the state; set_batch, set_offline,
+ * set_ahead and set_paced keep it. */
+NEO_HIP_API int neo_hip_upols_update_filter(neo_hip_upols* h, const void* filter, int is_device, int fade_blocks,
+                                            int curve, void* stream);
+/* The same from ir [C][length] float (host or device): normalize_impulse over the new impulse's
+ * channels if `normalize`, then uniform_partition on the device straight into the second bank, as
+ * set_impulse does. Also EINVAL: a length that gives another partition count than the handle's. */
+NEO_HIP_API int neo_hip_upols_update_impulse(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                             int is_device, int fade_blocks, int curve, void* stream);
+/* blocks left of the running fade (0: none), its length (0: none) and the bytes of the second filter
+ * bank (0 until the first update) */
+NEO_HIP_API int neo_hip_upols_fade_info(neo_hip_upols* h, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes);
 /* Streaming levels for single-block steps (upols / upola; upols_levels.hip): the
  * partitions are cut into bands -- p in [0, 8) MAC'd by the block itself; Toeplitz windows
  * of 4 / 8 / 16 / 32 blocks for [8, 16) / [16, 32) / [32, 64) / [64, 256); for [256, P) a
@@ -467,6 +512,13 @@ NEO_HIP_API int neo_hip_upols_multi_set_impulse(neo_hip_upols_multi* m, const fl
 NEO_HIP_API int neo_hip_upols_multi_process_samples(neo_hip_upols_multi* m, const float* in, int64_t ld_in, float* out,
                                                     int64_t ld_out, int64_t num_samples);
 NEO_HIP_API int neo_hip_upols_multi_reset(neo_hip_upols_multi* m);
+/* Live filter updates (neo_hip_upols_update_filter / _update_impulse) on every shard, host memory,
+ * each shard on its own stream; complete on return. For an impulse the normalisation factor is
+ * taken once over all C channels, as neo_hip_upols_multi_set_impulse takes it. A refusal by one
+ * shard is a refusal by all: every shard checks the same conditions. */
+NEO_HIP_API int neo_hip_upols_multi_update_filter(neo_hip_upols_multi* m, const void* filter, int fade_blocks, int curve);
+NEO_HIP_API int neo_hip_upols_multi_update_impulse(neo_hip_upols_multi* m, const float* ir, int64_t length, int normalize,
+                                                   int fade_blocks, int curve);
 /* -- Groups of single-channel convolvers (upols_group.hip) ---------------------------------
  * Members are C independent one-channel upols / upola convolvers of one shape, each with its
  * own filter and state, as the plugin's std::vector<upols_convolver> (DenseConvolution.hpp:35)

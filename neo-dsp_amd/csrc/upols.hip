@@ -30,9 +30,17 @@
 // frame for dense and sparse handles), the upola_convolver_v2 piece kernel, the one create function
 // (every kind of handle from its plan: upols_plan.hpp, all checks and shape rules, host only), the
 // filter calls (set_begin, a body, set_end) and the rest of the neo_hip_upols_* C-ABI.
+// Live filter updates (neo_hip_upols_update_filter / _update_impulse, include/neo_hip.h): the new
+// filter goes into a second bank H2 of the handle's own layout and the next fade_blocks blocks are
+// crossfaded in the time domain, no state reset. While a fade has blocks left launch_step and
+// process_samples run every whole block as one fade step (fade_step: upols_fade.hip's two-bank MAC,
+// then the matrix convolver's fade finish with one "output" per channel), whatever the handle's
+// modes; at its end the banks swap by pointer (fade_swap). H_alloc remembers the allocation that
+// holds the FDL, whichever bank is current.
 // upols_batch.hip: T blocks per pass (process_blocks). upols_sparse.hip: the sparse handle's
 // buffers, filter and MAC. upols_setup.hip: partitioning and normalization. upols_device.hpp /
 // upols_handle.hpp: what they share.
+#include "matrix_fade.hpp"
 #include "upols_device.hpp"
 #include "upols_handle.hpp"
 #include "perceptual_plan.hpp"
@@ -349,7 +357,10 @@ void destroy(upols_t* h)
     lvl_free(h);  // joins the background stream first
     // device buffers back to the pool (dmem.hip): no device-wide synchronization; the caller
     // joined every stream that used them
-    dfree(h->H);  // the FDL shares H's allocation (rows [nrows, 2 nrows))
+    dfree(h->H_alloc);  // the FDL shares H's allocation (rows [nrows, 2 nrows))
+    dfree(h->H == h->H_alloc ? h->H2 : h->H);  // a live update's bank: the one that is not in that allocation
+    dfree(h->part_f);
+    dfree(h->ovl2);
     if (h->sparse) {  // no dense filter: the FDL is an allocation of its own
         dfree(h->fdl);
         sparse_free(h);
@@ -370,9 +381,38 @@ void destroy(upols_t* h)
     delete h;  // h->stream is shared (a group's, or one of the device's four: dmem.hip)
 }
 
+// the end of a fade: bank B is the filter (pointers swap, no copy; overlap-add: its tails are the
+// tails), and what is computed from the filter follows it (far segment spectra, offline spectra)
+void fade_swap(upols_t* h)
+{
+    std::swap(h->H, h->H2);
+    if (h->ola) std::swap(h->prev, h->ovl2);
+    h->fade_left = h->fade_total = 0;
+    lvl_filter_changed(h);
+}
+
+// One block of a running fade, whatever the handle's modes: an excursion from the streaming levels
+// like the plain step's (launch_step_normal: background slices joined, the levels prime again at
+// the next streaming step), both banks against the same FDL rows, the mix in the finish.
+int fade_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
+{
+    if (int rc = lvl_join(h, s)) return rc;
+    if (int rc = launch_upols_fade_mac(h, h->H, h->H2, in, ld_in, h->fade_S, h->fade_rows, h->wpos, false, s)) return rc;
+    h->fdl_zero = false;
+    const int64_t n0 = int64_t(h->fade_total - h->fade_left) * h->B;
+    if (int rc = launch_matrix_fade_finish(h->part_f, out, ld_out, h->prev, h->ovl2, h->tw, h->B, h->C, h->fade_S, h->ola,
+                                           false, n0, int64_t(h->fade_total) * h->B, h->fade_curve, s))
+        return rc;
+    advance(h, 1);
+    h->lv_n = -1;
+    if (--h->fade_left == 0) fade_swap(h);
+    return NEO_HIP_OK;
+}
+
 int launch_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
     if (int rc = note_stream(h, s)) return rc;
+    if (h->fade_left > 0) return fade_step(h, in, ld_in, out, ld_out, s);  // (never with the latency mode on)
     if (h->sched.persist) return persist_process(h, in, ld_in, out, ld_out, 1);  // synchronous: s is not used
     return launch_step_normal(h, in, ld_in, out, ld_out, s);
 }
@@ -494,6 +534,11 @@ int process_samples(upols_t* h, const float* in, int64_t ld_in, float* out, int6
         const float* ip = in + done;
         float* op = out + done;
         int rc;
+        if (h->fade_left > 0) {  // a running fade: single fade steps to its last block, then the usual passes
+            if ((rc = launch_step(h, ip, ld_in, op, ld_out, s))) return rc;
+            done += B;
+            continue;
+        }
         // offline windows: 256 or 128 whole blocks left, every block known (batching on)
         const int64_t left = (n - done) / B;
         if (h->shape.off && h->shape.batch && !stream_all && h->in_pos == 0 && a16 && done % 4 == 0 && left >= kFarT) {
@@ -583,6 +628,7 @@ int create_convolver(int channels, int block, int partitions, int device, upols_
         (sparse && sparse_alloc(h)))
         return bail(fail(NEO_HIP_ENOMEM, "device allocation of %zu bytes failed", ringbytes));
     if (!sparse) h->fdl = h->H + nrows * size_t(block);
+    h->H_alloc = h->H;
     if (int rc = shared_tw(&h->tw, block)) return bail(rc);
     // stream-ordered zeroing, one wait at the end (the caller's later work may run on any stream)
     if (!sparse && hipMemsetAsync(h->H, 0, nrows * rowbytes, h->stream) != hipSuccess)
@@ -624,6 +670,8 @@ int set_begin(upols_t* h, bool device_input)
 int set_end(upols_t* h, int rc, std::initializer_list<void*> scratch)
 {
     lvl_filter_changed(h);
+    h->fade_left = h->fade_total = 0;  // a running fade is cancelled: the filter just loaded (bank A) is the filter
+    if (!rc) h->has_filter = true;
     if (!rc) rc = reset_state(h, h->stream);
     if (!rc) rc = lvl_setup_prime(h);
     if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
@@ -639,16 +687,31 @@ int check_impulse(const upols_t* h, int64_t length)
     return NEO_HIP_OK;
 }
 
-// impulse [C][length], host or device -> a copy of it (*tmp), normalized on request, partitioned:
-// packed into the handle's filter rows (out null) or as [C][P][B + 1] into out
-int load_impulse(upols_t* h, const float* ir, int64_t length, int normalize, int is_device, cf* out, float** tmp)
+// impulse [C][length], host or device -> a copy of it (*tmp), normalized on request, partitioned on s:
+// packed into `bank` (a filter bank of the handle's layout; out null) or as [C][P][B + 1] into out.
+// The copy is pooled scratch (stage_in: the caller gives it back once s is joined) or, stream_scratch,
+// stream-ordered scratch (the caller frees it on s: no host-side wait anywhere)
+int load_impulse(upols_t* h, const float* ir, int64_t length, int normalize, int is_device, cf* out, float** tmp, cf* bank,
+                 hipStream_t s, bool stream_scratch = false)
 {
     const float* d = nullptr;
-    int rc = stage_in(ir, size_t(h->C) * size_t(length) * sizeof(float), is_device != 0, true, h->stream, tmp, &d);
-    if (!rc && normalize) rc = normalize_device(*tmp, h->C, length, h->stream);
+    const size_t bytes = size_t(h->C) * size_t(length) * sizeof(float);
+    int rc = NEO_HIP_OK;
+    if (stream_scratch) {
+        if (hipMallocAsync(reinterpret_cast<void**>(tmp), bytes, s) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(NEO_HIP_ENOMEM, "allocation of %zu bytes failed", bytes);
+        }
+        if (hipMemcpyAsync(*tmp, ir, bytes, is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s) != hipSuccess)
+            rc = fail(NEO_HIP_ERUNTIME, "copy to the device failed");
+        d = *tmp;
+    } else {
+        rc = stage_in(ir, bytes, is_device != 0, true, s, tmp, &d);
+    }
+    if (!rc && normalize) rc = normalize_device(*tmp, h->C, length, s);
     if (!rc)
-        rc = out ? partition_device(d, h->C, length, h->B, false, out, h->tw, h->stream)
-                 : partition_device(d, h->C, length, h->B, true, h->H, h->tw, h->stream, h->shape.cstride, h->shape.pstride);
+        rc = out ? partition_device(d, h->C, length, h->B, false, out, h->tw, s)
+                 : partition_device(d, h->C, length, h->B, true, bank, h->tw, s, h->shape.cstride, h->shape.pstride);
     return rc;
 }
 
@@ -678,6 +741,96 @@ std::vector<float> weights_for(const upols_t* h, const neo_hip_perceptual* pp)
     std::vector<float> w(size_t(h->B) + 1);
     perceptual_weights(h->B, pp, w.data());
     return w;
+}
+
+// -- live filter updates: update_* = check, the fade's buffers, the load into the spare bank on the
+// call's stream, update_end (overlap-add's priming pass, the fade armed) -------------------------
+
+// what every update checks before it touches anything
+int update_check(const upols_t* h, int fade_blocks, int curve)
+{
+    if (h->sparse) return fail(NEO_HIP_EINVAL, "filter update: a sparse handle keeps no dense filter bank");
+    if (h->v2) return fail(NEO_HIP_EINVAL, "filter update: upola_convolver_v2 handles (sub-block input) are not faded");
+    if (h->grouped) return fail(NEO_HIP_EINVAL, "filter update: the handle belongs to a convolver group");
+    if (h->sched.persist) return fail(NEO_HIP_EINVAL, "filter update: the handle is in latency mode (set_persistent)");
+    if (!h->has_filter) return fail(NEO_HIP_EINVAL, "filter update: no filter set (neo_hip_upols_set_filter)");
+    if (fade_blocks < 1 || fade_blocks > kMatrixFadeMaxBlocks)
+        return fail(NEO_HIP_EINVAL, "filter update: fade_blocks must be in [1, %d]", kMatrixFadeMaxBlocks);
+    if (curve < 0 || curve >= kMatrixFadeCurves)
+        return fail(NEO_HIP_EINVAL, "filter update: curve must be 0 (linear) or 1 (raised cosine)");
+    if (h->fade_left > 0) return fail(NEO_HIP_EINVAL, "filter update: a fade is still running (%d blocks left)", h->fade_left);
+    return NEO_HIP_OK;
+}
+
+// device memory: the caller's stream; host memory: the handle's own unless one is given
+hipStream_t update_stream(const upols_t* h, int is_device, void* stream)
+{
+    return is_device || stream ? as_stream(stream) : h->stream;
+}
+
+// the call's stream noted; a host filter's call is synchronous, so it also comes after the
+// handle's earlier steps on every stream (the last fade step may still read the spare bank)
+int update_begin(upols_t* h, bool is_device, hipStream_t s)
+{
+    if (!is_device)
+        if (int rc = h->used.join()) return rc;
+    return note_stream(h, s);
+}
+
+// the spare bank (zero, on s: rows >= P of a channel stay zero as in the first bank), the fade
+// step's slabs and bank B's overlap-add tails, at the first update; kept until the handle goes
+int fade_buffers(upols_t* h, hipStream_t s)
+{
+    if (h->H2) return NEO_HIP_OK;
+    const upols_fade_plan f = upols_fade_split(h->shape);
+    cf *bank = nullptr, *slabs = nullptr;
+    float* tails = nullptr;
+    if (dalloc(&bank, size_t(f.bank_bytes)) || dalloc(&slabs, size_t(f.slab_bytes)) ||
+        (h->ola && dalloc(&tails, size_t(h->C) * h->B * sizeof(float)))) {
+        dfree(bank);
+        dfree(slabs);
+        dfree(tails);
+        return fail(NEO_HIP_ENOMEM, "filter update: allocation of the second bank (%lld bytes) failed", (long long)f.bank_bytes);
+    }
+    if (hipMemsetAsync(bank, 0, size_t(f.bank_bytes), s) != hipSuccess) {
+        dfree(bank);
+        dfree(slabs);
+        dfree(tails);
+        return fail(NEO_HIP_ERUNTIME, "memset failed");
+    }
+    h->H2 = bank;
+    h->part_f = slabs;
+    h->ovl2 = tails;
+    h->fade_S = f.S;
+    h->fade_rows = f.rows;
+    return NEO_HIP_OK;
+}
+
+// An update call after its load (rc) on s. Overlap-add: a fade that starts at block k needs bank
+// B's tail of block k - 1; the rows (w - 1 - p) mod ring, p < P, are all intact (a step writes row
+// w alone), so one pass of the spare bank at write position w - 1 (no window, no insert) and the
+// finish's prime form leave it in ovl2. Nothing stepped since a reset: the tail is zero. Then the
+// fade is armed. Host memory: complete on return.
+int update_end(upols_t* h, int rc, bool is_device, int fade_blocks, int curve, hipStream_t s)
+{
+    if (!rc && h->ola) {
+        if (h->fdl_zero) {
+            if (hipMemsetAsync(h->ovl2, 0, size_t(h->C) * h->B * sizeof(float), s) != hipSuccess)
+                rc = fail(NEO_HIP_ERUNTIME, "memset failed");
+        } else {
+            const int w1 = (h->wpos + h->ring - 1) % h->ring;
+            rc = launch_upols_fade_mac(h, h->H2, h->H2, nullptr, 0, h->fade_S, h->fade_rows, w1, true, s);
+            if (!rc)
+                rc = launch_matrix_fade_finish(h->part_f, nullptr, 0, h->prev, h->ovl2, h->tw, h->B, h->C, h->fade_S, true, true,
+                                               0, 1, 0, s);
+        }
+    }
+    if (!is_device && hipStreamSynchronize(s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
+    if (!rc) {
+        h->fade_left = h->fade_total = fade_blocks;
+        h->fade_curve = curve;
+    }
+    return rc;
 }
 
 }  // namespace
@@ -744,7 +897,7 @@ NEO_HIP_API int neo_hip_upols_set_impulse_perceptual(neo_hip_upols* h, const flo
     uint8_t* mask = nullptr;
     float* tmp = nullptr;
     int rc = dalloc(&parts, filter_elems(h) * sizeof(cf)) ? fail(NEO_HIP_ENOMEM, "allocation failed") : NEO_HIP_OK;
-    if (!rc) rc = load_impulse(h, ir, length, normalize, is_device, parts, &d);
+    if (!rc) rc = load_impulse(h, ir, length, normalize, is_device, parts, &d, nullptr, h->stream);
     if (!rc) rc = store_perceptual(h, parts, pp, w, &mask, &tmp);
     return set_end(h, rc, {tmp, d, parts, mask});
 }
@@ -837,6 +990,7 @@ NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h)
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     device_guard g(h->device);
     if (int rc = set_begin(h, false)) return rc;  // after this handle's steps on any stream
+    if (h->fade_left > 0) fade_swap(h);  // a running fade completes: the new filter is the filter
     int rc = reset_state(h, h->stream);
     if (!rc) rc = lvl_setup_prime(h);  // the next call is an ordinary streaming step
     if (rc) return rc;
@@ -871,8 +1025,57 @@ NEO_HIP_API int neo_hip_upols_set_impulse(neo_hip_upols* h, const float* ir, int
     if (g.rc) return g.rc;
     if (int rc = set_begin(h, is_device != 0)) return rc;
     float* d = nullptr;
-    const int rc = load_impulse(h, ir, length, normalize, is_device, nullptr, &d);
+    const int rc = load_impulse(h, ir, length, normalize, is_device, nullptr, &d, h->H, h->stream);
     return set_end(h, rc, {d});
+}
+
+NEO_HIP_API int neo_hip_upols_update_filter(neo_hip_upols* h, const void* filter, int is_device, int fade_blocks,
+                                            int curve, void* stream)
+{
+    if (!h || !filter) return fail(NEO_HIP_EINVAL, "null handle or filter");
+    if (int rc = update_check(h, fade_blocks, curve)) return rc;
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = update_stream(h, is_device, stream);
+    if (int rc = update_begin(h, is_device != 0, s)) return rc;
+    if (int rc = fade_buffers(h, s)) return rc;
+    cf* tmp = nullptr;
+    const cf* src = nullptr;
+    int rc = stage_in(static_cast<const cf*>(filter), filter_elems(h) * sizeof(cf), is_device != 0, false, s, &tmp, &src);
+    if (!rc) rc = pack_filter(h, src, s, h->H2);
+    rc = update_end(h, rc, is_device != 0, fade_blocks, curve, s);
+    dfree(tmp);  // a host filter's staging: s was joined above
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_upols_update_impulse(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                             int is_device, int fade_blocks, int curve, void* stream)
+{
+    if (!h || !ir || length < 1) return fail(NEO_HIP_EINVAL, "null handle/ir or empty impulse");
+    if (int rc = update_check(h, fade_blocks, curve)) return rc;
+    if (int rc = check_impulse(h, length)) return rc;
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = update_stream(h, is_device, stream);
+    if (int rc = update_begin(h, is_device != 0, s)) return rc;
+    if (int rc = fade_buffers(h, s)) return rc;
+    // the impulse's working copy: a device impulse leaves the call asynchronous, so its copy is
+    // stream-ordered scratch; a host one is staged in pooled scratch and the call waits for s
+    float* d = nullptr;
+    int rc = load_impulse(h, ir, length, normalize, is_device, nullptr, &d, h->H2, s, is_device != 0);
+    if (is_device && d && hipFreeAsync(d, s) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "impulse scratch free failed");
+    rc = update_end(h, rc, is_device != 0, fade_blocks, curve, s);
+    if (!is_device) dfree(d);
+    return rc;
+}
+
+NEO_HIP_API int neo_hip_upols_fade_info(neo_hip_upols* h, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes)
+{
+    if (!h) return fail(NEO_HIP_EINVAL, "null handle");
+    if (remaining_blocks) *remaining_blocks = h->fade_left;
+    if (fade_blocks) *fade_blocks = h->fade_total;
+    if (bank_bytes) *bank_bytes = h->H2 ? upols_fade_split(h->shape).bank_bytes : 0;
+    return NEO_HIP_OK;
 }
 
 NEO_HIP_API int neo_hip_upols_process_device(neo_hip_upols* h, const float* in, int64_t ld_in, float* out,
@@ -1040,6 +1243,8 @@ NEO_HIP_API int neo_hip_upols_set_persistent(neo_hip_upols* h, int enable, doubl
     if (enable) {
         if (h->sparse) return fail(NEO_HIP_EINVAL, "latency mode: a sparse handle has no persistent step");
         if (const char* why = persist_ineligible(h)) return fail(NEO_HIP_EINVAL, "latency mode: %s", why);
+        if (h->fade_left > 0)
+            return fail(NEO_HIP_EINVAL, "latency mode: a filter fade is still running (%d blocks left)", h->fade_left);
         if (!(idle_ms > 0.0 && idle_ms <= 10000.0)) return fail(NEO_HIP_EINVAL, "idle_ms must be in (0, 10000]");
         if (int rc = setup_join(h)) return rc;  // this handle's steps queued on any stream come first
         h->ps_idle_ms = idle_ms;

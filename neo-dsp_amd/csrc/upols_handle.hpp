@@ -184,6 +184,14 @@ struct neo_hip_upols {
     bool off_dirty = true;           // off_hf to recompute (filter changed)
     neo_hip::cf* off_y = nullptr;    // a pass's output spectra [C][128 kOffMaxWP][B]
     float* off_tail = nullptr;       // OLA: a pass's tails [C][128 kOffMaxWP][B]
+    // live filter updates (neo_hip_upols_update_filter; upols_fade.hip): from the first update on
+    neo_hip::cf* H_alloc = nullptr;  // the allocation H and the FDL were made in (H may be the other bank by now)
+    neo_hip::cf* H2 = nullptr;       // the spare bank [C][ring][B], the handle's own strides: bank B while a fade runs
+    neo_hip::cf* part_f = nullptr;   // [C][fade_S][2][B] the fade step's slabs
+    float* ovl2 = nullptr;           // overlap-add: bank B's tails [C][B]
+    int fade_S = 1, fade_rows = 1;   // the fade step's splits (upols_fade_split)
+    int fade_left = 0, fade_total = 0, fade_curve = 0;  // blocks left of the running fade (0: none)
+    bool has_filter = false;         // a filter call succeeded (an update needs a filter to fade from)
     float* samples_dev = nullptr;   // process_samples host staging (device side)
     float* samples_host = nullptr;  // process_samples host staging (pinned)
     size_t samples_cap = 0;
@@ -349,6 +357,13 @@ int launch_matrix_fade_mac(const cf* HA, const cf* HB, const cf* fdl, cf* part, 
                            int O, int S, int w, hipStream_t s);
 int launch_matrix_fade_finish(const cf* part, float* out, int64_t ld_out, float* ovl_a, float* ovl_b, const cf* tw, int B,
                               int O, int S, bool ola, bool prime, int64_t n0, int64_t total, int curve, hipStream_t s);
+// upols_fade.hip: the MAC of a dense handle's fade step: banks HA, HB (the handle's layout) against
+// the FDL at write position w into the slabs h->part_f [C][S][2][B]; split 0 runs the window r2c of
+// `in`, inserts row w and (overlap-save) saves the previous block, as the plain step does. prime
+// (overlap-add, at the update call): no window and no insert, p = 0 from ring row w. The finish is
+// launch_matrix_fade_finish with O = C.
+int launch_upols_fade_mac(const upols_t* h, const cf* HA, const cf* HB, const float* in, int64_t ld_in, int S, int rows, int w,
+                          bool prime, hipStream_t s);
 // upols_matrix_levels.hip: window levels of a matrix handle. mac: the workgroups [wg0, wg1) of a
 // level's grid O x S x chunks (a part; none: no launch) for the window of T blocks whose block 0 is
 // ring row w, over the level's run table tab (matrix_level_table, matrix_plan.hpp), into that
@@ -433,7 +448,8 @@ int upload_tw(cf** d, int B);
 int partition_device(const float* d_ir, int C, int64_t L, int B, bool packed, cf* out, const cf* tw, hipStream_t s,
                      int64_t cstride = 0, int64_t pstride = 0);
 int normalize_device(float* d_ir, int C, int64_t L, hipStream_t s);
-// filter [C][P][B+1] (reference layout, device) -> packed H rows of the handle
-int pack_filter(upols_t* h, const cf* src, hipStream_t s);
+// filter [C][P][B+1] (reference layout, device) -> packed H rows of the handle (bank: another bank
+// of the handle's layout instead, a live update's)
+int pack_filter(upols_t* h, const cf* src, hipStream_t s, cf* bank = nullptr);
 
 }  // namespace neo_hip

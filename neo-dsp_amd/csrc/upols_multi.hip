@@ -139,6 +139,35 @@ NEO_HIP_API int neo_hip_upols_multi_set_impulse(neo_hip_upols_multi* m, const fl
     });
 }
 
+NEO_HIP_API int neo_hip_upols_multi_update_filter(neo_hip_upols_multi* m, const void* filter, int fade_blocks, int curve)
+{
+    if (!m || !filter) return fail(NEO_HIP_EINVAL, "null argument");
+    const size_t per_channel = size_t(m->P) * size_t(m->B + 1) * 2 * sizeof(float);
+    const char* base = static_cast<const char*>(filter);
+    return fan_out(m, [&](int i) {
+        return neo_hip_upols_update_filter(m->shard[size_t(i)], base + size_t(m->c0[size_t(i)]) * per_channel, 0,
+                                           fade_blocks, curve, nullptr);
+    });
+}
+
+NEO_HIP_API int neo_hip_upols_multi_update_impulse(neo_hip_upols_multi* m, const float* ir, int64_t length, int normalize,
+                                                   int fade_blocks, int curve)
+{
+    if (!m || !ir) return fail(NEO_HIP_EINVAL, "null argument");
+    if (length < 1) return fail(NEO_HIP_EINVAL, "length must be >= 1");
+    const float* src = ir;
+    std::vector<float> tmp;
+    if (normalize) {  // one factor over all channels, as neo_hip_upols_multi_set_impulse takes it
+        tmp.assign(ir, ir + size_t(m->C) * size_t(length));
+        if (int rc = neo_hip_normalize_impulse(tmp.data(), m->C, length, 0, m->dev[0])) return rc;
+        src = tmp.data();
+    }
+    return fan_out(m, [&](int i) {
+        return neo_hip_upols_update_impulse(m->shard[size_t(i)], src + size_t(m->c0[size_t(i)]) * size_t(length), length,
+                                            0, 0, fade_blocks, curve, nullptr);
+    });
+}
+
 NEO_HIP_API int neo_hip_upols_multi_process_samples(neo_hip_upols_multi* m, const float* in, int64_t ld_in, float* out,
                                                     int64_t ld_out, int64_t num_samples)
 {

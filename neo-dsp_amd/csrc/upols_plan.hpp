@@ -183,6 +183,26 @@ inline const char* make_upols_shape(int channels, int block, int partitions, con
     return nullptr;
 }
 
+// The fade step of a live filter update (upols_fade.hip: both banks against the same FDL rows, always
+// MAC + finish, never the last-arriver form): it cuts the partitions where the plain step does, S
+// splits of `rows` partitions (the last one shorter), so a fade block runs the plain step's grid
+// C x S (~1024 workgroups of 4 waves, 4 per CU) over 24 bytes per bin and partition instead of 16.
+// slab_bytes: its slabs [C][S][2][B]; bank_bytes: the second filter bank, the handle's own layout
+// [C][ring][B] (cstride, pstride), so every kernel takes it by pointer.
+struct upols_fade_plan {
+    int S = 1, rows = 1;
+    int64_t slab_bytes = 0, bank_bytes = 0;
+};
+inline upols_fade_plan upols_fade_split(const upols_shape& sh)
+{
+    upols_fade_plan f;
+    f.S = sh.S;
+    f.rows = sh.rows;
+    f.slab_bytes = int64_t(sh.sched.C) * f.S * 2 * sh.sched.B * int64_t(sizeof(cf));
+    f.bank_bytes = int64_t(sh.sched.C) * sh.cstride * int64_t(sizeof(cf));
+    return f;
+}
+
 // A sparse handle's cacheable rows: all P while the kept bytes of its filter fit the budget (the
 // Infinity Cache budget of the dense step, in kept bytes), else the budget's share of them
 inline int sparse_cache_rows(int P, double kept_bytes, double budget)

@@ -190,10 +190,10 @@ int normalize_device(float* d_ir, int C, int64_t L, hipStream_t s)
     return NEO_HIP_OK;
 }
 
-int pack_filter(upols_t* h, const cf* src, hipStream_t s)
+int pack_filter(upols_t* h, const cf* src, hipStream_t s, cf* bank)
 {
     const int64_t rows = int64_t(h->C) * h->P, total = rows * h->B;
-    hipLaunchKernelGGL(k_pack_filter, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, src, h->H, h->B, rows,
+    hipLaunchKernelGGL(k_pack_filter, dim3(unsigned((total + 255) / 256)), dim3(256), 0, s, src, bank ? bank : h->H, h->B, rows,
                        h->P, h->shape.cstride, h->shape.pstride);
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;

@@ -16,7 +16,7 @@ from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_c
                           sparse_upols_convolver, PerceptualSparsity, a_weighting, amplitude_to_db, perceptual_histogram,
                           perceptual_histogram_host, perceptual_mask, perceptual_mask_host, perceptual_weights,
                           threshold_for_tile_density, tile_density_curve,
-                          MatrixConvolver, matrix_batch_plan, matrix_convolve, matrix_fade_gains, matrix_level_plan,
+                          MatrixConvolver, fade_gains, matrix_batch_plan, matrix_convolve, matrix_fade_gains, matrix_level_plan,
                           matrix_offline_plan, matrix_plan)
 
 __version__ = "0.1.0"
@@ -56,6 +56,7 @@ __all__ = [
     "matrix_level_plan",
     "matrix_convolve",
     "matrix_fade_gains",
+    "fade_gains",
     "a_weighting",
     "amplitude_to_db",
     "PerceptualSparsity",

@@ -130,6 +130,9 @@ SIGNATURES = {
     "neo_hip_upols_process_device": (_i, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "neo_hip_upols_process_blocks": (_i, [_vp, _vp, _vp, _i64, _i64, _vp]),
     "neo_hip_upols_reset": (_i, [_vp]),
+    "neo_hip_upols_update_filter": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "neo_hip_upols_update_impulse": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "neo_hip_upols_fade_info": (_i, [_vp, _vp, _vp, _vp]),
     "neo_hip_upols_set_ahead": (_i, [_vp, _i]),
     "neo_hip_upols_set_offline": (_i, [_vp, _i]),
     "neo_hip_upols_get_offline": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
@@ -163,6 +166,8 @@ SIGNATURES = {
     "neo_hip_upols_multi_set_impulse": (_i, [_vp, _vp, _i64, _i]),
     "neo_hip_upols_multi_process_samples": (_i, [_vp, _vp, _i64, _vp, _i64, _i64]),
     "neo_hip_upols_multi_reset": (_i, [_vp]),
+    "neo_hip_upols_multi_update_filter": (_i, [_vp, _vp, _i, _i]),
+    "neo_hip_upols_multi_update_impulse": (_i, [_vp, _vp, _i64, _i, _i, _i]),
     "neo_hip_matrix_create": (_i, [_i, _i, _i, _i, _i, _i, _vp, ctypes.POINTER(_vp)]),
     "neo_hip_matrix_destroy": (_i, [_vp]),
     "neo_hip_matrix_set_filter": (_i, [_vp, _vp, _vp, _vp, _i, _i]),
@@ -213,7 +218,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1200 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1300 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -60,6 +60,7 @@ __all__ = [
     "matrix_level_plan",
     "matrix_convolve",
     "matrix_fade_gains",
+    "fade_gains",
     "a_weighting",
     "amplitude_to_db",
     "PerceptualSparsity",
@@ -317,7 +318,72 @@ class UpolsConvolver:
         _native.check(_native.load().neo_hip_upols_set_impulse(self._h, _ptr(ir), ir.shape[1], int(normalize), 0))
 
     def reset(self) -> None:
+        """Clears all state; a running fade (update_filter) completes: the new filter is the filter."""
         _native.check(_native.load().neo_hip_upols_reset(self._h))
+
+    # -- live updates -------------------------------------------------------
+    def update_filter(self, partitions, fade_blocks: int = 1, curve: str = "linear", stream: int = 0) -> None:
+        """Live update (neo_hip_upols_update_filter): crossfade to `partitions` [C][P][B+1] complex64
+        over the next fade_blocks blocks and KEEP ALL STATE (delay line, previous block, overlap-add
+        tail); filter() remains the resetting call. Sample n of the fade is y_A + g[n] (y_B - y_A)
+        with g = fade_gains(block_size, fade_blocks, curve), curve "linear" or "cosine"; every
+        block of the fade runs as one two-bank step (about a plain step and a half), whatever the
+        handle's modes. A CUDA tensor: asynchronous on torch's current stream (or `stream`), which
+        must be the stream the process calls run on; an ndarray: complete on return. Dense upols /
+        upola convolvers only (not sparse, upola_v2, group members or latency mode)."""
+        c = _fade_curve(curve)
+        lib = _native.load()
+        if _is_torch(partitions) and partitions.is_cuda:
+            import torch
+
+            if (partitions.dtype != torch.complex64 or not partitions.is_contiguous() or
+                    partitions.numel() != self.channels * self.partitions * (self.block_size + 1)):
+                raise ValueError(f"filter must be a contiguous complex64 tensor of "
+                                 f"{(self.channels, self.partitions, self.block_size + 1)}")
+            _producer_join(partitions)
+            current = torch.cuda.current_stream(partitions.device).cuda_stream
+            _native.check(lib.neo_hip_upols_update_filter(self._h, ctypes.c_void_p(partitions.data_ptr()), 1,
+                                                          int(fade_blocks), c, ctypes.c_void_p(stream or current or None)))
+            return
+        H = np.ascontiguousarray(partitions, dtype=np.complex64)
+        if H.ndim == 2:
+            H = H[None]
+        if H.shape != (self.channels, self.partitions, self.block_size + 1):
+            raise ValueError(f"filter shape {H.shape} != {(self.channels, self.partitions, self.block_size + 1)}")
+        _native.check(lib.neo_hip_upols_update_filter(self._h, _ptr(H), 0, int(fade_blocks), c,
+                                                      ctypes.c_void_p(stream or None)))
+
+    def update_impulse(self, impulse_response, normalize: bool = True, fade_blocks: int = 1, curve: str = "linear",
+                       stream: int = 0) -> None:
+        """update_filter from impulse responses [C][L] float32 (host array or CUDA tensor):
+        normalize_impulse over the new impulse's channels (optional), then uniform_partition on the
+        device straight into the second bank (neo_hip_upols_update_impulse). Keeps all state."""
+        c = _fade_curve(curve)
+        lib = _native.load()
+        if _is_torch(impulse_response) and impulse_response.is_cuda:
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.channels * t.shape[-1]:
+                raise ValueError("impulse must be a contiguous float32 tensor of one row per channel")
+            _producer_join(t)
+            current = torch.cuda.current_stream(t.device).cuda_stream
+            _native.check(lib.neo_hip_upols_update_impulse(self._h, ctypes.c_void_p(t.data_ptr()), t.shape[-1],
+                                                           int(normalize), 1, int(fade_blocks), c,
+                                                           ctypes.c_void_p(stream or current or None)))
+            return
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)))
+        if ir.shape[0] != self.channels:
+            raise ValueError("impulse channel count mismatch")
+        _native.check(lib.neo_hip_upols_update_impulse(self._h, _ptr(ir), ir.shape[1], int(normalize), 0,
+                                                       int(fade_blocks), c, ctypes.c_void_p(stream or None)))
+
+    def fade_info(self) -> dict:
+        """remaining_blocks of the running fade (0: none), its fade_blocks (0: none) and bank_bytes,
+        the second filter bank (0 until the first update; kept from then on)."""
+        r, f, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols_fade_info(self._h, ctypes.byref(r), ctypes.byref(f), ctypes.byref(n)))
+        return {"remaining_blocks": r.value, "fade_blocks": f.value, "bank_bytes": n.value}
 
     # -- processing ---------------------------------------------------------
     def __call__(self, block, stream: int = 0):
@@ -592,6 +658,44 @@ class UpolsMultiConvolver:
         if ir.shape[0] != self.channels:
             raise ValueError("impulse channel count mismatch")
         _native.check(_native.load().neo_hip_upols_multi_set_impulse(self._h, _ptr(ir), ir.shape[1], int(normalize)))
+
+    def update_filter(self, partitions, fade_blocks: int = 1, curve: str = "linear", stream: int = 0) -> None:
+        """UpolsConvolver.update_filter on every shard (neo_hip_upols_multi_update_filter): host
+        partitions [C][P][B+1], complete on return (`stream` must stay 0: every shard has its own)."""
+        if stream:
+            raise ValueError("a multi-device convolver runs every shard on its own stream")
+        H = np.ascontiguousarray(partitions, dtype=np.complex64)
+        if H.shape != (self.channels, self.partitions, self.block_size + 1):
+            raise ValueError(f"filter shape {H.shape} != {(self.channels, self.partitions, self.block_size + 1)}")
+        _native.check(_native.load().neo_hip_upols_multi_update_filter(self._h, _ptr(H), int(fade_blocks),
+                                                                       _fade_curve(curve)))
+
+    def update_impulse(self, impulse_response, normalize: bool = True, fade_blocks: int = 1, curve: str = "linear",
+                       stream: int = 0) -> None:
+        """UpolsConvolver.update_impulse on every shard; the normalisation factor is taken once over
+        all channels, as set_impulse takes it."""
+        if stream:
+            raise ValueError("a multi-device convolver runs every shard on its own stream")
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)))
+        if ir.shape[0] != self.channels:
+            raise ValueError("impulse channel count mismatch")
+        _native.check(_native.load().neo_hip_upols_multi_update_impulse(self._h, _ptr(ir), ir.shape[1], int(normalize),
+                                                                        int(fade_blocks), _fade_curve(curve)))
+
+    def fade_info(self) -> dict:
+        """The shards' fades run in step: remaining_blocks and fade_blocks of shard 0, bank_bytes
+        summed over the shards."""
+        lib = _native.load()
+        out = {"remaining_blocks": 0, "fade_blocks": 0, "bank_bytes": 0}
+        for i in range(len(self.shards())):
+            h = ctypes.c_void_p()
+            _native.check(lib.neo_hip_upols_multi_shard(self._h, i, ctypes.byref(h), None, None, None))
+            r, f, n = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+            _native.check(lib.neo_hip_upols_fade_info(h, ctypes.byref(r), ctypes.byref(f), ctypes.byref(n)))
+            if i == 0:
+                out["remaining_blocks"], out["fade_blocks"] = r.value, f.value
+            out["bank_bytes"] += n.value
+        return out
 
     def process(self, samples) -> np.ndarray:
         """[C][n] float32 host samples (n a multiple of the block except for upola_v2) ->
@@ -1552,6 +1656,9 @@ def matrix_fade_gains(block: int, fade_blocks: int, curve="linear") -> np.ndarra
     g = np.zeros(int(fade_blocks) * int(block) if ok else 1, np.float32)
     _native.check(_native.load().neo_hip_matrix_fade_gains(int(block), int(fade_blocks), c, _ptr(g)))
     return g
+
+
+fade_gains = matrix_fade_gains  # shape-free: the dense convolvers' updates (UpolsConvolver.update_filter) fade by it too
 
 
 def _matrix_arg(x, np_dtype, count, bad_tensor: str, bad_array: str):
