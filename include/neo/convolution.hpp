@@ -312,6 +312,32 @@ struct upols_multichannel {
         neo::hip::check(neo_hip_upols_update_impulse(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, 0, fade_blocks,
                                                      int(curve), nullptr));
     }
+    /// sparse handles: live update (neo_hip_upols_update_filter_sparse) to `partitions` under `mask`
+    /// ([C][P][B+1] each, host memory), keeping all state; filter_sparse() remains the resetting call.
+    /// Complete on return; throws on a handle that is not sparse and while a fade still runs.
+    auto update_filter_sparse(std::complex<float> const* partitions, std::uint8_t const* mask, int fade_blocks = 1,
+                              fade_curve curve = fade_curve::linear) -> void
+    {
+        neo::hip::check(neo_hip_upols_update_filter_sparse(_h.get(), partitions, mask, 0, fade_blocks, int(curve), nullptr));
+    }
+    /// the same with the mask made on the device by the plugin's rule (the threshold knob)
+    auto update_filter_perceptual(std::complex<float> const* partitions, perceptual_sparsity const& sparsity,
+                                  int fade_blocks = 1, fade_curve curve = fade_curve::linear) -> void
+    {
+        sparsity.validate(_B);
+        auto const p = sparsity.c_struct();
+        neo::hip::check(neo_hip_upols_update_filter_perceptual(_h.get(), partitions, &p, 0, fade_blocks, int(curve), nullptr));
+    }
+    /// and from ir [C][length] (another impulse response while audio runs): normalize_impulse
+    /// (optional), uniform_partition, mask and tiles on the GPU; keeps all state
+    auto update_impulse_perceptual(float const* ir, std::size_t length, perceptual_sparsity const& sparsity,
+                                   bool normalize = true, int fade_blocks = 1, fade_curve curve = fade_curve::linear) -> void
+    {
+        sparsity.validate(_B);
+        auto const p = sparsity.c_struct();
+        neo::hip::check(neo_hip_upols_update_impulse_perceptual(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, &p, 0,
+                                                                fade_blocks, int(curve), nullptr));
+    }
     [[nodiscard]] auto fade_info() const -> fade_desc
     {
         fade_desc d{};
@@ -541,6 +567,31 @@ struct hip_sparse_upols_convolver {
         _block.resize(bins - 1);
     }
 
+    /// Live update: crossfade to `filter` under `sparsity` (a callable, as filter() takes it) over the
+    /// next fade_blocks blocks, keeping all state (upols_multichannel::update_filter_sparse); filter()
+    /// remains the resetting call. The shape must be the current filter's; throws before a filter()
+    /// and while a fade still runs.
+    template<typename InMat, typename Sparsity>
+        requires(neo::hip::detail::matrix_like<InMat> && !std::same_as<std::remove_cvref_t<Sparsity>, perceptual_sparsity>)
+    auto update_filter(InMat filter, Sparsity&& sparsity, int fade_blocks = 1, fade_curve curve = fade_curve::linear) -> void
+    {
+        auto const h = checked_copy(filter);
+        auto const mask = sparsity_mask(filter, sparsity);
+        _impl->update_filter_sparse(h.data(), mask.data(), fade_blocks, curve);
+    }
+
+    /// the same with the plugin's rule: the mask is made on the device from the filter
+    template<typename InMat>
+        requires neo::hip::detail::matrix_like<InMat>
+    auto update_filter(InMat filter, perceptual_sparsity const& sparsity, int fade_blocks = 1,
+                       fade_curve curve = fade_curve::linear) -> void
+    {
+        auto const h = checked_copy(filter);
+        _impl->update_filter_perceptual(h.data(), sparsity, fade_blocks, curve);
+    }
+
+    [[nodiscard]] auto fade_info() const -> fade_desc { return _impl ? _impl->fade_info() : fade_desc{}; }
+
     template<typename Vec>
         requires neo::hip::detail::vector_like<Vec>
     auto operator()(Vec block) -> void
@@ -555,6 +606,20 @@ struct hip_sparse_upols_convolver {
     }
 
 private:
+    // an update's filter as contiguous [P][B+1]: the shape of the filter the handle has
+    template<typename InMat>
+    auto checked_copy(InMat filter) const -> std::vector<Complex>
+    {
+        auto const P = std::size_t(filter.extent(0)), bins = std::size_t(filter.extent(1));
+        if (!_impl) throw std::runtime_error("sparse convolver: update_filter before filter()");
+        if (_impl->partitions() != P || _impl->block_size() != bins - 1)
+            throw std::runtime_error("sparse convolver: update_filter takes a filter of the current filter's shape");
+        std::vector<Complex> h(P * bins);
+        for (std::size_t p = 0; p < P; ++p)
+            for (std::size_t k = 0; k < bins; ++k) h[p * bins + k] = Complex(neo::hip::detail::at(filter, p, k));
+        return h;
+    }
+
     std::unique_ptr<upols_multichannel> _impl;
     std::vector<float> _block;
 };

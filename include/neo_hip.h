@@ -93,8 +93,12 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.12.0: the step groups' background stream is readable (neo_hip_upols_get_background_stream).
  * 0.13.0: crossfaded live filter updates on dense upols / upola handles (neo_hip_upols_update_filter,
  *        neo_hip_upols_update_impulse, neo_hip_upols_fade_info, neo_hip_upols_multi_update_filter,
- *        neo_hip_upols_multi_update_impulse). */
-#define NEO_HIP_VERSION 1300 /* 0.13.0 */
+ *        neo_hip_upols_multi_update_impulse).
+ * 0.14.0: crossfaded live filter updates on sparse handles (neo_hip_upols_update_filter_sparse,
+ *        neo_hip_upols_update_filter_perceptual, neo_hip_upols_update_impulse_perceptual,
+ *        neo_hip_upols_sparse_fade_plan; neo_hip_upols_fade_info and neo_hip_upols_sparse_info follow
+ *        a sparse handle's fade). */
+#define NEO_HIP_VERSION 1400 /* 0.14.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -223,7 +227,8 @@ NEO_HIP_API int neo_hip_upols_create_sparse(int channels, int block, int partiti
  * tiles are made on the device; the call waits on the handle's stream, never on the device. */
 NEO_HIP_API int neo_hip_upols_set_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device);
 /* the current filter's kept columns and kept tiles over all channels, and the device bytes that
- * stand in for a dense handle's [C][R][B] filter buffer (tiles, bitmaps, offsets) */
+ * stand in for a dense handle's [C][R][B] filter buffer (tiles, bitmaps, offsets); from a live
+ * update's call on (neo_hip_upols_update_filter_sparse) the filter being faded to */
 NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, int64_t* kept_tiles, int64_t* filter_bytes);
 /* The format on the host (no device needed; it is what set_filter_sparse computes on the device):
  * mask [C][P][B+1] -> tile_mask [C][P][NW], row_off [C][P+1], kept columns, kept tiles. */
@@ -369,7 +374,8 @@ NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h);
  * handle's stream, as host process calls) after the handle's earlier steps on any stream; returns
  * when the bank is written.
  * EINVAL, the handle unchanged: a null argument; before a filter is set; fade_blocks < 1 or > 2^20;
- * curve not 0 or 1; while a fade has blocks left; a sparse handle; an upola_convolver_v2 handle; a
+ * curve not 0 or 1; while a fade has blocks left; a sparse handle (it has forms of its own:
+ * neo_hip_upols_update_filter_sparse); an upola_convolver_v2 handle; a
  * handle owned by a convolver group; a handle in latency mode (neo_hip_upols_set_persistent, which
  * in turn refuses to switch on while a fade has blocks left). set_filter / set_impulse cancel a
  * running fade; reset completes it (B is the filter) and clears the state; set_batch, set_offline,
@@ -382,8 +388,51 @@ NEO_HIP_API int neo_hip_upols_update_filter(neo_hip_upols* h, const void* filter
 NEO_HIP_API int neo_hip_upols_update_impulse(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
                                              int is_device, int fade_blocks, int curve, void* stream);
 /* blocks left of the running fade (0: none), its length (0: none) and the bytes of the second filter
- * bank (0 until the first update) */
+ * bank (0 until the first update; a sparse handle: the spare bank's tables plus the tiles it holds) */
 NEO_HIP_API int neo_hip_upols_fade_info(neo_hip_upols* h, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes);
+/* Live filter update of a SPARSE handle (neo_hip_upols_create_sparse): neo_hip_upols_update_filter's
+ * definition, curves and guarantees with sparse filters. A is the handle's filter (its kept tiles), B
+ * is `filter` [C][P][B+1] under `mask` [C][P][B+1] (nonzero = keep; both host or both device memory,
+ * as set_filter_sparse takes them): y_A and y_B are the outputs of two sparse convolvers that had A
+ * and B from the start. ALL state is kept: the delay line is dense, so both banks run against the
+ * same rows; set_filter_sparse and the set_*_perceptual calls remain the resetting calls. A fade
+ * block is one two-bank sparse step (k_upols_sparse_fade_step: a delay-line tile is loaded once if
+ * either bank keeps it; neo_hip_upols_sparse_fade_plan gives its bytes) and the finish of the dense
+ * fade; its blocks equal the dense handle's fade on the zeroed filters bit for bit (same splits, up to
+ * the sign of zero), the blocks after it a sparse handle's that had B from the start (overlap-add:
+ * from the second block after the fade on). While a fade has blocks left every whole block of
+ * every process call is one fade step, whatever set_batch says; batched passes after it use B's
+ * window bitmaps. The spare bank's tables, the slabs [C][splits][2][B] and (overlap-add) a second
+ * set of tails come from the pool at the first update and are kept; B's tiles are sized by its kept
+ * tiles and so are allocated per update (none for a mask that keeps nothing: the fade to silence).
+ * The retired bank's tiles go back to the pool at the next update, resetting filter call, reset or
+ * destroy.
+ * STREAM CONTRACT: as neo_hip_upols_update_filter, with ONE difference: the call is NOT asynchronous,
+ * even with device memory. It waits on `stream` (never on the device) for the three counts that
+ * size B's tiles, as set_filter_sparse does; the perceptual forms wait once more for their scratch.
+ * EINVAL, the handle unchanged: a null argument; a handle that is not sparse; before a filter is
+ * set; fade_blocks < 1 or > 2^20; curve not 0 or 1; while a fade has blocks left.
+ * set_filter_sparse / set_*_perceptual cancel a running fade; reset completes it; set_batch keeps it. */
+NEO_HIP_API int neo_hip_upols_update_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device,
+                                                   int fade_blocks, int curve, void* stream);
+/* The same with the mask made on the device from `filter` by the perceptual predicate (the threshold
+ * knob: the same filter under another neo_hip_perceptual), and from an impulse response ir
+ * [C][length] (normalize_impulse if `normalize`, uniform_partition, mask, tiles: another impulse
+ * response while audio runs). Also EINVAL: parameters neo_hip_perceptual_weights refuses; a length
+ * that gives another partition count than the handle's. */
+NEO_HIP_API int neo_hip_upols_update_filter_perceptual(neo_hip_upols* h, const void* filter, const neo_hip_perceptual* p,
+                                                       int is_device, int fade_blocks, int curve, void* stream);
+NEO_HIP_API int neo_hip_upols_update_impulse_perceptual(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                                        const neo_hip_perceptual* p, int is_device, int fade_blocks,
+                                                        int curve, void* stream);
+/* What a sparse fade will cost, before a handle exists (host only): masks A and B [C][P][B+1] -> the
+ * kept tiles of A, of B and of A | B, the splits of a sparse handle of that shape with default
+ * options, and the model bytes of one fade step: 128 (tiles_a + tiles_b + tiles_union) + both banks'
+ * bitmap words and offsets 2 C P (NW + 1) 4 + the inserted row C B 8 + the slabs, written and read,
+ * 2 C splits 2 B 8 + the block in and out 2 C B 4. Outputs may be null. */
+NEO_HIP_API int neo_hip_upols_sparse_fade_plan(const uint8_t* mask_a, const uint8_t* mask_b, int channels, int block,
+                                               int partitions, int64_t* tiles_a, int64_t* tiles_b, int64_t* tiles_union,
+                                               int* splits, int64_t* step_bytes);
 /* Streaming levels for single-block steps (upols / upola; upols_levels.hip): the
  * partitions are cut into bands -- p in [0, 8) MAC'd by the block itself; Toeplitz windows
  * of 4 / 8 / 16 / 32 blocks for [8, 16) / [16, 32) / [32, 64) / [64, 256); for [256, P) a

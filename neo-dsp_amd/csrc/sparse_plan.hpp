@@ -81,4 +81,40 @@ inline bool sparse_window_plan(const uint32_t* tile_mask, int channels, int bloc
     return true;
 }
 
+// One fade step of a live filter update between two sparse filters (upols_sparse_fade.hip): both
+// banks run against the same FDL rows, and a lane loads its FDL tile once if either bank keeps it.
+// masks [C][P][B + 1] -> the kept tiles of A, of B and of A | B, and the model bytes of the step:
+// 128 B per kept tile of each bank and per FDL tile of the union, both banks' bitmap words and
+// offsets, the inserted row, the slabs [C][S][2][B] (written, then read by the finish) and the
+// block in and out: DESIGN 5.7's "Bytes per step" with two banks. false: bad arguments.
+struct sparse_fade_cost {
+    int64_t tiles_a = 0, tiles_b = 0, tiles_union = 0, step_bytes = 0;
+};
+inline bool sparse_fade_plan(const uint8_t* mask_a, const uint8_t* mask_b, int channels, int block, int partitions,
+                             int splits, sparse_fade_cost* out)
+{
+    if (!mask_a || !mask_b || !out || channels < 1 || partitions < 1 || splits < 1 || !sparse_block_ok(block)) return false;
+    const int NW = sparse_words(block);
+    const int64_t rows = int64_t(channels) * partitions, stride = int64_t(block) + 1;
+    sparse_fade_cost f;
+    for (int64_t r = 0; r < rows; ++r) {
+        uint32_t wa[8] = {}, wb[8] = {};  // NW <= 8 (block <= 4096)
+        for (int k = 0; k <= block; ++k) {
+            const int t = k == block ? 0 : k / kSparseTile;
+            if (mask_a[r * stride + k]) wa[t >> 5] |= uint32_t(1) << (t & 31);
+            if (mask_b[r * stride + k]) wb[t >> 5] |= uint32_t(1) << (t & 31);
+        }
+        for (int i = 0; i < NW; ++i) {
+            f.tiles_a += __builtin_popcount(wa[i]);
+            f.tiles_b += __builtin_popcount(wb[i]);
+            f.tiles_union += __builtin_popcount(wa[i] | wb[i]);
+        }
+    }
+    const int64_t C = channels, B = block;
+    f.step_bytes = 128 * (f.tiles_a + f.tiles_b + f.tiles_union) + 2 * rows * (NW + 1) * 4 + C * B * 8 +
+                   2 * C * splits * 2 * B * 8 + 2 * C * B * 4;
+    *out = f;
+    return true;
+}
+
 }  // namespace neo_hip

@@ -36,7 +36,10 @@
 // process_samples run every whole block as one fade step (fade_step: upols_fade.hip's two-bank MAC,
 // then the matrix convolver's fade finish with one "output" per channel), whatever the handle's
 // modes; at its end the banks swap by pointer (fade_swap). H_alloc remembers the allocation that
-// holds the FDL, whichever bank is current.
+// holds the FDL, whichever bank is current. A sparse handle's update (neo_hip_upols_update_filter_sparse
+// and the two perceptual forms; sparse_update) is the same frame with a spare sparse bank (h->sp2,
+// upols_sparse.hip) and upols_sparse_fade.hip's two-bank MAC; its call waits on its stream for the
+// kept-tile counts.
 // upols_batch.hip: T blocks per pass (process_blocks). upols_sparse.hip: the sparse handle's
 // buffers, filter and MAC. upols_setup.hip: partitioning and normalization. upols_device.hpp /
 // upols_handle.hpp: what they share.
@@ -385,7 +388,8 @@ void destroy(upols_t* h)
 // tails), and what is computed from the filter follows it (far segment spectra, offline spectra)
 void fade_swap(upols_t* h)
 {
-    std::swap(h->H, h->H2);
+    if (h->sparse) sparse_fade_swap(h);  // bitmaps, offsets, bases, tiles and counts; pc / pcb follow the new tiles
+    else std::swap(h->H, h->H2);
     if (h->ola) std::swap(h->prev, h->ovl2);
     h->fade_left = h->fade_total = 0;
     lvl_filter_changed(h);
@@ -397,7 +401,9 @@ void fade_swap(upols_t* h)
 int fade_step(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
     if (int rc = lvl_join(h, s)) return rc;
-    if (int rc = launch_upols_fade_mac(h, h->H, h->H2, in, ld_in, h->fade_S, h->fade_rows, h->wpos, false, s)) return rc;
+    if (int rc = h->sparse ? launch_sparse_fade_mac(h, sparse_cur(h), h->sp2, in, ld_in, h->fade_S, h->fade_rows, h->wpos, false, s)
+                           : launch_upols_fade_mac(h, h->H, h->H2, in, ld_in, h->fade_S, h->fade_rows, h->wpos, false, s))
+        return rc;
     h->fdl_zero = false;
     const int64_t n0 = int64_t(h->fade_total - h->fade_left) * h->B;
     if (int rc = launch_matrix_fade_finish(h->part_f, out, ld_out, h->prev, h->ovl2, h->tw, h->B, h->C, h->fade_S, h->ola,
@@ -746,10 +752,13 @@ std::vector<float> weights_for(const upols_t* h, const neo_hip_perceptual* pp)
 // -- live filter updates: update_* = check, the fade's buffers, the load into the spare bank on the
 // call's stream, update_end (overlap-add's priming pass, the fade armed) -------------------------
 
-// what every update checks before it touches anything
-int update_check(const upols_t* h, int fade_blocks, int curve)
+// what every update checks before it touches anything (sparse_call: one of the sparse forms, which
+// take sparse handles only; the dense forms keep refusing them)
+int update_check(const upols_t* h, int fade_blocks, int curve, bool sparse_call = false)
 {
-    if (h->sparse) return fail(NEO_HIP_EINVAL, "filter update: a sparse handle keeps no dense filter bank");
+    if (h->sparse && !sparse_call) return fail(NEO_HIP_EINVAL, "filter update: a sparse handle keeps no dense filter bank");
+    if (!h->sparse && sparse_call)
+        return fail(NEO_HIP_EINVAL, "sparse filter update: not a sparse handle (neo_hip_upols_create_sparse)");
     if (h->v2) return fail(NEO_HIP_EINVAL, "filter update: upola_convolver_v2 handles (sub-block input) are not faded");
     if (h->grouped) return fail(NEO_HIP_EINVAL, "filter update: the handle belongs to a convolver group");
     if (h->sched.persist) return fail(NEO_HIP_EINVAL, "filter update: the handle is in latency mode (set_persistent)");
@@ -819,7 +828,8 @@ int update_end(upols_t* h, int rc, bool is_device, int fade_blocks, int curve, h
                 rc = fail(NEO_HIP_ERUNTIME, "memset failed");
         } else {
             const int w1 = (h->wpos + h->ring - 1) % h->ring;
-            rc = launch_upols_fade_mac(h, h->H2, h->H2, nullptr, 0, h->fade_S, h->fade_rows, w1, true, s);
+            rc = h->sparse ? launch_sparse_fade_mac(h, h->sp2, h->sp2, nullptr, 0, h->fade_S, h->fade_rows, w1, true, s)
+                           : launch_upols_fade_mac(h, h->H2, h->H2, nullptr, 0, h->fade_S, h->fade_rows, w1, true, s);
             if (!rc)
                 rc = launch_matrix_fade_finish(h->part_f, nullptr, 0, h->prev, h->ovl2, h->tw, h->B, h->C, h->fade_S, true, true,
                                                0, 1, 0, s);
@@ -830,6 +840,32 @@ int update_end(upols_t* h, int rc, bool is_device, int fade_blocks, int curve, h
         h->fade_left = h->fade_total = fade_blocks;
         h->fade_curve = curve;
     }
+    return rc;
+}
+
+// A sparse handle's update after its checks: the call's stream, the fixed-size buffers (first update),
+// `load` (what differs between the three forms: the filter [C][P][B + 1] and its mask on the device,
+// on s; scratch it allocates goes into `scratch`), the one packing path into the spare bank, then
+// update_end. NOT asynchronous, even for device memory: sparse_fill waits on s for the three
+// counts that size bank B's tiles (the stream, never the device), and pooled scratch is given back
+// after a second wait on s. That first wait also covers the last step of an earlier fade, so the
+// retired bank's tiles go back to the pool inside sparse_fill.
+template<class Load>
+int sparse_update(upols_t* h, int is_device, int fade_blocks, int curve, void* stream, Load load)
+{
+    device_guard g(h->device);
+    if (g.rc) return g.rc;
+    hipStream_t s = update_stream(h, is_device, stream);
+    if (int rc = update_begin(h, is_device != 0, s)) return rc;
+    if (int rc = sparse_fade_buffers(h, s)) return rc;
+    std::vector<void*> scratch;
+    const cf* filter = nullptr;
+    const uint8_t* mask = nullptr;
+    int rc = load(s, &filter, &mask, scratch);
+    if (!rc) rc = sparse_fill(h, h->sp2, filter, mask, s);
+    const bool wait = !is_device || !scratch.empty();
+    rc = update_end(h, rc, !wait, fade_blocks, curve, s);  // (is_device = false: it waits on s)
+    for (void* p : scratch) dfree(p);
     return rc;
 }
 
@@ -906,10 +942,12 @@ NEO_HIP_API int neo_hip_upols_sparse_info(neo_hip_upols* h, int64_t* kept_bins, 
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     if (!h->sparse) return fail(NEO_HIP_EINVAL, "sparse_info: not a sparse handle");
-    if (kept_bins) *kept_bins = h->sp_bins;
-    if (kept_tiles) *kept_tiles = h->sp_tiles;
+    // from a live update's call on: the bank being faded to
+    const int64_t bins = h->fade_left > 0 ? h->sp2.bins : h->sp_bins, tiles = h->fade_left > 0 ? h->sp2.tiles : h->sp_tiles;
+    if (kept_bins) *kept_bins = bins;
+    if (kept_tiles) *kept_tiles = tiles;
     if (filter_bytes)  // the compacted tiles, the bitmaps and the offsets: what stands in for the [C][R][B] filter
-        *filter_bytes = h->sp_tiles * int64_t(kSparseTile * sizeof(cf)) +
+        *filter_bytes = tiles * int64_t(kSparseTile * sizeof(cf)) +
                         int64_t(h->C) * (int64_t(h->P) * sparse_words(h->B) + h->P + 1) * int64_t(sizeof(uint32_t));
     return NEO_HIP_OK;
 }
@@ -991,6 +1029,7 @@ NEO_HIP_API int neo_hip_upols_reset(neo_hip_upols* h)
     device_guard g(h->device);
     if (int rc = set_begin(h, false)) return rc;  // after this handle's steps on any stream
     if (h->fade_left > 0) fade_swap(h);  // a running fade completes: the new filter is the filter
+    if (h->sparse) sparse_release_spare(h);  // joined above: a retired sparse bank's tiles go back
     int rc = reset_state(h, h->stream);
     if (!rc) rc = lvl_setup_prime(h);  // the next call is an ordinary streaming step
     if (rc) return rc;
@@ -1069,12 +1108,101 @@ NEO_HIP_API int neo_hip_upols_update_impulse(neo_hip_upols* h, const float* ir, 
     return rc;
 }
 
+NEO_HIP_API int neo_hip_upols_update_filter_sparse(neo_hip_upols* h, const void* filter, const uint8_t* mask, int is_device,
+                                                   int fade_blocks, int curve, void* stream)
+{
+    if (!h || !filter || !mask) return fail(NEO_HIP_EINVAL, "update_filter_sparse: null handle, filter or mask");
+    if (int rc = update_check(h, fade_blocks, curve, true)) return rc;
+    return sparse_update(h, is_device, fade_blocks, curve, stream,
+                         [&](hipStream_t s, const cf** f, const uint8_t** m, std::vector<void*>& scratch) {
+                             const size_t n = filter_elems(h);
+                             cf* tmpf = nullptr;
+                             uint8_t* tmpm = nullptr;
+                             int rc = stage_in(static_cast<const cf*>(filter), n * sizeof(cf), is_device != 0, false, s, &tmpf, f);
+                             if (tmpf) scratch.push_back(tmpf);
+                             if (!rc) rc = stage_in(mask, n, is_device != 0, false, s, &tmpm, m);
+                             if (tmpm) scratch.push_back(tmpm);
+                             return rc;
+                         });
+}
+
+NEO_HIP_API int neo_hip_upols_update_filter_perceptual(neo_hip_upols* h, const void* filter, const neo_hip_perceptual* pp,
+                                                       int is_device, int fade_blocks, int curve, void* stream)
+{
+    if (int rc = check_perceptual("update_filter_perceptual", h, filter, pp)) return rc;
+    if (int rc = update_check(h, fade_blocks, curve, true)) return rc;
+    const std::vector<float> w = weights_for(h, pp);  // alive until the call's last wait on its stream
+    return sparse_update(h, is_device, fade_blocks, curve, stream,
+                         [&](hipStream_t s, const cf** f, const uint8_t** m, std::vector<void*>& scratch) {
+                             cf* tmpf = nullptr;
+                             uint8_t* msk = nullptr;
+                             float* tmp = nullptr;
+                             int rc = stage_in(static_cast<const cf*>(filter), filter_elems(h) * sizeof(cf), is_device != 0, false,
+                                               s, &tmpf, f);
+                             if (tmpf) scratch.push_back(tmpf);
+                             if (!rc && dalloc(&msk, filter_elems(h))) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+                             if (msk) scratch.push_back(msk);
+                             if (!rc) rc = perceptual_mask_device(*f, h->C, h->B, h->P, pp, w.data(), msk, &tmp, s);
+                             if (tmp) scratch.push_back(tmp);
+                             *m = msk;
+                             return rc;
+                         });
+}
+
+NEO_HIP_API int neo_hip_upols_update_impulse_perceptual(neo_hip_upols* h, const float* ir, int64_t length, int normalize,
+                                                        const neo_hip_perceptual* pp, int is_device, int fade_blocks,
+                                                        int curve, void* stream)
+{
+    if (length < 1) return fail(NEO_HIP_EINVAL, "update_impulse_perceptual: empty impulse");
+    if (int rc = check_perceptual("update_impulse_perceptual", h, ir, pp)) return rc;
+    if (int rc = update_check(h, fade_blocks, curve, true)) return rc;
+    if (int rc = check_impulse(h, length)) return rc;
+    const std::vector<float> w = weights_for(h, pp);
+    return sparse_update(h, is_device, fade_blocks, curve, stream,
+                         [&](hipStream_t s, const cf** f, const uint8_t** m, std::vector<void*>& scratch) {
+                             cf* parts = nullptr;
+                             uint8_t* msk = nullptr;
+                             float *d = nullptr, *tmp = nullptr;
+                             int rc = dalloc(&parts, filter_elems(h) * sizeof(cf)) ? fail(NEO_HIP_ENOMEM, "allocation failed")
+                                                                                  : NEO_HIP_OK;
+                             if (parts) scratch.push_back(parts);
+                             if (!rc) rc = load_impulse(h, ir, length, normalize, is_device, parts, &d, nullptr, s);
+                             if (d) scratch.push_back(d);
+                             if (!rc && dalloc(&msk, filter_elems(h))) rc = fail(NEO_HIP_ENOMEM, "allocation failed");
+                             if (msk) scratch.push_back(msk);
+                             if (!rc) rc = perceptual_mask_device(parts, h->C, h->B, h->P, pp, w.data(), msk, &tmp, s);
+                             if (tmp) scratch.push_back(tmp);
+                             *f = parts;
+                             *m = msk;
+                             return rc;
+                         });
+}
+
+NEO_HIP_API int neo_hip_upols_sparse_fade_plan(const uint8_t* mask_a, const uint8_t* mask_b, int channels, int block,
+                                               int partitions, int64_t* tiles_a, int64_t* tiles_b, int64_t* tiles_union,
+                                               int* splits, int64_t* step_bytes)
+{
+    // the splits of a sparse handle of this shape with default options (the fade step runs the plain step's)
+    upols_shape shape;
+    sparse_fade_cost f;
+    const char* why = make_upols_shape(channels, block, partitions, nullptr, upols_kind::sparse, false, shape);
+    if (why || !sparse_fade_plan(mask_a, mask_b, channels, block, partitions, upols_fade_split(shape).S, &f))
+        return fail(NEO_HIP_EINVAL, "sparse_fade_plan: %s", why ? why : "null mask");
+    if (tiles_a) *tiles_a = f.tiles_a;
+    if (tiles_b) *tiles_b = f.tiles_b;
+    if (tiles_union) *tiles_union = f.tiles_union;
+    if (splits) *splits = upols_fade_split(shape).S;
+    if (step_bytes) *step_bytes = f.step_bytes;
+    return NEO_HIP_OK;
+}
+
 NEO_HIP_API int neo_hip_upols_fade_info(neo_hip_upols* h, int* remaining_blocks, int* fade_blocks, int64_t* bank_bytes)
 {
     if (!h) return fail(NEO_HIP_EINVAL, "null handle");
     if (remaining_blocks) *remaining_blocks = h->fade_left;
     if (fade_blocks) *fade_blocks = h->fade_total;
-    if (bank_bytes) *bank_bytes = h->H2 ? upols_fade_split(h->shape).bank_bytes : 0;
+    // dense: the second bank [C][ring][B]; sparse: the spare bank's tables plus the tiles it holds
+    if (bank_bytes) *bank_bytes = h->sparse ? sparse_spare_bytes(h) : h->H2 ? upols_fade_split(h->shape).bank_bytes : 0;
     return NEO_HIP_OK;
 }
 

@@ -130,6 +130,16 @@ __device__ __forceinline__ bool ps_record(const persist_ctl& pc, int64_t n, bool
     return true;
 }
 
+// One bank of a sparse handle's filter (sparse_plan.hpp): the fixed-size tables, the compacted tiles
+// (sized by the filter's kept tiles; null while none is kept) and the counts that came back from
+// the device. The handle's current bank is its sp_* members; the spare one (a live update's) is sp2.
+struct sparse_bank {
+    uint32_t *bits = nullptr, *win = nullptr, *off = nullptr;
+    int64_t* base = nullptr;
+    cf* val = nullptr;
+    int64_t tiles = 0, bins = 0, wtiles = 0;
+};
+
 }  // namespace neo_hip
 
 struct neo_hip_upols {
@@ -214,6 +224,12 @@ struct neo_hip_upols {
     int64_t sp_tiles = 0, sp_bins = 0;
     uint32_t* sp_win = nullptr;    // window bitmaps [C][P][NW]: the OR of rows [p, min(P, p + kMaxBatch)) of sp_bits
     int64_t sp_wtiles = 0;         // their popcount sum
+    // live updates of a sparse handle (upols_sparse_fade.hip): the spare bank, bank B while a fade
+    // runs and the retired filter after it. Its tables come with the first update and stay; its
+    // tiles are allocated per update and go back to the pool at the next wait that covers the last
+    // step that read them (the next update's wait for the counts, a resetting call's join, destroy).
+    // part_f, ovl2 and the fade_* members above are shared with the dense handles' fades.
+    neo_hip::sparse_bank sp2;
     struct ev_group {
         hipEvent_t e[4] = {};
         int n = 0;
@@ -299,6 +315,31 @@ int create_handle(int channels, int block, int partitions, int device, int metho
 int sparse_alloc(upols_t* h);
 void sparse_free(upols_t* h);
 int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s);
+// live updates (upols_sparse.hip): the handle's current bank as a value and back; the spare bank's
+// tables, the fade step's slabs and overlap-add's second tails at the first update (on s);
+// sparse_fill: the one packing path, a filter into bank b on s (the bank's old tiles freed and the new
+// ones allocated after the wait on s for the three counts); the end of a fade (banks swap by
+// pointer, pc / pcb follow the new tiles); the spare bank's tiles back to the pool (the caller
+// joined every step that read them); what fade_info reports
+inline sparse_bank sparse_cur(const upols_t* h)
+{
+    return {h->sp_bits, h->sp_win, h->sp_off, h->sp_base, h->sp_val, h->sp_tiles, h->sp_bins, h->sp_wtiles};
+}
+inline void sparse_put(upols_t* h, const sparse_bank& b)
+{
+    h->sp_bits = b.bits, h->sp_win = b.win, h->sp_off = b.off, h->sp_base = b.base, h->sp_val = b.val;
+    h->sp_tiles = b.tiles, h->sp_bins = b.bins, h->sp_wtiles = b.wtiles;
+}
+int sparse_fill(upols_t* h, sparse_bank& b, const cf* filter, const uint8_t* mask, hipStream_t s);
+int sparse_fade_buffers(upols_t* h, hipStream_t s);
+void sparse_fade_swap(upols_t* h);
+void sparse_release_spare(upols_t* h);
+int64_t sparse_spare_bytes(const upols_t* h);
+// upols_sparse_fade.hip: the MAC of a sparse handle's fade step: banks a, b (kept tiles only) against
+// the FDL at write position w into the slabs h->part_f [C][S][2][B]; split 0 and prime as
+// launch_upols_fade_mac. The finish is launch_matrix_fade_finish with O = C.
+int launch_sparse_fade_mac(const upols_t* h, const sparse_bank& a, const sparse_bank& b, const float* in, int64_t ld_in,
+                           int S, int rows, int w, bool prime, hipStream_t s);
 int launch_sparse_mac(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s);
 // upols_sparse_batch.hip: the MAC of a batched pass of a sparse handle (launch_batch, upols_batch.hip):
 // T blocks at write position h->wpos into the slabs part_b [C][Sb][T][B], over the kept tiles

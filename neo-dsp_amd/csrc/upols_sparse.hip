@@ -15,6 +15,11 @@
 // of the sums per bin is the dense order with the dropped terms left out, so with the same
 // splits a sparse handle equals the dense plain step on the zeroed filter bit for bit (a 0 * x
 // term leaves a float sum unchanged), up to the sign of zero.
+//
+// Banks: the tables and tiles of one filter are a sparse_bank (upols_handle.hpp). The setup fills the
+// bank it is given (sparse_fill: one packing path), the handle's current one for the resetting filter
+// calls, the spare one for a live update (upols_sparse_fade.hip has the fade step); at the end of a
+// fade the two swap by pointer (sparse_fade_swap).
 #include "sparse_plan.hpp"
 #include "upols_handle.hpp"
 #include "upols_step.hpp"
@@ -184,68 +189,157 @@ __global__ __launch_bounds__(256) void k_sparse_pack(const cf* __restrict__ filt
     }
 }
 
+namespace {
+
+// a bank's fixed-size tables, zeroed on s: an empty filter (no tile kept, every offset zero)
+int bank_tables(const upols_t* h, sparse_bank& b, hipStream_t s)
+{
+    const size_t rows = size_t(h->C) * size_t(h->P), words = rows * sparse_words(h->B) * sizeof(uint32_t);
+    if (dalloc(&b.bits, words) || dalloc(&b.win, words) || dalloc(&b.off, (rows + h->C) * sizeof(uint32_t)) ||
+        dalloc(&b.base, size_t(h->C + 3) * sizeof(int64_t)))
+        return NEO_HIP_ENOMEM;
+    NEO_HIP_CHECK(hipMemsetAsync(b.bits, 0, words, s));
+    NEO_HIP_CHECK(hipMemsetAsync(b.win, 0, words, s));
+    NEO_HIP_CHECK(hipMemsetAsync(b.off, 0, (rows + h->C) * sizeof(uint32_t), s));
+    NEO_HIP_CHECK(hipMemsetAsync(b.base, 0, size_t(h->C + 3) * sizeof(int64_t), s));
+    return NEO_HIP_OK;
+}
+
+void bank_free(sparse_bank& b)
+{
+    dfree(b.bits);
+    dfree(b.win);
+    dfree(b.off);
+    dfree(b.base);
+    dfree(b.val);
+    b = sparse_bank{};
+}
+
+// what the step reads cacheable follows the current filter's kept bytes
+void cache_rows(upols_t* h)
+{
+    const double bytes = double(h->sp_tiles) * kSparseTile * sizeof(cf);
+    h->shape.pc = sparse_cache_rows(h->P, bytes, kCacheBudgetBytes);
+    h->shape.pcb = sparse_cache_rows(h->P, bytes, kBatchCacheBudgetBytes);
+}
+
+}  // namespace
+
 int sparse_alloc(upols_t* h)
 {
-    const size_t rows = size_t(h->C) * size_t(h->P);
-    if (dalloc(&h->sp_bits, rows * sparse_words(h->B) * sizeof(uint32_t)) ||
-        dalloc(&h->sp_win, rows * sparse_words(h->B) * sizeof(uint32_t)) ||
-        dalloc(&h->sp_off, (rows + h->C) * sizeof(uint32_t)) || dalloc(&h->sp_base, size_t(h->C + 3) * sizeof(int64_t)))
-        return NEO_HIP_ENOMEM;
-    // an empty filter until the first one is set: no tile kept, every offset zero
-    NEO_HIP_CHECK(hipMemsetAsync(h->sp_bits, 0, rows * sparse_words(h->B) * sizeof(uint32_t), h->stream));
-    NEO_HIP_CHECK(hipMemsetAsync(h->sp_win, 0, rows * sparse_words(h->B) * sizeof(uint32_t), h->stream));
-    NEO_HIP_CHECK(hipMemsetAsync(h->sp_off, 0, (rows + h->C) * sizeof(uint32_t), h->stream));
-    NEO_HIP_CHECK(hipMemsetAsync(h->sp_base, 0, size_t(h->C + 3) * sizeof(int64_t), h->stream));
-    return NEO_HIP_OK;
+    sparse_bank b;
+    const int rc = bank_tables(h, b, h->stream);
+    sparse_put(h, b);  // (a partial allocation too: the handle's destroy gives it back)
+    return rc;
 }
 
 void sparse_free(upols_t* h)
 {
-    dfree(h->sp_bits);
-    dfree(h->sp_win);
-    dfree(h->sp_off);
-    dfree(h->sp_base);
-    dfree(h->sp_val);
-    h->sp_bits = h->sp_win = h->sp_off = nullptr;
-    h->sp_base = nullptr;
-    h->sp_val = nullptr;
+    sparse_bank b = sparse_cur(h);
+    bank_free(b);
+    sparse_put(h, b);
+    bank_free(h->sp2);
 }
 
-int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s)
+// The one packing path: filter and mask [C][P][B + 1] (device) into bank b, on s. The call waits on
+// s for the three counts (kept tiles, kept columns, window tiles), never on the device; that wait
+// also covers whatever earlier work on s read the bank's old tiles, which go back to the pool after
+// it, before the new ones are allocated.
+int sparse_fill(upols_t* h, sparse_bank& b, const cf* filter, const uint8_t* mask, hipStream_t s)
 {
     const int64_t rows = int64_t(h->C) * h->P;
     if (rows > 0x7fffffff) return fail(NEO_HIP_EINVAL, "too many partitions");
-    // the caller joined every stream this handle's steps ran on: the old tiles are free to go
-    dfree(h->sp_val);
-    h->sp_val = nullptr;
-    h->sp_tiles = h->sp_bins = h->sp_wtiles = 0;
-    unsigned long long* cols = reinterpret_cast<unsigned long long*>(h->sp_base + h->C + 1);  // and the window tiles
+    unsigned long long* cols = reinterpret_cast<unsigned long long*>(b.base + h->C + 1);  // and the window tiles
     NEO_HIP_CHECK(hipMemsetAsync(cols, 0, 2 * sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(k_sparse_rows, dim3(unsigned(rows)), dim3(256), 0, s, mask, h->B, h->P, h->sp_bits, h->sp_off, cols);
+    hipLaunchKernelGGL(k_sparse_rows, dim3(unsigned(rows)), dim3(256), 0, s, mask, h->B, h->P, b.bits, b.off, cols);
     NEO_HIP_LAUNCH_CHECK();
     const int64_t words = rows * sparse_words(h->B);
-    hipLaunchKernelGGL(k_sparse_win, dim3(unsigned((words + 255) / 256)), dim3(256), 0, s, h->sp_bits, h->P,
-                       sparse_words(h->B), words, h->sp_win, cols + 1);
+    hipLaunchKernelGGL(k_sparse_win, dim3(unsigned((words + 255) / 256)), dim3(256), 0, s, b.bits, h->P,
+                       sparse_words(h->B), words, b.win, cols + 1);
     NEO_HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sparse_scan, dim3(unsigned(h->C)), dim3(256), 0, s, h->sp_off, h->P);
+    hipLaunchKernelGGL(k_sparse_scan, dim3(unsigned(h->C)), dim3(256), 0, s, b.off, h->P);
     NEO_HIP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sparse_base, dim3(1), dim3(64), 0, s, h->sp_off, h->C, h->P, h->sp_base);
+    hipLaunchKernelGGL(k_sparse_base, dim3(1), dim3(64), 0, s, b.off, h->C, h->P, b.base);
     NEO_HIP_LAUNCH_CHECK();
     int64_t tot[3] = {0, 0, 0};  // kept tiles, kept columns, window tiles: all that comes back to the host
-    NEO_HIP_CHECK(hipMemcpyAsync(tot, h->sp_base + h->C, sizeof tot, hipMemcpyDeviceToHost, s));
-    NEO_HIP_CHECK(hipStreamSynchronize(s));  // the handle's stream, never the device
-    h->sp_tiles = tot[0];
-    h->sp_bins = tot[1];
-    h->sp_wtiles = tot[2];
-    const double bytes = double(h->sp_tiles) * kSparseTile * sizeof(cf);
-    h->shape.pc = sparse_cache_rows(h->P, bytes, kCacheBudgetBytes);
-    h->shape.pcb = sparse_cache_rows(h->P, bytes, kBatchCacheBudgetBytes);
-    if (!h->sp_tiles) return NEO_HIP_OK;
-    if (int rc = dalloc(&h->sp_val, size_t(h->sp_tiles) * kSparseTile * sizeof(cf))) return rc;
-    hipLaunchKernelGGL(k_sparse_pack, dim3(unsigned(rows)), dim3(256), 0, s, filter, mask, h->B, h->P, h->sp_bits,
-                       h->sp_off, h->sp_base, h->sp_val);
+    NEO_HIP_CHECK(hipMemcpyAsync(tot, b.base + h->C, sizeof tot, hipMemcpyDeviceToHost, s));
+    NEO_HIP_CHECK(hipStreamSynchronize(s));  // the call's stream, never the device
+    dfree(b.val);
+    b.val = nullptr;
+    b.tiles = tot[0];
+    b.bins = tot[1];
+    b.wtiles = tot[2];
+    if (!b.tiles) return NEO_HIP_OK;
+    if (int rc = dalloc(&b.val, size_t(b.tiles) * kSparseTile * sizeof(cf))) return rc;
+    hipLaunchKernelGGL(k_sparse_pack, dim3(unsigned(rows)), dim3(256), 0, s, filter, mask, h->B, h->P, b.bits, b.off,
+                       b.base, b.val);
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
+}
+
+// the resetting filter call's store: the caller joined every stream this handle's steps ran on, so
+// the old tiles and a retired or cancelled spare bank's tiles are free to go
+int sparse_set_filter(upols_t* h, const cf* filter, const uint8_t* mask, hipStream_t s)
+{
+    sparse_release_spare(h);
+    sparse_bank b = sparse_cur(h);
+    dfree(b.val);
+    b.val = nullptr;
+    b.tiles = b.bins = b.wtiles = 0;
+    const int rc = sparse_fill(h, b, filter, mask, s);
+    sparse_put(h, b);
+    cache_rows(h);
+    return rc;
+}
+
+// A live update's fixed-size buffers, at the first update, kept until the handle goes: the spare
+// bank's tables, the fade step's slabs [C][S][2][B] (the plain step's splits, upols_fade_split) and,
+// overlap-add, bank B's tails [C][B].
+int sparse_fade_buffers(upols_t* h, hipStream_t s)
+{
+    if (h->sp2.bits) return NEO_HIP_OK;
+    const upols_fade_plan f = upols_fade_split(h->shape);
+    sparse_bank b;
+    cf* slabs = nullptr;
+    float* tails = nullptr;
+    int rc = bank_tables(h, b, s);
+    if (!rc && (dalloc(&slabs, size_t(f.slab_bytes)) || (h->ola && dalloc(&tails, size_t(h->C) * h->B * sizeof(float)))))
+        rc = NEO_HIP_ENOMEM;
+    if (rc) {
+        bank_free(b);
+        dfree(slabs);
+        dfree(tails);
+        return rc == NEO_HIP_ENOMEM ? fail(NEO_HIP_ENOMEM, "filter update: allocation of the second sparse bank failed") : rc;
+    }
+    h->sp2 = b;
+    h->part_f = slabs;
+    h->ovl2 = tails;
+    h->fade_S = f.S;
+    h->fade_rows = f.rows;
+    return NEO_HIP_OK;
+}
+
+void sparse_fade_swap(upols_t* h)
+{
+    const sparse_bank a = sparse_cur(h);
+    sparse_put(h, h->sp2);
+    h->sp2 = a;  // retired: its tiles stay until a wait covers the last fade step (sparse_release_spare, sparse_fill)
+    cache_rows(h);
+}
+
+void sparse_release_spare(upols_t* h)
+{
+    dfree(h->sp2.val);
+    h->sp2.val = nullptr;
+    h->sp2.tiles = h->sp2.bins = h->sp2.wtiles = 0;
+}
+
+int64_t sparse_spare_bytes(const upols_t* h)
+{
+    if (!h->sp2.bits) return 0;
+    const int64_t rows = int64_t(h->C) * h->P;
+    return (2 * rows * sparse_words(h->B) + rows + h->C) * int64_t(sizeof(uint32_t)) + int64_t(h->C + 3) * int64_t(sizeof(int64_t)) +
+           (h->sp2.val ? h->sp2.tiles * int64_t(kSparseTile * sizeof(cf)) : 0);
 }
 
 int launch_sparse_mac(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)

@@ -11,7 +11,7 @@ from .convolution import (UpolsConvolver, UpolsMultiConvolver, convolve, dense_c
                           host_register, host_unregister, memory_info, memory_trim, normalize_impulse, overlap_add, overlap_save, OverlapStage, UpolsGroup,
                           num_partitions, split_upola_convolver, split_upols_convolver, uniform_partition,
                           upola_convolver, upola_convolver_v2, upols_convolver,
-                          SparseUpolsConvolver, sparse_convolve, sparse_plan, sparse_window_plan,
+                          SparseUpolsConvolver, sparse_convolve, sparse_fade_plan, sparse_plan, sparse_window_plan,
                           sparse_upola_convolver,
                           sparse_upols_convolver, PerceptualSparsity, a_weighting, amplitude_to_db, perceptual_histogram,
                           perceptual_histogram_host, perceptual_mask, perceptual_mask_host, perceptual_weights,
@@ -48,6 +48,7 @@ __all__ = [
     "sparse_upola_convolver",
     "sparse_plan",
     "sparse_window_plan",
+    "sparse_fade_plan",
     "sparse_convolve",
     "MatrixConvolver",
     "matrix_plan",

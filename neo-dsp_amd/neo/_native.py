@@ -133,6 +133,11 @@ SIGNATURES = {
     "neo_hip_upols_update_filter": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "neo_hip_upols_update_impulse": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _vp]),
     "neo_hip_upols_fade_info": (_i, [_vp, _vp, _vp, _vp]),
+    "neo_hip_upols_update_filter_sparse": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "neo_hip_upols_update_filter_perceptual": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "neo_hip_upols_update_impulse_perceptual": (_i, [_vp, _vp, _i64, _i, _vp, _i, _i, _i, _vp]),
+    "neo_hip_upols_sparse_fade_plan": (_i, [_vp, _vp, _i, _i, _i] + [ctypes.POINTER(_i64)] * 3 +
+                                       [ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
     "neo_hip_upols_set_ahead": (_i, [_vp, _i]),
     "neo_hip_upols_set_offline": (_i, [_vp, _i]),
     "neo_hip_upols_get_offline": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
@@ -218,7 +223,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1300 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1400 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

@@ -52,6 +52,7 @@ __all__ = [
     "sparse_upola_convolver",
     "sparse_plan",
     "sparse_window_plan",
+    "sparse_fade_plan",
     "sparse_convolve",
     "MatrixConvolver",
     "matrix_plan",
@@ -1063,6 +1064,33 @@ def sparse_window_plan(tile_mask, block_size: int, window: int) -> dict:
     return {"win_mask": wm, "window_tiles": wt.value}
 
 
+def sparse_fade_plan(mask_a, mask_b, block_size: int) -> dict:
+    """What one block of a sparse fade from mask A to mask B will cost, on the host
+    (neo_hip_upols_sparse_fade_plan; no device or handle needed). Masks [C][P][B+1] or [P][B+1],
+    true = keep. Returns `tiles_a`, `tiles_b`, `tiles_union` (kept 128-byte tiles of A, of B and
+    of A | B: a fade step loads each bank's kept filter tiles and each delay-line tile of the union
+    once), `splits` (of a sparse handle of that shape with default options) and `step_bytes`, the
+    model bytes of one fade step: 128 (tiles_a + tiles_b + tiles_union) + both banks' bitmap words
+    and offsets + the inserted row + the slabs + the block in and out."""
+    ms = []
+    for mask in (mask_a, mask_b):
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.ndim == 2:
+            m = m[None]
+        if m.ndim != 3 or m.shape[2] != block_size + 1:
+            raise ValueError(f"mask must be [C][P][{block_size + 1}], got {m.shape}")
+        ms.append(m)
+    if ms[0].shape != ms[1].shape:
+        raise ValueError(f"the two masks differ in shape: {ms[0].shape} and {ms[1].shape}")
+    C, P, _ = ms[0].shape
+    ta, tb, tu, sb, sp = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    _native.check(_native.load().neo_hip_upols_sparse_fade_plan(_ptr(ms[0]), _ptr(ms[1]), C, int(block_size), P,
+                                                                ctypes.byref(ta), ctypes.byref(tb), ctypes.byref(tu),
+                                                                ctypes.byref(sp), ctypes.byref(sb)))
+    return {"tiles_a": ta.value, "tiles_b": tb.value, "tiles_union": tu.value, "splits": sp.value,
+            "step_bytes": sb.value}
+
+
 def a_weighting(frequency):
     """neo::a_weighting (src/neo/math/a_weighting.hpp; extra/python/src/main.cpp:260-263): the
     A-weighting in dB at `frequency` Hz, vectorised, in the input's float dtype (float64 for
@@ -1358,9 +1386,104 @@ class SparseUpolsConvolver(UpolsConvolver):
         _native.check(lib.neo_hip_upols_set_impulse_perceptual(self._h, _ptr(ir), ir.shape[1], int(normalize),
                                                                ctypes.byref(p), 0))
 
+    # -- live updates -------------------------------------------------------
+    def update_filter(self, partitions, mask=None, fade_blocks: int = 1, curve: str = "linear", stream: int = 0) -> None:
+        """Live update of a sparse convolver (neo_hip_upols_update_filter_sparse / _perceptual):
+        crossfade from the current sparse filter to `partitions` [C][P][B+1] under `mask` (an array
+        or tensor [C][P][B+1], true = keep, or a PerceptualSparsity, as filter() takes it) over the
+        next fade_blocks blocks and KEEP ALL STATE; filter() and set_impulse() remain the resetting
+        calls. Sample n of the fade is y_A + g[n] (y_B - y_A) with g = fade_gains(block_size,
+        fade_blocks, curve), y_A and y_B the outputs of two sparse convolvers that had the old and
+        the new filter from the start. Turning the threshold knob is update_filter(the same
+        partitions, another PerceptualSparsity). Host arrays and CUDA tensors; unlike the dense
+        update a CUDA tensor's call is NOT asynchronous: it waits on its stream (torch's current
+        stream, or `stream`; the stream the process calls run on) for the kept-tile counts that size
+        the new tiles. Without a mask the call falls through to the dense form, which the library
+        refuses on a sparse handle."""
+        if mask is None:
+            return super().update_filter(partitions, fade_blocks, curve, stream)
+        c = _fade_curve(curve)
+        lib = _native.load()
+        shape = (self.channels, self.partitions, self.block_size + 1)
+        perceptual = mask._c() if isinstance(mask, PerceptualSparsity) else None
+        if _is_torch(partitions) and partitions.is_cuda:
+            import torch
+
+            if partitions.dtype != torch.complex64 or not partitions.is_contiguous() or partitions.numel() != int(np.prod(shape)):
+                raise ValueError(f"filter must be a contiguous complex64 tensor of {shape}")
+            _producer_join(partitions)
+            current = torch.cuda.current_stream(partitions.device)
+            s = ctypes.c_void_p(stream or current.cuda_stream or None)
+            if perceptual is not None:
+                _native.check(lib.neo_hip_upols_update_filter_perceptual(self._h, ctypes.c_void_p(partitions.data_ptr()),
+                                                                         ctypes.byref(perceptual), 1, int(fade_blocks), c, s))
+                return
+            m = mask if _is_torch(mask) else torch.as_tensor(np.asarray(mask))
+            m = (m != 0).to(device=partitions.device, dtype=torch.uint8).contiguous()
+            if m.numel() != partitions.numel():
+                raise ValueError(f"mask must be {shape}")
+            if stream and stream != current.cuda_stream:
+                current.synchronize()  # the mask made above, on another stream than the call's
+            _native.check(lib.neo_hip_upols_update_filter_sparse(self._h, ctypes.c_void_p(partitions.data_ptr()),
+                                                                 ctypes.c_void_p(m.data_ptr()), 1, int(fade_blocks), c, s))
+            return
+        H = _host_partitions(partitions.numpy() if _is_torch(partitions) else partitions)
+        if H.shape != shape:
+            raise ValueError(f"filter shape {H.shape} != {shape}")
+        s = ctypes.c_void_p(stream or None)
+        if perceptual is not None:
+            _native.check(lib.neo_hip_upols_update_filter_perceptual(self._h, _ptr(H), ctypes.byref(perceptual), 0,
+                                                                     int(fade_blocks), c, s))
+            return
+        if _is_torch(mask):
+            mask = mask.cpu().numpy()
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.ndim == 2:
+            m = m[None]
+        if m.shape != shape:
+            raise ValueError(f"mask shape {m.shape} != {shape}")
+        _native.check(lib.neo_hip_upols_update_filter_sparse(self._h, _ptr(H), _ptr(m), 0, int(fade_blocks), c, s))
+
+    def update_impulse(self, impulse_response, sparsity=None, normalize: bool = True, fade_blocks: int = 1,
+                       curve: str = "linear", stream: int = 0) -> None:
+        """update_filter from impulse responses [C][L] float32 (host array or CUDA tensor) under a
+        PerceptualSparsity: normalize_impulse (optional), uniform_partition, the mask and the tiles
+        on the device (neo_hip_upols_update_impulse_perceptual), the same handle as
+        update_filter(P, perceptual_mask(P, sparsity)) with P = uniform_partition(normalize_impulse
+        (ir)). Keeps all state. Without a sparsity the call falls through to the dense form, which
+        the library refuses on a sparse handle."""
+        if sparsity is None:
+            return super().update_impulse(impulse_response, normalize, fade_blocks, curve, stream)
+        if not isinstance(sparsity, PerceptualSparsity):
+            raise TypeError("update_impulse on a sparse convolver takes a PerceptualSparsity")
+        c = _fade_curve(curve)
+        lib = _native.load()
+        p = sparsity._c()
+        if _is_torch(impulse_response) and impulse_response.is_cuda:
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != self.channels * t.shape[-1]:
+                raise ValueError("impulse must be a contiguous float32 tensor of one row per channel")
+            _producer_join(t)
+            current = torch.cuda.current_stream(t.device).cuda_stream
+            _native.check(lib.neo_hip_upols_update_impulse_perceptual(self._h, ctypes.c_void_p(t.data_ptr()), t.shape[-1],
+                                                                      int(normalize), ctypes.byref(p), 1, int(fade_blocks), c,
+                                                                      ctypes.c_void_p(stream or current or None)))
+            return
+        if _is_torch(impulse_response):
+            impulse_response = impulse_response.numpy()
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)))
+        if ir.shape[0] != self.channels:
+            raise ValueError("impulse channel count mismatch")
+        _native.check(lib.neo_hip_upols_update_impulse_perceptual(self._h, _ptr(ir), ir.shape[1], int(normalize),
+                                                                  ctypes.byref(p), 0, int(fade_blocks), c,
+                                                                  ctypes.c_void_p(stream or None)))
+
     def sparse_info(self) -> dict:
         """The current filter's kept columns and kept 128-byte tiles over all channels, and the
-        device bytes (tiles, bitmaps, offsets) that stand in for a dense handle's filter buffer."""
+        device bytes (tiles, bitmaps, offsets) that stand in for a dense handle's filter buffer;
+        from an update_filter / update_impulse call on, the filter being faded to."""
         kb, kt, fb = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _native.check(_native.load().neo_hip_upols_sparse_info(self._h, ctypes.byref(kb), ctypes.byref(kt),
                                                                ctypes.byref(fb)))
