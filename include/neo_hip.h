@@ -613,7 +613,16 @@ NEO_HIP_API int neo_hip_upols_group_register(neo_hip_upols_group* g, const void*
  * processFrame's loop. The frame's first call then writes EVERY member's output into its block in
  * place, and a later member's call has nothing left to do. A member called on another buffer is
  * still stepped exactly (its own block step again), but its speculative output was written to its
- * old block: that is the promise the flag makes. */
+ * old block: that is the promise the flag makes.
+ * Under the in-place promise a frame's blocks are consumed at its first call, and a state change in
+ * mid-frame takes effect after them: when set_filter, reset, join, leave or a second call of a member
+ * ends the one-launch mode while members have not made their call of the frame yet, their blocks hold
+ * their outputs already (the inputs are gone, so no member is stepped back), each one's remaining call
+ * of the frame on its block returns at once, and a new filter or a reset of such a member starts with
+ * its next frame (a member that leaves takes its consumed block with it). Called on another buffer
+ * instead, such a member is stepped on it as a NEW block: the owner broke the in-place promise.
+ * Without the flag (plain or STABLE) the inputs are still there: those members are stepped back one
+ * block and a state change applies where it is made. */
 #define NEO_HIP_GROUP_FRAME_INPLACE 2
 NEO_HIP_API int neo_hip_upols_group_register_ex(neo_hip_upols_group* g, const void* ptr, int64_t bytes, int flags);
 NEO_HIP_API int neo_hip_upols_group_unregister(neo_hip_upols_group* g, const void* ptr);

@@ -26,6 +26,13 @@
 //                     for bit). A member called twice before the others (or joining, leaving,
 //                     changing its filter) ends coalescing: the states move back into one-channel
 //                     handles (a speculatively stepped member one block back) before the call.
+//                     Under NEO_HIP_GROUP_FRAME_INPLACE a frame's blocks are consumed at its first
+//                     call (the step wrote every output over its input), and a state change in
+//                     mid-frame takes effect after them: such a split steps no member back, a
+//                     member's remaining call of the frame on its block has nothing left to do, and
+//                     a new filter or a reset starts with the member's next frame. A member called
+//                     on another buffer instead is stepped on it as a NEW block: the owner broke
+//                     the in-place promise (its frame block was already consumed).
 // So every output is the instance's own sequential step; the launch count per frame drops from
 // one per channel to one while the caller keeps the plugin's call pattern. Each handle takes the
 // code-path choices of its own shape (a member alone: one channel, one launch per block; the
@@ -87,6 +94,9 @@ struct member {
     const float* io_prev = nullptr;  // the buffer of the frame before (coalescing needs stable buffers)
     bool pending = false;          // coalesced: stepped by the frame's leader, call not yet seen
     bool seen = false;             // independent: called in the frame being observed
+    bool stepped = false;          // independent, after a split in the middle of a FRAME_INPLACE frame: the
+                                   // leader's step consumed this member's block of the frame and wrote its
+                                   // output there (io_last); its remaining call of the frame finds it done
     int slot = -1;                 // coalesced: channel in the shared handle
 };
 }  // namespace
@@ -301,16 +311,22 @@ int coalesce(group_t* g)
 
 // coalesced -> independent: every live member's state into a one-channel handle of its own; a
 // member the frame's leader stepped ahead of its call goes back to before that step (previous
-// block from the backup, ring row of the step: its own call writes that row again)
+// block from the backup, ring row of the step: its own call writes that row again) -- unless that
+// step wrote the frame's outputs in place (FRAME_INPLACE): the member's input block is gone, so it
+// stays stepped and its remaining call of the frame finds its output in its block (member::stepped).
+// In mid-frame the frame under observation goes on: the members that made their call count as seen.
 int split(group_t* g)
 {
     neo_hip_upols* sh = g->shared;
     NEO_GP_T(ts0);
+    const bool midframe = g->npending > 0;
+    int nseen = 0;
     for (auto& x : g->m) {
         if (!x.live) continue;
         int rc = make_own(g, x);
         if (rc) return rc;
-        const bool back = x.pending;
+        const bool done = x.pending && g->out_inplace;
+        const bool back = x.pending && !done;
         if (x.slot >= 0) {
             if ((rc = copy_channel(x.own, 0, sh, x.slot, back ? g->prev_bak : sh->prev, g->stream))) return rc;
             x.own->wpos = back ? g->step_w : sh->wpos;
@@ -318,9 +334,11 @@ int split(group_t* g)
         }
         neo_hip::lvl_filter_changed(x.own);
         x.own->shape.batch = false;
+        x.seen = midframe && !x.pending;
+        nseen += x.seen;
+        x.stepped = done;
         x.pending = false;
         x.slot = -1;
-        x.seen = false;
     }
     NEO_GP_ADD(9, ts0);
     NEO_GP_T(ts1);
@@ -331,7 +349,7 @@ int split(group_t* g)
     NEO_GP_ADD(11, ts2);
     g->coalesced = false;
     g->npending = 0;
-    g->nseen = 0;
+    g->nseen = nseen;
     g->good_frames = 0;
     ++g->stat_switches;
     return NEO_HIP_OK;
@@ -346,20 +364,27 @@ int call_independent(group_t* g, int i, float* io)
         g->nseen = 0;
         g->good_frames = 0;
     }
-    // the block through the group's own mapped staging, on the group's stream: no per-call
-    // pointer query of the caller's buffer, no per-member stream or staging
-    if (!g->stage_pin) {
-        if (int rc = neo_hip::halloc(reinterpret_cast<void**>(&g->stage_pin), reinterpret_cast<void**>(&g->stage_dev),
-                                     size_t(g->B) * sizeof(float)))
-            return rc;
+    // a member whose block of a FRAME_INPLACE frame was consumed before the split: on that block
+    // this is its call of the frame and the output is there already; on another buffer the owner
+    // broke the in-place promise, and the block it brings is stepped as a new one
+    const bool done = x.stepped && io == x.io_last;
+    x.stepped = false;
+    if (!done) {
+        // the block through the group's own mapped staging, on the group's stream: no per-call
+        // pointer query of the caller's buffer, no per-member stream or staging
+        if (!g->stage_pin) {
+            if (int rc = neo_hip::halloc(reinterpret_cast<void**>(&g->stage_pin), reinterpret_cast<void**>(&g->stage_dev),
+                                         size_t(g->B) * sizeof(float)))
+                return rc;
+        }
+        const size_t bb = size_t(g->B) * sizeof(float);
+        std::memcpy(g->stage_pin, io, bb);
+        int rc = neo_hip_upols_process_device(x.own, g->stage_dev, g->B, g->stage_dev, g->B, g->stream);
+        if (!rc) rc = neo_hip::spin_sync(g->stream);
+        if (!rc) std::memcpy(io, g->stage_pin, bb);
+        if (rc) return rc;
+        ++x.steps;
     }
-    const size_t bb = size_t(g->B) * sizeof(float);
-    std::memcpy(g->stage_pin, io, bb);
-    int rc = neo_hip_upols_process_device(x.own, g->stage_dev, g->B, g->stage_dev, g->B, g->stream);
-    if (!rc) rc = neo_hip::spin_sync(g->stream);
-    if (!rc) std::memcpy(io, g->stage_pin, bb);
-    if (rc) return rc;
-    ++x.steps;
     x.io_prev = x.io_last;
     x.io_last = io;
     x.seen = true;
@@ -584,8 +609,7 @@ NEO_HIP_API int neo_hip_upols_group_join(neo_hip_upols_group* g, int* id)
         g->m[i] = member{};
         return rc;
     }
-    for (auto& y : g->m) y.seen = false;
-    g->nseen = 0;
+    // the frame under observation goes on (it completes once the new member has made its call too)
     g->good_frames = 0;
     *id = int(i);
     return NEO_HIP_OK;
@@ -602,9 +626,14 @@ NEO_HIP_API int neo_hip_upols_group_leave(neo_hip_upols_group* g, int id)
         if (int rc = split(g)) return rc;
     member& x = g->m[size_t(id)];
     if (x.own) neo_hip_upols_destroy(x.own);
+    if (x.seen) --g->nseen;
     x = member{};
-    for (auto& y : g->m) y.seen = false;
-    g->nseen = 0;
+    // the frame under observation goes on among the others; if the member that left was the only
+    // one still to call, it is over (and not counted as a good one: no call completed it)
+    if (g->nseen >= live_count(g)) {
+        for (auto& y : g->m) y.seen = false;
+        g->nseen = 0;
+    }
     g->good_frames = 0;
     return NEO_HIP_OK;
 }
@@ -623,10 +652,7 @@ NEO_HIP_API int neo_hip_upols_group_set_filter(neo_hip_upols_group* g, int id, c
     x.own->shape.batch = false;
     x.filtered = true;
     x.steps = 0;
-    x.seen = false;
-    for (auto& y : g->m) y.seen = false;
-    g->nseen = 0;
-    g->good_frames = 0;
+    g->good_frames = 0;  // the frame under observation goes on: the member's call of it stays made or due
     return NEO_HIP_OK;
 }
 

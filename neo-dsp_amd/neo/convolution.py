@@ -899,7 +899,14 @@ class UpolsGroup:
         calls writes it (neo_hip_upols_group_register_ex, NEO_HIP_GROUP_FRAME_STABLE): members then
         commit without comparing their blocks with a snapshot. in_place (NEO_HIP_GROUP_FRAME_INPLACE,
         implies frame_stable): it also reads each member's block only through that member's call,
-        each member on the same block every frame: the frame's first call writes every output in place."""
+        each member on the same block every frame: the frame's first call writes every output in place.
+        Under the in-place promise a frame's blocks are consumed at its first call, and a state change
+        in mid-frame takes effect after them: after filter(), reset(), join(), leave() or a member's
+        second call in a one-launch frame, a member that has not made its call of the frame yet finds
+        its output in its block (that call returns at once), and its new filter or zero state starts
+        with its next frame; called on another buffer instead it is stepped on that as a new block (the
+        promise is broken). Plain and frame_stable ranges keep their inputs: a change applies where it
+        is made."""
         if not isinstance(buffer, np.ndarray) or not buffer.flags.c_contiguous:
             raise TypeError("register takes a C-contiguous numpy array")
         self._keep = getattr(self, "_keep", {})
