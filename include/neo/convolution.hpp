@@ -3,14 +3,15 @@
 //
 // Same names and semantics as the reference's src/neo/convolution/*:
 //   fdl_index                 fdl_index.hpp:12-41 (host ring bookkeeping)
-//   uniform_partition         uniform_partition.hpp:12-26  -> [C][P][B+1] complex<float>
-//   normalize_impulse         normalize_impulse.hpp:11-33  (bit-exact rounding on the GPU)
+//   uniform_partition         uniform_partition.hpp:12-26  -> [C][P][B+1] complex<float> (complex<double> for a double view)
+//   normalize_impulse         normalize_impulse.hpp:11-33  (bit-exact rounding on the GPU; double views in double)
 //   upols_convolver           dense_convolver.hpp:19-20 + uniform_partitioned_convolver.hpp:13-65
 //   split_upols_convolver     dense_convolver.hpp:38-42 (same math; one device layout)
 //   upola_convolver(_v2)      dense_convolver.hpp:23-28 (overlap_add / overlap_add_convolver)
 // plus the GPU-shaped entry the plugin and CLI loops map onto: upols_multichannel,
 // C channels stepped by one launch pair per block ([C][B] in, [C][P][B+1] filter),
-// and dense_convolve (extra/plugin/src/dsp/DenseConvolution.hpp:39-70).
+// and dense_convolve (extra/plugin/src/dsp/DenseConvolution.hpp:39-70). upols_multichannel64 and
+// std::complex<double> instances of upols_convolver / upola_convolver / split_*: the same in double.
 #pragma once
 
 #include <neo/fft.hpp>
@@ -94,31 +95,55 @@ private:
     return std::size_t(p);
 }
 
-/// uniform_partition.hpp:12-26: impulse [C][L] -> [C][P][B+1] (computed on the GPU)
+namespace detail {
+/// Float = InMat::value_type of the reference's free functions: double for a view of double,
+/// float for everything else (as before double views existed here)
+template<typename V>
+struct view_float {
+    using type = float;
+};
+template<typename V>
+    requires std::same_as<std::remove_cv_t<typename V::value_type>, double>
+struct view_float<V> {
+    using type = double;
+};
+template<typename V>
+using view_float_t = typename view_float<V>::type;
+}  // namespace detail
+
+/// uniform_partition.hpp:12-26: impulse [C][L] -> [C][P][B+1] (computed on the GPU), in the view's
+/// precision: a view of double gives complex<double>, computed in double
 template<typename InMat>
     requires neo::hip::detail::matrix_like<InMat>
 [[nodiscard]] auto uniform_partition(InMat impulse_response, std::size_t block_size)
-    -> neo::hip::array<std::complex<float>, 3>
+    -> neo::hip::array<std::complex<detail::view_float_t<InMat>>, 3>
 {
+    using Float = detail::view_float_t<InMat>;
     auto const C = std::size_t(impulse_response.extent(0)), L = std::size_t(impulse_response.extent(1));
-    std::vector<float> ir(C * L);
+    std::vector<Float> ir(C * L);
     for (std::size_t c = 0; c < C; ++c)
-        for (std::size_t i = 0; i < L; ++i) ir[c * L + i] = float(neo::hip::detail::at(impulse_response, c, i));
+        for (std::size_t i = 0; i < L; ++i) ir[c * L + i] = Float(neo::hip::detail::at(impulse_response, c, i));
     auto const P = num_partitions(L, block_size);
-    neo::hip::array<std::complex<float>, 3> out;
+    neo::hip::array<std::complex<Float>, 3> out;
     out.buf.resize(C * P * (block_size + 1));
     out.ext[0] = C;
     out.ext[1] = P;
     out.ext[2] = block_size + 1;
-    neo::hip::check(neo_hip_uniform_partition(ir.data(), int(C), std::int64_t(L), int(block_size), out.data(), 0,
-                                              neo::hip::detail::default_device()));
+    if constexpr (std::same_as<Float, double>)
+        neo::hip::check(neo_hip_uniform_partition_f64(ir.data(), int(C), std::int64_t(L), int(block_size), out.data(), 0,
+                                                      neo::hip::detail::default_device()));
+    else
+        neo::hip::check(neo_hip_uniform_partition(ir.data(), int(C), std::int64_t(L), int(block_size), out.data(), 0,
+                                                  neo::hip::detail::default_device()));
     return out;
 }
 
-/// normalize_impulse.hpp:11-33 (rank 1: unit energy; rank 2: min factor over channels)
+/// normalize_impulse.hpp:11-33 (rank 1: unit energy; rank 2: min factor over channels), in the
+/// view's precision (a view of double: in double, written back as double)
 template<typename Obj>
 auto normalize_impulse(Obj obj) noexcept -> void
 {
+    using Float = detail::view_float_t<Obj>;
     std::size_t C = 1, L = 0;
     if constexpr (neo::hip::detail::matrix_like<Obj>) {
         C = std::size_t(obj.extent(0));
@@ -127,14 +152,18 @@ auto normalize_impulse(Obj obj) noexcept -> void
         L = std::size_t(obj.extent(0));
     }
     if (C == 0 || L == 0) return;
-    std::vector<float> buf(C * L);
+    std::vector<Float> buf(C * L);
     for (std::size_t c = 0; c < C; ++c)
         for (std::size_t i = 0; i < L; ++i) {
             if constexpr (neo::hip::detail::matrix_like<Obj>) buf[c * L + i] = neo::hip::detail::at(obj, c, i);
             else buf[i] = neo::hip::detail::at(obj, i);
         }
-    neo::hip::check_or_abort(neo_hip_normalize_impulse(buf.data(), int(C), std::int64_t(L), 0,
-                                                       neo::hip::detail::default_device()));
+    if constexpr (std::same_as<Float, double>)
+        neo::hip::check_or_abort(neo_hip_normalize_impulse_f64(buf.data(), int(C), std::int64_t(L), 0,
+                                                               neo::hip::detail::default_device()));
+    else
+        neo::hip::check_or_abort(neo_hip_normalize_impulse(buf.data(), int(C), std::int64_t(L), 0,
+                                                           neo::hip::detail::default_device()));
     for (std::size_t c = 0; c < C; ++c)
         for (std::size_t i = 0; i < L; ++i) {
             if constexpr (neo::hip::detail::matrix_like<Obj>) neo::hip::detail::at(obj, c, i) = buf[c * L + i];
@@ -371,6 +400,84 @@ private:
 };
 
 namespace detail {
+struct upols64_deleter {
+    void operator()(neo_hip_upols64* h) const noexcept { neo_hip_upols64_destroy(h); }
+};
+using upols64_ptr = std::unique_ptr<neo_hip_upols64, upols64_deleter>;
+}  // namespace detail
+
+/// upols_multichannel over double / std::complex<double> (neo_hip_upols64): C independent
+/// upols_convolver<complex<double>> (or upola with method::upola) on one GPU, stepped together, one
+/// launch pair per block. Whole blocks only; no live updates, latency mode, batched or offline passes.
+struct upols_multichannel64 {
+    /// split_workgroups: the workgroups the MAC launch aims for (0: automatic)
+    upols_multichannel64(std::size_t channels, std::size_t block_size, std::size_t partitions,
+                         int device = neo::hip::detail::default_device(), method m = method::upols,
+                         int split_workgroups = 0)
+        : _C{channels}, _B{block_size}, _P{partitions}
+    {
+        if (m != method::upols && m != method::upola)
+            throw std::invalid_argument{"neo_hip: multichannel convolver supports method::upols and method::upola"};
+        neo_hip_upols64* h = nullptr;
+        neo::hip::check(neo_hip_upols64_create(int(channels), int(block_size), int(partitions), device,
+                                               m == method::upola ? 1 : 0, split_workgroups, &h));
+        _h.reset(h);
+    }
+
+    /// filter [C][P][B+1] complex<double>, contiguous host memory; resets state
+    auto filter(std::complex<double> const* partitions) -> void
+    {
+        neo::hip::check(neo_hip_upols64_set_filter(_h.get(), partitions, 0));
+    }
+    /// normalize_impulse (optional) + uniform_partition of ir [C][length] on the GPU, in double
+    auto impulse(double const* ir, std::size_t length, bool normalize = true) -> void
+    {
+        neo::hip::check(neo_hip_upols64_set_impulse(_h.get(), ir, std::int64_t(length), normalize ? 1 : 0, 0));
+    }
+    /// one block for every channel, in place, io [C][B] host memory (synchronous)
+    auto operator()(double* io) noexcept -> void
+    {
+        auto const n = std::int64_t(_B);
+        neo::hip::check_or_abort(neo_hip_upols64_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
+    }
+    /// one block, device pointers, channel c at in + c*ld_in (strides in doubles, even;
+    /// asynchronous on stream)
+    auto process_device(double const* in, std::size_t ld_in, double* out, std::size_t ld_out, void* stream = nullptr) -> void
+    {
+        neo::hip::check(neo_hip_upols64_process_samples(_h.get(), in, std::int64_t(ld_in), out, std::int64_t(ld_out),
+                                                        std::int64_t(_B), 1, stream));
+    }
+    /// num_samples (whole blocks) per channel, in place, io [C][num_samples] host memory (synchronous)
+    auto process(double* io, std::size_t num_samples) noexcept -> void
+    {
+        auto const n = std::int64_t(num_samples);
+        neo::hip::check_or_abort(neo_hip_upols64_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
+    }
+    /// process() that throws std::runtime_error on a refusal or device failure instead of aborting
+    auto process_checked(double* io, std::size_t num_samples) -> void
+    {
+        auto const n = std::int64_t(num_samples);
+        neo::hip::check(neo_hip_upols64_process_samples(_h.get(), io, n, io, n, n, 0, nullptr));
+    }
+    auto reset() -> void { neo::hip::check(neo_hip_upols64_reset(_h.get())); }
+
+    [[nodiscard]] auto channels() const noexcept { return _C; }
+    [[nodiscard]] auto block_size() const noexcept { return _B; }
+    [[nodiscard]] auto partitions() const noexcept { return _P; }
+    /// splits per channel and partitions per split of the MAC launch
+    [[nodiscard]] auto splits() const -> std::pair<int, int>
+    {
+        int s = 0, r = 0;
+        neo::hip::check(neo_hip_upols64_info(_h.get(), &s, &r, nullptr));
+        return {s, r};
+    }
+
+private:
+    std::size_t _C, _B, _P;
+    detail::upols64_ptr _h;
+};
+
+namespace detail {
 struct upols_multi_deleter {
     void operator()(neo_hip_upols_multi* m) const noexcept { neo_hip_upols_multi_destroy(m); }
 };
@@ -453,14 +560,18 @@ private:
     std::unique_ptr<neo_hip_upols_multi, detail::upols_multi_deleter> _h;
 };
 
-/// Single-channel drop-in for upols_convolver<complex<float>> (uniform_partitioned_convolver.hpp:13-65)
+/// Single-channel drop-in for upols_convolver<Complex> (uniform_partitioned_convolver.hpp:13-65)
 /// and, with M = method::upola, upola_convolver: default-constructible; filter([P][B+1])
-/// (re)initializes everything; operator()(block[B]) in place.
+/// (re)initializes everything; operator()(block[B]) in place. Complex = std::complex<float> runs on
+/// upols_multichannel, std::complex<double> on upols_multichannel64 (no latency mode there).
 template<typename Complex, method M = method::upols>
 struct hip_upols_convolver {
-    static_assert(std::same_as<Complex, std::complex<float>>);
+    static_assert(std::same_as<Complex, std::complex<float>> || std::same_as<Complex, std::complex<double>>);
     using value_type = Complex;
+    using real_type = typename Complex::value_type;
     using accumulator_type = neo::hip::array<Complex, 1>;
+    static constexpr bool is_double = std::same_as<real_type, double>;
+    using impl_type = std::conditional_t<is_double, upols_multichannel64, upols_multichannel>;
 
     hip_upols_convolver() = default;
 
@@ -473,20 +584,27 @@ struct hip_upols_convolver {
         for (std::size_t p = 0; p < P; ++p)
             for (std::size_t k = 0; k < bins; ++k) h[p * bins + k] = Complex(neo::hip::detail::at(filter, p, k));
         if (!_impl || _impl->partitions() != P || _impl->block_size() != bins - 1) {
-            _impl = std::make_unique<upols_multichannel>(1, bins - 1, P, neo::hip::detail::default_device(), M);
-            if (_latency) _impl->latency_mode(true, _idle_ms);
+            _impl = std::make_unique<impl_type>(1, bins - 1, P, neo::hip::detail::default_device(), M);
+            if constexpr (!is_double)
+                if (_latency) _impl->latency_mode(true, _idle_ms);
         }
         _impl->filter(h.data());
         _block.resize(bins - 1);
     }
 
     /// latency mode for this instance (upols_multichannel::latency_mode), kept across filter()
-    /// calls; applied at the next filter() when no filter was set yet
+    /// calls; applied at the next filter() when no filter was set yet. The double type has none: throws.
     auto latency_mode(bool on, double idle_ms = 50.0) -> void
     {
-        _latency = on;
-        _idle_ms = idle_ms;
-        if (_impl) _impl->latency_mode(on, idle_ms);
+        if constexpr (is_double) {
+            (void)on;
+            (void)idle_ms;
+            throw std::invalid_argument{"neo_hip: the latency mode is float32 only (std::complex<double> convolvers have none)"};
+        } else {
+            _latency = on;
+            _idle_ms = idle_ms;
+            if (_impl) _impl->latency_mode(on, idle_ms);
+        }
     }
 
     template<typename Vec>
@@ -503,8 +621,8 @@ struct hip_upols_convolver {
     }
 
 private:
-    std::unique_ptr<upols_multichannel> _impl;
-    std::vector<float> _block;
+    std::unique_ptr<impl_type> _impl;
+    std::vector<real_type> _block;
     bool _latency = false;
     double _idle_ms = 50.0;
 };
@@ -1145,6 +1263,28 @@ inline auto dense_convolve(float const* signal, std::size_t channels, std::size_
         std::size_t const t1 = std::min(nb, t0 + chunk), lo = t0 * block_size,
                           hi = std::min(num_samples, t1 * block_size), n = (t1 - t0) * block_size;
         buf.assign(channels * n, 0.0F);
+        for (std::size_t c = 0; c < channels; ++c)
+            std::copy(signal + c * num_samples + lo, signal + c * num_samples + hi, buf.data() + c * n);
+        conv.process(buf.data(), n);
+        for (std::size_t c = 0; c < channels; ++c)
+            std::copy(buf.data() + c * n, buf.data() + c * n + (hi - lo), out + c * num_samples + lo);
+    }
+}
+
+/// the same in double (upols_multichannel64): signal, ir and out of double
+inline auto dense_convolve(double const* signal, std::size_t channels, std::size_t num_samples, double const* ir,
+                           std::size_t ir_length, std::size_t block_size, double* out, method m = method::upols) -> void
+{
+    upols_multichannel64 conv{channels, block_size, num_partitions(ir_length, block_size),
+                              neo::hip::detail::default_device(), m};
+    conv.impulse(ir, ir_length, true);
+    std::size_t const nb = (num_samples + block_size - 1) / block_size;
+    std::size_t const chunk = std::max<std::size_t>(1, (std::size_t(1) << 25) / (channels * block_size));
+    std::vector<double> buf;
+    for (std::size_t t0 = 0; t0 < nb; t0 += chunk) {
+        std::size_t const t1 = std::min(nb, t0 + chunk), lo = t0 * block_size,
+                          hi = std::min(num_samples, t1 * block_size), n = (t1 - t0) * block_size;
+        buf.assign(channels * n, 0.0);
         for (std::size_t c = 0; c < channels; ++c)
             std::copy(signal + c * num_samples + lo, signal + c * num_samples + hi, buf.data() + c * n);
         conv.process(buf.data(), n);

@@ -97,8 +97,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.14.0: crossfaded live filter updates on sparse handles (neo_hip_upols_update_filter_sparse,
  *        neo_hip_upols_update_filter_perceptual, neo_hip_upols_update_impulse_perceptual,
  *        neo_hip_upols_sparse_fade_plan; neo_hip_upols_fade_info and neo_hip_upols_sparse_info follow
- *        a sparse handle's fade). */
-#define NEO_HIP_VERSION 1400 /* 0.14.0 */
+ *        a sparse handle's fade).
+ * 0.15.0: double-precision upols / upola convolvers (neo_hip_upols64_*) and the setup path in double
+ *        (neo_hip_uniform_partition_f64, neo_hip_normalize_impulse_f64). */
+#define NEO_HIP_VERSION 1500 /* 0.15.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -952,6 +954,46 @@ NEO_HIP_API int neo_hip_uniform_partition(const float* ir, int channels, int64_t
                                           int is_device, int device);
 /* in place on ir [C][L]: scale all channels by min_c 1/sqrt(sum ir[c]^2). */
 NEO_HIP_API int neo_hip_normalize_impulse(float* ir, int channels, int64_t length, int is_device, int device);
+
+/* the same in double: ir [C][L] double -> out [C][P][B+1] complex double; in place on ir [C][L]
+ * double. The energy sum runs in a fixed order that depends on L alone (not the reference's
+ * sequential one; the two agree to ~1e-13 relative). */
+NEO_HIP_API int neo_hip_uniform_partition_f64(const double* ir, int channels, int64_t length, int block, void* out,
+                                              int is_device, int device);
+NEO_HIP_API int neo_hip_normalize_impulse_f64(double* ir, int channels, int64_t length, int is_device, int device);
+
+/* -- double-precision UPOLS / UPOLA convolver ----------------------------------
+ * C instances of upols_convolver<complex<double>> (method 0) or upola_convolver<complex<double>>
+ * (method 1): the float handles' semantics per block and bin with Float = double
+ * (uniform_partitioned_convolver.hpp:13-65, overlap_save.hpp:84-112, overlap_add.hpp:76-106), a
+ * handle type of its own. `block` = B a power of two in [16, 4096]. A block is two launches (MAC
+ * over C x splits workgroups, then one workgroup per channel sums the splits' slabs in order and
+ * runs the c2r); equal calls give equal bits. split_workgroups: the workgroups the MAC aims for
+ * (0: automatic, the float plain step's rule). Whole blocks only; no streaming levels, batched
+ * passes, fades, latency mode or groups. Bad arguments return NEO_HIP_EINVAL before any device call. */
+typedef struct neo_hip_upols64 neo_hip_upols64;
+NEO_HIP_API int neo_hip_upols64_create(int channels, int block, int partitions, int device, int method /* 0 upols, 1 upola */,
+                                       int split_workgroups /* 0 auto */, neo_hip_upols64** h);
+NEO_HIP_API int neo_hip_upols64_destroy(neo_hip_upols64* h);
+/* filter [C][P][B+1] complex double (uniform_partition layout), host or device. Resets all state,
+ * as filter() does in the reference. Synchronous. */
+NEO_HIP_API int neo_hip_upols64_set_filter(neo_hip_upols64* h, const void* filter, int is_device);
+/* ir [C][length] double -> (normalize_impulse) -> uniform_partition -> filter, all on the device;
+ * equal bit for bit to the three calls in turn. length must give the handle's partitions. */
+NEO_HIP_API int neo_hip_upols64_set_impulse(neo_hip_upols64* h, const double* ir, int64_t length, int normalize,
+                                            int is_device);
+NEO_HIP_API int neo_hip_upols64_reset(neo_hip_upols64* h);
+/* n = k B samples per channel, channel c at in + c*ld_in / out + c*ld_out (in == out allowed):
+ * k step pairs. Strides in doubles, >= n and even (16-byte rows); device bases 16-byte aligned;
+ * anything else is refused without advancing state. Device memory: asynchronous on `stream`, no
+ * host wait between blocks. Host memory: through pinned staging, synchronous. */
+NEO_HIP_API int neo_hip_upols64_process_samples(neo_hip_upols64* h, const double* in, int64_t ld_in, double* out,
+                                                int64_t ld_out, int64_t num_samples, int is_device, void* stream);
+/* splits per channel, partitions per split (the last split may be shorter), device bytes held */
+NEO_HIP_API int neo_hip_upols64_info(neo_hip_upols64* h, int* splits, int* rows, int64_t* state_bytes);
+/* the same for a shape, host only (no device call) */
+NEO_HIP_API int neo_hip_upols64_plan(int channels, int block, int partitions, int split_workgroups, int* splits,
+                                     int* rows, int64_t* state_bytes);
 
 /* -- one-shot full convolution (extra/python/src/neo/__init__.py:43-48) ----
  * out has n + m - 1 samples; n == 0 or m == 0 is a no-op (empty result).

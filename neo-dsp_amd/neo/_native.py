@@ -214,6 +214,16 @@ SIGNATURES = {
     "neo_hip_num_partitions": (_i, [_i64, _i, ctypes.POINTER(_i64)]),
     "neo_hip_uniform_partition": (_i, [_vp, _i, _i64, _i, _vp, _i, _i]),
     "neo_hip_normalize_impulse": (_i, [_vp, _i, _i64, _i, _i]),
+    "neo_hip_uniform_partition_f64": (_i, [_vp, _i, _i64, _i, _vp, _i, _i]),
+    "neo_hip_normalize_impulse_f64": (_i, [_vp, _i, _i64, _i, _i]),
+    "neo_hip_upols64_create": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "neo_hip_upols64_destroy": (_i, [_vp]),
+    "neo_hip_upols64_set_filter": (_i, [_vp, _vp, _i]),
+    "neo_hip_upols64_set_impulse": (_i, [_vp, _vp, _i64, _i, _i]),
+    "neo_hip_upols64_reset": (_i, [_vp]),
+    "neo_hip_upols64_process_samples": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _vp]),
+    "neo_hip_upols64_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
+    "neo_hip_upols64_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
     "neo_hip_fft_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_direct_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_fft_convolve_f64": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
@@ -223,7 +233,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1400 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1500 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

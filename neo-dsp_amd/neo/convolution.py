@@ -12,6 +12,8 @@ Python; extra/python/src/main.cpp:227-234 only lists the `upols` method enum):
   - upola_convolver_v2     dense_convolver.hpp:28 (overlap_add_convolver.hpp:20-136,
                            sub-block input)
   - dense_convolve         extra/plugin/src/dsp/DenseConvolution.hpp:39-70
+  - UpolsConvolver64       upols_convolver / upola_convolver of complex<double> (dtype=np.float64 on
+                           uniform_partition, normalize_impulse, dense_convolve and the two classes)
   - sparse_upols_convolver / sparse_upola_convolver
                            src/neo/convolution/sparse_convolver.hpp:12-17 (sparse_filter.hpp:25-45;
                            kept in 128-byte tiles of 16 bins here, include/neo_hip.h)
@@ -75,6 +77,8 @@ __all__ = [
     "fft_convolve",
     "direct_convolve",
     "convolve",
+    "UpolsConvolver64",
+    "upols64_plan",
 ]
 
 
@@ -204,9 +208,41 @@ def memory_trim(device: int = 0) -> None:
     _native.check(_native.load().neo_hip_memory_trim(device))
 
 
-def uniform_partition(impulse_response, block_size: int, device: int = 0):
+def _f64(dtype) -> bool:
+    """The dtype keyword of the float32 / float64 entry points: True for float64."""
+    dt = np.dtype(dtype)
+    if dt == np.float32:
+        return False
+    if dt == np.float64:
+        return True
+    raise TypeError(f"dtype must be np.float32 or np.float64, got {dtype!r}")
+
+
+def uniform_partition(impulse_response, block_size: int, device: int = 0, *, dtype=np.float32):
     """[C][L] float32 -> [C][P][B+1] complex64: rfft_2B of each zero-padded B-sample partition.
-    A CUDA tensor gives a CUDA tensor on its device (no host copies)."""
+    A CUDA tensor gives a CUDA tensor on its device (no host copies). dtype=np.float64: computed
+    in double on the device, [C][L] float64 -> [C][P][B+1] complex128."""
+    if _f64(dtype):
+        lib = _native.load()
+        if _is_torch(impulse_response) and impulse_response.is_cuda:
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float64 or not t.is_contiguous():
+                raise TypeError("uniform_partition(dtype=float64) takes a contiguous float64 tensor")
+            C, L = (1, t.shape[0]) if t.dim() == 1 else tuple(t.shape)
+            P = num_partitions(L, block_size)
+            out = torch.empty((C, P, block_size + 1), dtype=torch.complex128, device=t.device)
+            _producer_join(t)
+            _native.check(lib.neo_hip_uniform_partition_f64(ctypes.c_void_p(t.data_ptr()), C, L, int(block_size),
+                                                            ctypes.c_void_p(out.data_ptr()), 1, t.device.index or 0))
+            return out
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float64)))
+        C, L = ir.shape
+        P = num_partitions(L, block_size)
+        out = np.empty((C, P, block_size + 1), dtype=np.complex128)
+        _native.check(lib.neo_hip_uniform_partition_f64(_ptr(ir), C, L, int(block_size), _ptr(out), 0, int(device)))
+        return out
     if _is_torch(impulse_response) and impulse_response.is_cuda:
         import torch
 
@@ -228,9 +264,29 @@ def uniform_partition(impulse_response, block_size: int, device: int = 0):
     return out
 
 
-def normalize_impulse(impulse_response, device: int = 0):
+def normalize_impulse(impulse_response, device: int = 0, *, dtype=np.float32):
     """In place: scale every channel by min_c 1/sqrt(sum(ir[c]^2)), rounded exactly like the
-    reference's sequential float sum. Accepts a float32 ndarray (rank 1 or 2) or CUDA tensor."""
+    reference's sequential float sum. Accepts a float32 ndarray (rank 1 or 2) or CUDA tensor.
+    dtype=np.float64: a float64 ndarray or CUDA tensor, in double (the energy summed in a fixed
+    order, not the reference's sequential one: the two agree to ~1e-13)."""
+    if _f64(dtype):
+        lib = _native.load()
+        if _is_torch(impulse_response):
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+                raise TypeError("normalize_impulse(dtype=float64) works in place on a contiguous float64 CUDA tensor")
+            C, L = (1, t.shape[0]) if t.dim() == 1 else tuple(t.shape)
+            _producer_join(t)
+            _native.check(lib.neo_hip_normalize_impulse_f64(ctypes.c_void_p(t.data_ptr()), C, L, 1, t.device.index or 0))
+            return t
+        a = impulse_response
+        if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
+            raise TypeError("normalize_impulse(dtype=float64) works in place on a C-contiguous float64 array")
+        C, L = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        _native.check(lib.neo_hip_normalize_impulse_f64(_ptr(a), C, L, 0, int(device)))
+        return a
     if _is_torch(impulse_response):
         t = impulse_response
         C, L = (1, t.shape[0]) if t.dim() == 1 else tuple(t.shape)
@@ -607,6 +663,129 @@ class UpolsConvolver:
             pass
 
 
+class UpolsConvolver64:
+    """C independent double-precision UPOLS / UPOLA convolvers stepped together (neo_hip_upols64:
+    upols_convolver<complex<double>> / upola_convolver<complex<double>>), one launch pair per block.
+
+    State lives in HBM in complex128 / float64: filter [C][P][B] and FDL [C][P][B] (packed bins),
+    previous block or overlap tail [C][B]. Whole blocks, in place, zero latency. `split_workgroups`
+    (0: automatic) is the number of workgroups the MAC launch aims for. No streaming levels, batched
+    passes, live updates, latency mode or groups: the float32 UpolsConvolver has those."""
+
+    def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
+                 split_workgroups: int = 0):
+        methods = {"upols": 0, "upola": 1}
+        if method not in methods:
+            raise ValueError(f"method must be 'upols' or 'upola', got {method!r}")
+        h = ctypes.c_void_p()
+        _native.check(_native.load().neo_hip_upols64_create(int(channels), int(block_size), int(partitions), int(device),
+                                                            methods[method], int(split_workgroups), ctypes.byref(h)))
+        self._h = h
+        self.channels, self.block_size, self.partitions, self.device = channels, block_size, partitions, device
+        self.method = method
+
+    def filter(self, partitions) -> None:
+        """[C][P][B+1] complex128 (host array or CUDA tensor); resets FDL, window and write position."""
+        shape = (self.channels, self.partitions, self.block_size + 1)
+        if _is_torch(partitions):
+            import torch
+
+            t = partitions
+            if t.dtype != torch.complex128 or not t.is_contiguous() or not t.is_cuda or t.numel() != int(np.prod(shape)):
+                raise ValueError(f"filter must be a contiguous complex128 CUDA tensor of {shape}")
+            _producer_join(t)
+            _native.check(_native.load().neo_hip_upols64_set_filter(self._h, ctypes.c_void_p(t.data_ptr()), 1))
+            return
+        H = np.ascontiguousarray(partitions, dtype=np.complex128)
+        if H.ndim == 2:
+            H = H[None]
+        if H.shape != shape:
+            raise ValueError(f"filter shape {H.shape} != {shape}")
+        _native.check(_native.load().neo_hip_upols64_set_filter(self._h, _ptr(H), 0))
+
+    def set_impulse(self, impulse_response, normalize: bool = True) -> None:
+        """normalize_impulse (optional) + uniform_partition in double straight into the device filter;
+        [C][L] float64 (host array or CUDA tensor, left as it is)."""
+        if _is_torch(impulse_response):
+            import torch
+
+            t = impulse_response
+            if t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda or t.numel() != self.channels * t.shape[-1]:
+                raise ValueError("impulse must be a contiguous float64 CUDA tensor of one row per channel")
+            _producer_join(t)
+            _native.check(_native.load().neo_hip_upols64_set_impulse(self._h, ctypes.c_void_p(t.data_ptr()), t.shape[-1],
+                                                                     int(normalize), 1))
+            return
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float64)))
+        if ir.shape[0] != self.channels:
+            raise ValueError("impulse channel count mismatch")
+        _native.check(_native.load().neo_hip_upols64_set_impulse(self._h, _ptr(ir), ir.shape[1], int(normalize), 0))
+
+    def reset(self) -> None:
+        _native.check(_native.load().neo_hip_upols64_reset(self._h))
+
+    def process(self, samples, stream: int = 0):
+        """Whole blocks per channel, in place: [C][k * block_size] float64 ndarray or CUDA tensor (a
+        tensor: asynchronous on torch's current stream, or `stream`)."""
+        lib = _native.load()
+        if _is_torch(samples):
+            import torch
+
+            if samples.dtype != torch.float64 or not samples.is_contiguous() or not samples.is_cuda:
+                raise TypeError("samples must be a contiguous float64 CUDA tensor")
+            n = samples.shape[-1]
+            if samples.numel() != self.channels * n:
+                raise ValueError("samples must be [channels][n]")
+            s = stream or torch.cuda.current_stream(samples.device).cuda_stream
+            p = ctypes.c_void_p(samples.data_ptr())
+            _native.check(lib.neo_hip_upols64_process_samples(self._h, p, n, p, n, n, 1, ctypes.c_void_p(s)))
+            return samples
+        if not (isinstance(samples, np.ndarray) and samples.dtype == np.float64 and samples.flags.c_contiguous):
+            raise TypeError("samples must be a C-contiguous float64 array")
+        n = samples.shape[-1] if samples.ndim else 0
+        if samples.size != self.channels * n:
+            raise ValueError("samples must be [channels][n]")
+        _native.check(lib.neo_hip_upols64_process_samples(self._h, _ptr(samples), n, _ptr(samples), n, n, 0, None))
+        return samples
+
+    __call__ = process
+
+    def process_device(self, in_ptr: int, ld_in: int, out_ptr: int, ld_out: int, n: int | None = None,
+                       stream: int = 0, is_device: bool = True) -> None:
+        """n samples (default: one block) of every channel, channel c at in_ptr + 8 c ld_in bytes and
+        out_ptr + 8 c ld_out (strides in doubles, even, >= n; in_ptr == out_ptr allowed)."""
+        n = self.block_size if n is None else n
+        _native.check(_native.load().neo_hip_upols64_process_samples(self._h, ctypes.c_void_p(in_ptr), int(ld_in),
+                                                                     ctypes.c_void_p(out_ptr), int(ld_out), int(n),
+                                                                     int(bool(is_device)), ctypes.c_void_p(stream or None)))
+
+    def info(self) -> dict:
+        """splits per channel, partitions per split (rows; the last split may be shorter), device bytes."""
+        s, r, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols64_info(self._h, ctypes.byref(s), ctypes.byref(r), ctypes.byref(b)))
+        return {"splits": s.value, "rows": r.value, "state_bytes": b.value}
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            _native.check(_native.load().neo_hip_upols64_destroy(self._h))
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def upols64_plan(channels: int, block_size: int, partitions: int, split_workgroups: int = 0) -> dict:
+    """UpolsConvolver64.info() for a shape, without a device (neo_hip_upols64_plan)."""
+    s, r, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+    _native.check(_native.load().neo_hip_upols64_plan(int(channels), int(block_size), int(partitions),
+                                                      int(split_workgroups), ctypes.byref(s), ctypes.byref(r),
+                                                      ctypes.byref(b)))
+    return {"splits": s.value, "rows": r.value, "state_bytes": b.value}
+
+
 class UpolsMultiConvolver:
     """C channels sharded over several devices of one node (neo_hip_upols_multi_*): shard i
     = channels [C i / n, C (i + 1) / n) on devices[i] (a device may repeat), one handle and
@@ -950,24 +1129,39 @@ class upols_convolver:
 
     _method = "upols"
 
-    def __init__(self, device: int = 0):
+    def __init__(self, device: int = 0, *, dtype=np.float32):
+        """dtype=np.float64: upols_convolver<complex<double>> (complex128 filter, float64 blocks)."""
         self._impl = None
         self._device = device
+        self._f64 = _f64(dtype)
+        if self._f64 and self._method == "upola_v2":
+            raise TypeError("upola_convolver_v2 is float32 only")
 
     def filter(self, filt) -> None:
-        H = np.ascontiguousarray(filt, dtype=np.complex64)
+        H = np.ascontiguousarray(filt, dtype=np.complex128 if self._f64 else np.complex64)
         if H.ndim != 2:
             raise ValueError("filter must be [P][B+1]")
         P, bins = H.shape
         impl = self._impl
         if impl is None or (impl.partitions, impl.block_size) != (P, bins - 1):
-            impl = UpolsConvolver(1, bins - 1, P, self._device, method=self._method)
+            make = UpolsConvolver64 if self._f64 else UpolsConvolver
+            impl = make(1, bins - 1, P, self._device, method=self._method)
         impl.filter(H[None])
         self._impl = impl
 
     def __call__(self, block):
         if self._impl is None:
             raise RuntimeError("filter() must be called first")
+        if self._f64:
+            if _is_torch(block):
+                self._impl.process(block.view(1, -1))
+                return block
+            if not (isinstance(block, np.ndarray) and block.dtype == np.float64 and block.flags.c_contiguous):
+                raise TypeError("block must be a C-contiguous float64 array")
+            if block.size != self._impl.block_size:
+                raise ValueError("block must hold block_size samples")
+            self._impl.process(block.reshape(1, -1))  # a view: processed in place
+            return block
         return self._impl(block)
 
 
@@ -1001,10 +1195,35 @@ class upola_convolver_v2(upols_convolver):
 
 
 def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, method: str = "upols",
-                   options: dict | None = None) -> np.ndarray:
+                   options: dict | None = None, *, dtype=np.float32) -> np.ndarray:
     """dense_convolve<upols_convolver | upola_convolver> (DenseConvolution.hpp:39-70): normalize
     the IR matrix, partition it, run every block (tail zero-padded), output truncated to N.
-    `options`: UpolsConvolver code-path choices (same results)."""
+    `options`: UpolsConvolver code-path choices (same results). dtype=np.float64: the whole chain in
+    double (UpolsConvolver64; of `options` it reads split_workgroups alone), float64 out."""
+    if _f64(dtype):
+        sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float64)))
+        ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float64)))
+        C, N = sig.shape
+        if ir.shape[0] != C:
+            raise ValueError("signal and impulse response channel counts differ")
+        for k in options or {}:
+            if k not in UpolsConvolver.OPTION_DEFAULTS:
+                raise ValueError(f"unknown convolver option {k!r}")
+        conv = UpolsConvolver64(C, block_size, num_partitions(ir.shape[1], block_size), device, method=method,
+                                split_workgroups=int((options or {}).get("split_workgroups", 0)))
+        conv.set_impulse(ir, normalize=True)
+        nb = -(-N // block_size)
+        chunk = max(1, (1 << 25) // (C * block_size))  # <= 2^25 doubles per upload
+        out = np.empty_like(sig)
+        for t0 in range(0, nb, chunk):
+            t1 = min(nb, t0 + chunk)
+            lo, hi = t0 * block_size, min(N, t1 * block_size)
+            buf = np.zeros((C, (t1 - t0) * block_size), dtype=np.float64)
+            buf[:, : hi - lo] = sig[:, lo:hi]
+            conv.process(buf)
+            out[:, lo:hi] = buf[:, : hi - lo]
+        conv.close()
+        return out
     sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float32)))
     ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float32)))
     C, N = sig.shape
