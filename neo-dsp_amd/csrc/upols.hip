@@ -167,13 +167,9 @@ int plain_persist_launch(upols_t* h, const persist_ctl& ctl, int64_t ld_in, int6
     pa.pc = h->shape.pc;
     const unsigned grid = unsigned(h->C) * unsigned(h->shape.S);
     bool room = false;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(h->B, room = persist_room(h, reinterpret_cast<const void*>(&k_plain_persist<BB, true>), int(grid));
-                           if (room) hipLaunchKernelGGL((k_plain_persist<BB, true>), dim3(grid), dim3(256), 0, h->ps_stream, pa))
-    } else {
-        NEO_UPOLS_DISPATCH(h->B, room = persist_room(h, reinterpret_cast<const void*>(&k_plain_persist<BB, false>), int(grid));
-                           if (room) hipLaunchKernelGGL((k_plain_persist<BB, false>), dim3(grid), dim3(256), 0, h->ps_stream, pa))
-    }
+    NEO_UPOLS_DISPATCH_OLA(h->B, h->ola,
+                           room = persist_room(h, reinterpret_cast<const void*>(&k_plain_persist<BB, OL>), int(grid));
+                           if (room) hipLaunchKernelGGL((k_plain_persist<BB, OL>), dim3(grid), dim3(256), 0, h->ps_stream, pa))
     if (!room) return NEO_HIP_OK;
     *launched = true;
     NEO_HIP_LAUNCH_CHECK();
@@ -433,13 +429,8 @@ int neo_hip::launch_finish(upols_t* h, float* out, int64_t ld_out, hipStream_t s
 int neo_hip::launch_finish_slabs(int C, int B, int S, bool ola, const cf* part, float* out, int64_t ld_out, float* ovl,
                                  const cf* tw, hipStream_t s)
 {
-    if (ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_upols_finish<BB, true>), dim3(unsigned(C)), dim3(256), 0, s, part,
-                                                 out, ld_out, ovl, tw, S))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_upols_finish<BB, false>), dim3(unsigned(C)), dim3(256), 0, s, part,
-                                                 out, ld_out, ovl, tw, S))
-    }
+    NEO_UPOLS_DISPATCH_OLA(B, ola, hipLaunchKernelGGL((k_upols_finish<BB, OL>), dim3(unsigned(C)), dim3(256), 0, s, part, out,
+                                                      ld_out, ovl, tw, S))
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }

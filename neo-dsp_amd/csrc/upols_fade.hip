@@ -162,15 +162,9 @@ int launch_upols_fade_mac(const upols_t* h, const cf* HA, const cf* HB, const fl
 {
     const unsigned grid = unsigned(h->C) * unsigned(S);
     const upols_shape& sh = h->shape;
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_fade_step<BB, true>), dim3(grid), dim3(256), 0, s, in, ld_in,
-                                                    h->prev, HA, HB, h->fdl, h->part_f, h->tw, h->P, h->ring, S, rows, w,
-                                                    sh.cstride, sh.pstride, int(prime)))
-    } else {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_fade_step<BB, false>), dim3(grid), dim3(256), 0, s, in, ld_in,
-                                                    h->prev, HA, HB, h->fdl, h->part_f, h->tw, h->P, h->ring, S, rows, w,
-                                                    sh.cstride, sh.pstride, int(prime)))
-    }
+    NEO_UPOLS_DISPATCH_OLA(h->B, h->ola, hipLaunchKernelGGL((k_upols_fade_step<BB, OL>), dim3(grid), dim3(256), 0, s, in, ld_in,
+                                                            h->prev, HA, HB, h->fdl, h->part_f, h->tw, h->P, h->ring, S, rows,
+                                                            w, sh.cstride, sh.pstride, int(prime)))
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }

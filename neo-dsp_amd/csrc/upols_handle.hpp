@@ -273,18 +273,33 @@ inline int note_stream(upols_t* h, hipStream_t s) { return h->used.note(s); }
 // after work on the null stream (a device-resident filter or impulse produced there)
 int setup_join(upols_t* h, bool device_input = false);
 
-#define NEO_UPOLS_DISPATCH(B_, BODY) \
-    switch (B_) {                    \
-        case 16: { constexpr int BB = 16; BODY; break; }     \
-        case 32: { constexpr int BB = 32; BODY; break; }     \
-        case 64: { constexpr int BB = 64; BODY; break; }     \
-        case 128: { constexpr int BB = 128; BODY; break; }   \
-        case 256: { constexpr int BB = 256; BODY; break; }   \
-        case 512: { constexpr int BB = 512; BODY; break; }   \
-        case 1024: { constexpr int BB = 1024; BODY; break; } \
-        case 2048: { constexpr int BB = 2048; BODY; break; } \
-        case 4096: { constexpr int BB = 4096; BODY; break; } \
+// The body is variadic on purpose. NEO_UPOLS_DISPATCH_OLA hands its BODY on to this macro, and a macro
+// argument is expanded before it is handed on: a hipLaunchKernelGGL(...) in it has by then become
+// kernel<<<grid, block, shmem, stream>>>(args), whose commas inside <<< >>> no parenthesis protects.
+// A single named parameter would take them for argument separators.
+#define NEO_UPOLS_DISPATCH(B_, ...) \
+    switch (B_) {                   \
+        case 16: { constexpr int BB = 16; __VA_ARGS__; break; }     \
+        case 32: { constexpr int BB = 32; __VA_ARGS__; break; }     \
+        case 64: { constexpr int BB = 64; __VA_ARGS__; break; }     \
+        case 128: { constexpr int BB = 128; __VA_ARGS__; break; }   \
+        case 256: { constexpr int BB = 256; __VA_ARGS__; break; }   \
+        case 512: { constexpr int BB = 512; __VA_ARGS__; break; }   \
+        case 1024: { constexpr int BB = 1024; __VA_ARGS__; break; } \
+        case 2048: { constexpr int BB = 2048; __VA_ARGS__; break; } \
+        case 4096: { constexpr int BB = 4096; __VA_ARGS__; break; } \
         default: return fail(NEO_HIP_EINVAL, "unsupported block size %d", B_); \
+    }
+// the same for a kernel with an overlap-add build: BODY also sees a constexpr bool OL (= OLA_)
+#define NEO_UPOLS_DISPATCH_OLA(B_, OLA_, BODY) \
+    {                                          \
+        if (OLA_) {                            \
+            constexpr bool OL = true;          \
+            NEO_UPOLS_DISPATCH(B_, BODY)       \
+        } else {                               \
+            constexpr bool OL = false;         \
+            NEO_UPOLS_DISPATCH(B_, BODY)       \
+        }                                      \
     }
 
 inline int64_t partitions_for(int64_t L, int B)

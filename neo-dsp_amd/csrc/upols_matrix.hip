@@ -486,11 +486,8 @@ int matrix_row(const matrix_t* m, int d) { return (m->wpos + d + m->ring) % m->r
 // the window launch of one block: every read of `in` (k_matrix_window)
 int matrix_window(matrix_t* m, const float* in, int64_t ld_in, hipStream_t s)
 {
-#define NEO_MATRIX_WINDOW(OL)                                                                                          \
-    NEO_UPOLS_DISPATCH(m->B, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s, in, \
-                                                ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
-    if (m->ola) NEO_MATRIX_WINDOW(true) else NEO_MATRIX_WINDOW(false)
-#undef NEO_MATRIX_WINDOW
+    NEO_UPOLS_DISPATCH_OLA(m->B, m->ola, hipLaunchKernelGGL((k_matrix_window<BB, OL>), dim3(unsigned(m->I)), dim3(256), 0, s,
+                                                            in, ld_in, m->prev, m->fdl, m->tw, m->ring, m->wpos))
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }
@@ -513,21 +510,17 @@ int matrix_step_launch(matrix_t* m, const matrix_plan& p, const cf* H, cf* part,
                        float* out, int64_t ld_out, hipStream_t s)
 {
     const unsigned grid = unsigned(p.ntiles) * unsigned(p.S);
-#define NEO_MATRIX_STEP(OT_, FU, OL)                                                                              \
+#define NEO_MATRIX_STEP(OT_, FU)                                                                                     \
     hipLaunchKernelGGL((k_matrix_step<BB, OT_, FU, OL>), dim3(grid), dim3(256), 0, s, out, ld_out, m->ovl, H, m->fdl, \
                        part, arrivals, m->tw, tab, p.ntiles, m->I, P, m->ring, p.S, m->wpos)
-#define NEO_MATRIX_STEP_T(FU, OL)                                                              \
-    NEO_UPOLS_DISPATCH(m->B, {                                                                 \
-        constexpr int CAP = matrix_max_tile(BB);                                               \
-        if (CAP >= 4 && p.OT == 4) NEO_MATRIX_STEP((CAP >= 4 ? 4 : 1), FU, OL);                \
-        else if (CAP >= 2 && p.OT == 2) NEO_MATRIX_STEP((CAP >= 2 ? 2 : 1), FU, OL);           \
-        else NEO_MATRIX_STEP(1, FU, OL);                                                       \
+#define NEO_MATRIX_STEP_T(FU)                                                          \
+    NEO_UPOLS_DISPATCH_OLA(m->B, m->ola, {                                             \
+        constexpr int CAP = matrix_max_tile(BB);                                       \
+        if (CAP >= 4 && p.OT == 4) NEO_MATRIX_STEP((CAP >= 4 ? 4 : 1), FU);            \
+        else if (CAP >= 2 && p.OT == 2) NEO_MATRIX_STEP((CAP >= 2 ? 2 : 1), FU);       \
+        else NEO_MATRIX_STEP(1, FU);                                                   \
     })
-    if (p.fused) {
-        if (m->ola) NEO_MATRIX_STEP_T(true, true) else NEO_MATRIX_STEP_T(true, false)
-    } else {
-        if (m->ola) NEO_MATRIX_STEP_T(false, true) else NEO_MATRIX_STEP_T(false, false)
-    }
+    if (p.fused) NEO_MATRIX_STEP_T(true) else NEO_MATRIX_STEP_T(false)
 #undef NEO_MATRIX_STEP_T
 #undef NEO_MATRIX_STEP
     NEO_HIP_LAUNCH_CHECK();

@@ -155,13 +155,8 @@ int launch_matrix_lvl_finish(int O, int B, bool ola, const cf* head, int Sh, con
                              int64_t ld_out, float* ovl, const cf* tw, hipStream_t s)
 {
     if (lv.n < 0 || lv.n > kMatrixMaxLevels || Sh < 1) return fail(NEO_HIP_EINVAL, "matrix levels: %d levels, %d head slabs", lv.n, Sh);
-    if (ola) {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_matrix_lvl_finish<BB, true>), dim3(unsigned(O)), dim3(256), 0, s, head, Sh,
-                                                 lv, out, ld_out, ovl, tw))
-    } else {
-        NEO_UPOLS_DISPATCH(B, hipLaunchKernelGGL((k_matrix_lvl_finish<BB, false>), dim3(unsigned(O)), dim3(256), 0, s, head,
-                                                 Sh, lv, out, ld_out, ovl, tw))
-    }
+    NEO_UPOLS_DISPATCH_OLA(B, ola, hipLaunchKernelGGL((k_matrix_lvl_finish<BB, OL>), dim3(unsigned(O)), dim3(256), 0, s, head, Sh,
+                                                      lv, out, ld_out, ovl, tw))
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }

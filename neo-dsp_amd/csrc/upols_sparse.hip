@@ -345,17 +345,14 @@ int64_t sparse_spare_bytes(const upols_t* h)
 int launch_sparse_mac(upols_t* h, const float* in, int64_t ld_in, float* out, int64_t ld_out, hipStream_t s)
 {
     const unsigned grid = unsigned(h->C) * unsigned(h->shape.S);
-#define NEO_SPARSE_STEP(FU, OL)                                                                                       \
-    NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_sparse_step<BB, FU, OL>), dim3(grid), dim3(256), 0, s, in, ld_in, \
-                                                out, ld_out, h->prev, h->sp_bits, h->sp_off, h->sp_base,                 \
-                                                reinterpret_cast<const float4*>(h->sp_val), h->fdl, h->part,            \
-                                                h->arrivals, h->tw, h->P, h->ring, h->shape.S, h->shape.rows, h->wpos,  \
-                                                h->shape.cstride, h->shape.pstride, h->shape.pc))
-    if (h->shape.fused) {
-        if (h->ola) NEO_SPARSE_STEP(true, true) else NEO_SPARSE_STEP(true, false)
-    } else {
-        if (h->ola) NEO_SPARSE_STEP(false, true) else NEO_SPARSE_STEP(false, false)
-    }
+#define NEO_SPARSE_STEP(FU)                                                                                             \
+    NEO_UPOLS_DISPATCH_OLA(h->B, h->ola,                                                                                \
+                           hipLaunchKernelGGL((k_upols_sparse_step<BB, FU, OL>), dim3(grid), dim3(256), 0, s, in, ld_in, \
+                                              out, ld_out, h->prev, h->sp_bits, h->sp_off, h->sp_base,                  \
+                                              reinterpret_cast<const float4*>(h->sp_val), h->fdl, h->part, h->arrivals, \
+                                              h->tw, h->P, h->ring, h->shape.S, h->shape.rows, h->wpos,                 \
+                                              h->shape.cstride, h->shape.pstride, h->shape.pc))
+    if (h->shape.fused) NEO_SPARSE_STEP(true) else NEO_SPARSE_STEP(false)
 #undef NEO_SPARSE_STEP
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;

@@ -246,15 +246,9 @@ int launch_sparse_fade_mac(const upols_t* h, const sparse_bank& a, const sparse_
     const upols_shape& sh = h->shape;
     const sfade_bank ba{a.bits, a.off, a.base, reinterpret_cast<const float4*>(a.val)};
     const sfade_bank bb{b.bits, b.off, b.base, reinterpret_cast<const float4*>(b.val)};
-    if (h->ola) {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_sparse_fade_step<BB, true>), dim3(grid), dim3(256), 0, s, in,
-                                                    ld_in, h->prev, ba, bb, h->fdl, h->part_f, h->tw, h->P, h->ring, S, rows,
-                                                    w, sh.cstride, sh.pstride, int(prime)))
-    } else {
-        NEO_UPOLS_DISPATCH(h->B, hipLaunchKernelGGL((k_upols_sparse_fade_step<BB, false>), dim3(grid), dim3(256), 0, s, in,
-                                                    ld_in, h->prev, ba, bb, h->fdl, h->part_f, h->tw, h->P, h->ring, S, rows,
-                                                    w, sh.cstride, sh.pstride, int(prime)))
-    }
+    NEO_UPOLS_DISPATCH_OLA(h->B, h->ola, hipLaunchKernelGGL((k_upols_sparse_fade_step<BB, OL>), dim3(grid), dim3(256), 0, s,
+                                                            in, ld_in, h->prev, ba, bb, h->fdl, h->part_f, h->tw, h->P, h->ring,
+                                                            S, rows, w, sh.cstride, sh.pstride, int(prime)))
     NEO_HIP_LAUNCH_CHECK();
     return NEO_HIP_OK;
 }
