@@ -408,7 +408,8 @@ using upols64_ptr = std::unique_ptr<neo_hip_upols64, upols64_deleter>;
 
 /// upols_multichannel over double / std::complex<double> (neo_hip_upols64): C independent
 /// upols_convolver<complex<double>> (or upola with method::upola) on one GPU, stepped together, one
-/// launch pair per block. Whole blocks only; no live updates, latency mode, batched or offline passes.
+/// launch pair per block. Whole blocks only; no live updates, latency mode or offline windows.
+/// batch(true) turns batched passes on for calls of many blocks.
 struct upols_multichannel64 {
     /// split_workgroups: the workgroups the MAC launch aims for (0: automatic)
     upols_multichannel64(std::size_t channels, std::size_t block_size, std::size_t partitions,
@@ -470,6 +471,22 @@ struct upols_multichannel64 {
         int s = 0, r = 0;
         neo::hip::check(neo_hip_upols64_info(_h.get(), &s, &r, nullptr));
         return {s, r};
+    }
+
+    /// what batch_info() reports
+    struct batch_report {
+        int blocks_per_pass;      ///< 1 while batching is off
+        int splits;               ///< splits per channel of the pass's MAC
+        std::int64_t extra_bytes; ///< device bytes that batching holds
+    };
+    /// batched passes on or off: a process call of q T + r blocks then runs q passes of T blocks
+    /// and r plain steps. State stays as it is, so it may come between any two process calls.
+    auto batch(bool enable) -> void { neo::hip::check(neo_hip_upols64_set_batch(_h.get(), enable ? 1 : 0)); }
+    [[nodiscard]] auto batch_info() const -> batch_report
+    {
+        batch_report r{};
+        neo::hip::check(neo_hip_upols64_batch_info(_h.get(), &r.blocks_per_pass, &r.splits, &r.extra_bytes));
+        return r;
     }
 
 private:

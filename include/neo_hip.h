@@ -99,8 +99,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  *        neo_hip_upols_sparse_fade_plan; neo_hip_upols_fade_info and neo_hip_upols_sparse_info follow
  *        a sparse handle's fade).
  * 0.15.0: double-precision upols / upola convolvers (neo_hip_upols64_*) and the setup path in double
- *        (neo_hip_uniform_partition_f64, neo_hip_normalize_impulse_f64). */
-#define NEO_HIP_VERSION 1500 /* 0.15.0 */
+ *        (neo_hip_uniform_partition_f64, neo_hip_normalize_impulse_f64).
+ * 0.16.0: batched passes on double-precision handles (neo_hip_upols64_set_batch,
+ *        neo_hip_upols64_batch_info, neo_hip_upols64_batch_plan). */
+#define NEO_HIP_VERSION 1600 /* 0.16.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -969,8 +971,15 @@ NEO_HIP_API int neo_hip_normalize_impulse_f64(double* ir, int channels, int64_t 
  * handle type of its own. `block` = B a power of two in [16, 4096]. A block is two launches (MAC
  * over C x splits workgroups, then one workgroup per channel sums the splits' slabs in order and
  * runs the c2r); equal calls give equal bits. split_workgroups: the workgroups the MAC aims for
- * (0: automatic, the float plain step's rule). Whole blocks only; no streaming levels, batched
- * passes, fades, latency mode or groups. Bad arguments return NEO_HIP_EINVAL before any device call. */
+ * (0: automatic, the float plain step's rule). Whole blocks only; no streaming levels, fades,
+ * latency mode or groups. Bad arguments return NEO_HIP_EINVAL before any device call.
+ * Batched passes (neo_hip_upols64_set_batch, off by default) are for calls of many blocks, as in
+ * offline work: T consecutive blocks of every channel share one read of the filter and the delay
+ * line. A pass is three launches, four for overlap-add: the T window transforms into scratch rows;
+ * the MAC with T accumulators and a sliding window of T delay-line rows per bin; the slab sums and
+ * c2r of the T blocks, where the last min(T, P) spectra also enter the ring. A call of q T + r
+ * blocks runs q passes, then r plain steps. Passes and steps share the ring and the previous block /
+ * tail, so calls with and without batching interleave freely. Fixed order, no atomics. */
 typedef struct neo_hip_upols64 neo_hip_upols64;
 NEO_HIP_API int neo_hip_upols64_create(int channels, int block, int partitions, int device, int method /* 0 upols, 1 upola */,
                                        int split_workgroups /* 0 auto */, neo_hip_upols64** h);
@@ -984,7 +993,8 @@ NEO_HIP_API int neo_hip_upols64_set_impulse(neo_hip_upols64* h, const double* ir
                                             int is_device);
 NEO_HIP_API int neo_hip_upols64_reset(neo_hip_upols64* h);
 /* n = k B samples per channel, channel c at in + c*ld_in / out + c*ld_out (in == out allowed):
- * k step pairs. Strides in doubles, >= n and even (16-byte rows); device bases 16-byte aligned;
+ * k step pairs (with batching on: whole passes, then step pairs). Strides in doubles, >= n and even
+ * (16-byte rows); device bases 16-byte aligned;
  * anything else is refused without advancing state. Device memory: asynchronous on `stream`, no
  * host wait between blocks. Host memory: through pinned staging, synchronous. */
 NEO_HIP_API int neo_hip_upols64_process_samples(neo_hip_upols64* h, const double* in, int64_t ld_in, double* out,
@@ -994,6 +1004,20 @@ NEO_HIP_API int neo_hip_upols64_info(neo_hip_upols64* h, int* splits, int* rows,
 /* the same for a shape, host only (no device call) */
 NEO_HIP_API int neo_hip_upols64_plan(int channels, int block, int partitions, int split_workgroups, int* splits,
                                      int* rows, int64_t* state_bytes);
+/* Batched passes on or off. blocks: 0 off, 1 on with the plan's blocks per pass, 8 or 16 on with that
+ * many. A setup call: it waits for the handle's queued work; turning on takes the scratch, the
+ * pass's slabs and (overlap-add) the tails from the device pool, turning off or destroy gives them
+ * back. Filter, ring and previous block / tail are untouched: it may come between any two process
+ * calls. Off by default; a handle that never calls it behaves and reports as before. */
+NEO_HIP_API int neo_hip_upols64_set_batch(neo_hip_upols64* h, int blocks);
+/* blocks per pass (1 while batching is off), splits per channel of the pass's MAC, device bytes that
+ * batching holds on top of state_bytes */
+NEO_HIP_API int neo_hip_upols64_batch_info(neo_hip_upols64* h, int* blocks_per_pass, int* splits, int64_t* extra_bytes);
+/* the same for a shape, host only, `blocks` as in set_batch (0 counts as 1): also the partitions per
+ * split (the last split may be shorter) and the algorithmic bytes of one pass */
+NEO_HIP_API int neo_hip_upols64_batch_plan(int channels, int block, int partitions, int method, int split_workgroups,
+                                           int blocks, int* blocks_per_pass, int* splits, int* rows, int64_t* extra_bytes,
+                                           int64_t* pass_bytes);
 
 /* -- one-shot full convolution (extra/python/src/neo/__init__.py:43-48) ----
  * out has n + m - 1 samples; n == 0 or m == 0 is a no-op (empty result).

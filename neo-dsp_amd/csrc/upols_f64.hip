@@ -3,17 +3,16 @@
 // (uniform_partitioned_convolver.hpp:13-65 over overlap_save.hpp:84-112 / overlap_add.hpp:76-106 with
 // Float = double), and the setup path in double (uniform_partition.hpp:12-26,
 // normalize_impulse.hpp:11-33). A handle type of its own: no float path is touched.
-//   cfg64                     per-B geometry: one 16-byte load (one bin) per lane and value
+//   cfg64                     per-B geometry (upols_f64_handle.hpp, with the handle itself)
 //   k_upols64_step            launch 1, grid C x S: split 0 window r2c + FDL insert; every split its MAC
 //   k_upols64_finish          launch 2, one workgroup per channel: slabs in order, c2r, output
 //   k_partition64, k_pack64   IR -> filter rows; reference layout [C][P][B+1] -> packed rows
 //   k_energy64, k_scale_min64 normalize_impulse
 //   neo_hip_upols64           the handle; the plan is an upols64_shape (upols_f64_plan.hpp, host only)
 // A block is the plain two-launch step: no last-arriver fusion, no atomics; equal calls give equal bits.
-#include "common.hpp"
-#include "fft_device_real.hpp"
-#include "upols_f64_plan.hpp"
-#include "upols_handle.hpp"
+// With batching on (neo_hip_upols64_set_batch, upols_f64_batch.hip) a call's whole passes of T blocks
+// go first and its remainder runs as plain steps, on the same ring and prev.
+#include "upols_f64_handle.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -21,26 +20,6 @@
 #include <mutex>
 
 namespace neo_hip {
-
-// Rows are B complex doubles, 16 bytes each: a lane loads one bin per value (global_load_dwordx4),
-// QT lanes cover (a chunk of) a row, RPI rows per iteration where a row is shorter than the
-// workgroup. Above 512 bins a workgroup walks the row in NCH chunks of 512 bins, the loop over the
-// partitions inside, so the accumulators (8 VGPRs per bin) and the loads in flight (U rows x VPT
-// bins x 2 values x 4 VGPRs = 32) do not grow with B.
-template<int B>
-struct cfg64 {
-    static constexpr int QT = B < 256 ? B : 256;
-    static constexpr int RPI = 256 / QT;
-    static constexpr int VPT = B / QT >= 2 ? 2 : 1;
-    static constexpr int NCH = B / (QT * VPT);
-    static constexpr int U = 4 / VPT;
-    static constexpr int EW = B / 8 <= 256 ? 8 : B / 256;  // window transform: elements per lane
-    static constexpr int EF = B / 4 <= 256 ? 4 : B / 256;  // tail transform
-    static constexpr int TW1 = twiddle_len<B>();
-    static constexpr int TW2 = twiddle_len<2 * B>();
-    static constexpr int LL = lds_len(B);
-    static_assert(RPI == 1 || NCH == 1, "row groups fold through LDS once");
-};
 
 struct acc4d {  // 4 partial products per bin keep the packed bin 0 exact (DC and Nyquist are real products)
     double rr, ii, ri, ir;
@@ -349,21 +328,20 @@ __global__ void k_scale_min64(double* __restrict__ ir, int64_t n, const double* 
 
 using namespace neo_hip;
 
-struct neo_hip_upols64 {
-    upols64_shape shape;  // the plan (upols_f64_plan.hpp)
-    int device = 0;
-    hipStream_t stream = nullptr;  // one of the device's shared setup streams
-    cd* H = nullptr;               // [C][P][B]
-    cd* fdl = nullptr;             // [C][P][B], ring of P rows
-    cd* part = nullptr;            // slabs [C][S][B]
-    double* prev = nullptr;        // [C][B]
-    const cd* tw = nullptr;        // twiddles of B and 2B
-    int wpos = 0;                  // FDL write position (fdl_index.hpp:35-37), host-side
-    double* samples_dev = nullptr;   // host-pointer process_samples: device side
-    double* samples_host = nullptr;  // and pinned staging
-    size_t samples_cap = 0;
-    stream_set used;  // streams the step calls ran on since the last setup call
-};
+namespace neo_hip {
+
+// order a setup call after every step of this handle (the streams its step calls ran on, its own
+// stream) and, device_input, after work on the null stream that produced a device-resident input
+int setup_join64(neo_hip_upols64* h, bool device_input)
+{
+    if (int rc = h->used.join()) return rc;
+    if (device_input)
+        if (int rc = null_join()) return rc;
+    NEO_HIP_CHECK(hipStreamSynchronize(h->stream));
+    return NEO_HIP_OK;
+}
+
+}  // namespace neo_hip
 
 namespace {
 
@@ -421,17 +399,6 @@ int normalize64(double* d_ir, int C, int64_t L, double* factor, hipStream_t s)
     return NEO_HIP_OK;
 }
 
-// order a setup call after every step of this handle (the streams its step calls ran on, its own
-// stream) and, device_input, after work on the null stream that produced a device-resident input
-int setup_join64(upols64_t* h, bool device_input)
-{
-    if (int rc = h->used.join()) return rc;
-    if (device_input)
-        if (int rc = null_join()) return rc;
-    NEO_HIP_CHECK(hipStreamSynchronize(h->stream));
-    return NEO_HIP_OK;
-}
-
 int reset_state64(upols64_t* h, hipStream_t s)
 {
     NEO_HIP_CHECK(hipMemsetAsync(h->fdl, 0, size_t(h->shape.fdl_bytes), s));
@@ -447,6 +414,7 @@ void destroy64(upols64_t* h)
     dfree(h->fdl);
     dfree(h->part);
     dfree(h->prev);
+    batch_free64(h);
     dfree(h->samples_dev);
     hfree(h->samples_host);
     delete h;  // h->stream is shared (dmem.hip)
@@ -487,11 +455,16 @@ int launch_step64(upols64_t* h, const double* in, int64_t ld_in, double* out, in
     return NEO_HIP_OK;
 }
 
-// n = k B samples of every channel: k step pairs on s, no host wait in between
+// n = k B samples of every channel on s, no host wait in between: with batching on, the whole
+// passes of T blocks first; what is left (all of it with batching off), one step pair per block
 int process64(upols64_t* h, const double* in, int64_t ld_in, double* out, int64_t ld_out, int64_t n, hipStream_t s)
 {
     if (int rc = h->used.note(s)) return rc;
-    for (int64_t done = 0; done < n; done += h->shape.B)
+    int64_t done = 0;
+    if (h->batch.T > 1)
+        for (const int64_t pass = int64_t(h->batch.T) * h->shape.B; done + pass <= n; done += pass)
+            if (int rc = launch_pass64(h, in + done, ld_in, out + done, ld_out, s)) return rc;
+    for (; done < n; done += h->shape.B)
         if (int rc = launch_step64(h, in + done, ld_in, out + done, ld_out, s)) return rc;
     return NEO_HIP_OK;
 }
@@ -524,6 +497,7 @@ NEO_HIP_API int neo_hip_upols64_create(int channels, int block, int partitions, 
     if (g.rc) return g.rc;
     auto* h = new upols64_t{};
     h->shape = sh;
+    h->split_workgroups = split_workgroups;
     auto bail = [&](int code) {
         destroy64(h);
         return code;

@@ -5,6 +5,9 @@
 //   upols64_shape        the plan
 //   make_upols64_shape   checks + rules; the refusal text or nullptr
 //   upols64_io_refusal   the I/O contract of process_samples; the refusal text or nullptr
+// and of its batched passes (upols_f64_batch.hip; tests/cpp/upols_f64_batch_plan_main.cpp):
+//   upols64_window_src, upols64_commit_row   the two index rules of a pass, host and device
+//   upols64_batch_shape, make_upols64_batch_shape   blocks per pass, splits, byte counts
 #pragma once
 
 #include "upols_plan.hpp"
@@ -66,6 +69,89 @@ inline const char* make_upols64_shape(int channels, int block, int partitions, i
     // and (overlap-save) the previous one, writes the next prev / tail, writes and reads the slabs
     // and writes the output block
     out.step_bytes = 2 * out.filter_bytes + 2 * out.slab_bytes + int64_t(channels) * block * 8 * 4;
+    return nullptr;
+}
+
+#if defined(__HIPCC__)
+#define NEO_F64_HD __host__ __device__
+#else
+#define NEO_F64_HD
+#endif
+
+// ---- batched passes (upols_f64_batch.hip) ----
+// A pass is T consecutive blocks of every channel at write position w. Block j's spectrum is the
+// fresh row N[j] of a scratch [C][T][B]; block j at partition p takes window row e = j - p: the
+// fresh row N[e] when e >= 0, else the ring row (w + e) mod P as it stood before the pass (one wrap:
+// e > -P). The ring takes the fresh rows after the MAC, in the finish launch.
+
+// where window row e comes from: the scratch row `row`, or the ring row `row`
+struct upols64_row_src {
+    bool scratch;
+    int row;
+};
+NEO_F64_HD inline upols64_row_src upols64_window_src(int e, int w, int P)
+{
+    if (e >= 0) return {true, e};
+    const int r = w + e;
+    return {false, r < 0 ? r + P : r};
+}
+
+// the ring row that block j of a pass of T commits its fresh row to, or -1: only the last
+// min(T, P) blocks commit, so a ring row is written at most once per pass
+NEO_F64_HD inline int upols64_commit_row(int j, int T, int P, int w) { return j < T - P ? -1 : (w + j) % P; }
+
+struct upols64_batch_shape {
+    int T = 1;            // blocks per pass; 1: batching off
+    int S = 1, rows = 1;  // splits per channel of the pass's MAC, partitions per split (the last may be shorter)
+    int64_t scratch_bytes = 0, slab_bytes = 0, tail_bytes = 0;
+    int64_t extra_bytes = 0;  // their sum: what batching adds to the handle on the device
+    int64_t pass_bytes = 0;   // algorithmic bytes of one pass
+};
+
+// Blocks per pass: 16 for every B, by measurement. The MAC lane holds T accumulators and T window
+// rows of 4 VGPRs each and 4 rows of prefetch: T = 16 compiles to 236 VGPRs without spills (2 waves
+// per SIMD), T = 8 to 140 (3 waves), T = 32 cannot fit. The pass is HBM-bound and 16 halves the filter
+// and ring traffic per block against 8: measured per block (profiles/upols_f64_batch_sweep.json,
+// DESIGN.md 6) 45.7 us against 94.7 at 256 x 512 x 938, 82.6 against 176.1 at 256 x 256 x 3750 and
+// 1.4 against 2.2 at 1 x 512 x 188. T = 8 was faster nowhere.
+inline int upols64_default_blocks_per_pass(int /*block*/) { return 16; }
+
+// The plan of the passes of a handle of shape sh. blocks: 0 or 1 the rule above, 8 or 16 that many.
+// split_workgroups as at create: 0 automatic, else the plain step's splits are taken as they are.
+// Returns nullptr or the refusal text.
+inline const char* make_upols64_batch_shape(const upols64_shape& sh, int blocks, int split_workgroups, upols64_batch_shape& out)
+{
+    if (blocks != 0 && blocks != 1 && blocks != 8 && blocks != 16) return "blocks per pass must be 0 (automatic), 8 or 16";
+    out = upols64_batch_shape{};
+    out.T = blocks > 1 ? blocks : upols64_default_blocks_per_pass(sh.B);
+    if (split_workgroups) {
+        out.S = sh.S;
+        out.rows = sh.rows;
+    } else {
+        // The plain step's rule over the pass's grid, C x S x ceil(B / 256) workgroups: ~1024 of them,
+        // at least T rows per split (the sliding window fills once per split), <= 64 slabs. The
+        // constants are the float step's, inherited: the sweep only shows that asking for two and
+        // four times the workgroups is slower at all three shapes (more window rows and slabs).
+        const int chunks = (sh.B + 255) / 256;
+        const int64_t per_split = int64_t(sh.C) * chunks;
+        const int want = int(std::min<int64_t>((1024 + per_split - 1) / per_split, 64));
+        const int S = std::max(1, std::min(want, sh.P / out.T));
+        out.rows = (sh.P + S - 1) / S;
+        out.S = (sh.P + out.rows - 1) / out.rows;
+    }
+    const int64_t row = int64_t(sh.B) * 16;
+    out.scratch_bytes = int64_t(sh.C) * out.T * row;
+    out.slab_bytes = int64_t(sh.C) * out.S * out.T * row;
+    out.tail_bytes = sh.ola ? int64_t(sh.C) * out.T * sh.B * 8 : 0;
+    out.extra_bytes = out.scratch_bytes + out.slab_bytes + out.tail_bytes;
+    // a pass reads the filter and the ring once, writes the scratch, reads T window rows per split,
+    // writes and reads the slabs, copies min(T, P) rows into the ring, and moves per block 3 rows of
+    // samples (overlap-save: block, previous block, output) or 6 (overlap-add: block; output and
+    // tail written; output and the tail before it read, output written again); the next prev /
+    // overlap adds one row per channel
+    out.pass_bytes = sh.filter_bytes + sh.fdl_bytes + out.scratch_bytes + int64_t(sh.C) * out.S * out.T * row +
+                     2 * out.slab_bytes + 2 * int64_t(sh.C) * std::min(out.T, sh.P) * row +
+                     int64_t(sh.C) * sh.B * 8 * (int64_t(out.T) * (sh.ola ? 6 : 3) + 1);
     return nullptr;
 }
 

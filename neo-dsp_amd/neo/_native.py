@@ -224,6 +224,10 @@ SIGNATURES = {
     "neo_hip_upols64_process_samples": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _i, _vp]),
     "neo_hip_upols64_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
     "neo_hip_upols64_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
+    "neo_hip_upols64_set_batch": (_i, [_vp, _i]),
+    "neo_hip_upols64_batch_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
+    "neo_hip_upols64_batch_plan": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
+                                        ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "neo_hip_fft_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_direct_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_fft_convolve_f64": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
@@ -233,7 +237,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1500 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1600 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

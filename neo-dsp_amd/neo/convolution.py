@@ -14,6 +14,7 @@ Python; extra/python/src/main.cpp:227-234 only lists the `upols` method enum):
   - dense_convolve         extra/plugin/src/dsp/DenseConvolution.hpp:39-70
   - UpolsConvolver64       upols_convolver / upola_convolver of complex<double> (dtype=np.float64 on
                            uniform_partition, normalize_impulse, dense_convolve and the two classes)
+                           with set_batch(): calls of many blocks in passes of 16 blocks
   - sparse_upols_convolver / sparse_upola_convolver
                            src/neo/convolution/sparse_convolver.hpp:12-17 (sparse_filter.hpp:25-45;
                            kept in 128-byte tiles of 16 bins here, include/neo_hip.h)
@@ -79,6 +80,7 @@ __all__ = [
     "convolve",
     "UpolsConvolver64",
     "upols64_plan",
+    "upols64_batch_plan",
 ]
 
 
@@ -669,8 +671,10 @@ class UpolsConvolver64:
 
     State lives in HBM in complex128 / float64: filter [C][P][B] and FDL [C][P][B] (packed bins),
     previous block or overlap tail [C][B]. Whole blocks, in place, zero latency. `split_workgroups`
-    (0: automatic) is the number of workgroups the MAC launch aims for. No streaming levels, batched
-    passes, live updates, latency mode or groups: the float32 UpolsConvolver has those."""
+    (0: automatic) is the number of workgroups the MAC launch aims for. set_batch() turns batched
+    passes on for calls of many blocks (offline work): T blocks per read of the filter and the delay
+    line. No streaming levels, live updates, latency mode or groups: the float32 UpolsConvolver has
+    those."""
 
     def __init__(self, channels: int, block_size: int, partitions: int, device: int = 0, method: str = "upols",
                  split_workgroups: int = 0):
@@ -765,6 +769,19 @@ class UpolsConvolver64:
         _native.check(_native.load().neo_hip_upols64_info(self._h, ctypes.byref(s), ctypes.byref(r), ctypes.byref(b)))
         return {"splits": s.value, "rows": r.value, "state_bytes": b.value}
 
+    def set_batch(self, enable=True) -> None:
+        """Batched passes on or off (neo_hip_upols64_set_batch): a call of q T + r blocks then runs q
+        passes of T blocks and r plain steps. True: the plan's T; 8 or 16: that T. Filter and state
+        stay as they are, so it may come between any two process calls."""
+        _native.check(_native.load().neo_hip_upols64_set_batch(self._h, int(enable)))
+
+    def batch_info(self) -> dict:
+        """blocks per pass (1 while batching is off), splits per channel of the pass's MAC, and the
+        device bytes batching holds on top of info()['state_bytes']."""
+        t, s, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols64_batch_info(self._h, ctypes.byref(t), ctypes.byref(s), ctypes.byref(b)))
+        return {"blocks_per_pass": t.value, "splits": s.value, "extra_bytes": b.value}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.check(_native.load().neo_hip_upols64_destroy(self._h))
@@ -784,6 +801,21 @@ def upols64_plan(channels: int, block_size: int, partitions: int, split_workgrou
                                                       int(split_workgroups), ctypes.byref(s), ctypes.byref(r),
                                                       ctypes.byref(b)))
     return {"splits": s.value, "rows": r.value, "state_bytes": b.value}
+
+
+def upols64_batch_plan(channels: int, block_size: int, partitions: int, method: str = "upols", split_workgroups: int = 0,
+                       blocks: int = 0) -> dict:
+    """The batched passes of a UpolsConvolver64 of this shape, without a device
+    (neo_hip_upols64_batch_plan): what batch_info() reports once set_batch(blocks or True) is on, the
+    partitions per split and the algorithmic bytes of one pass."""
+    methods = {"upols": 0, "upola": 1}
+    if method not in methods:
+        raise ValueError(f"method must be 'upols' or 'upola', got {method!r}")
+    t, s, r, e, b = ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+    _native.check(_native.load().neo_hip_upols64_batch_plan(int(channels), int(block_size), int(partitions), methods[method],
+                                                            int(split_workgroups), int(blocks), ctypes.byref(t),
+                                                            ctypes.byref(s), ctypes.byref(r), ctypes.byref(e), ctypes.byref(b)))
+    return {"blocks_per_pass": t.value, "splits": s.value, "rows": r.value, "extra_bytes": e.value, "pass_bytes": b.value}
 
 
 class UpolsMultiConvolver:
@@ -1195,11 +1227,15 @@ class upola_convolver_v2(upols_convolver):
 
 
 def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, method: str = "upols",
-                   options: dict | None = None, *, dtype=np.float32) -> np.ndarray:
+                   options: dict | None = None, *, dtype=np.float32, batch: bool = False) -> np.ndarray:
     """dense_convolve<upols_convolver | upola_convolver> (DenseConvolution.hpp:39-70): normalize
     the IR matrix, partition it, run every block (tail zero-padded), output truncated to N.
     `options`: UpolsConvolver code-path choices (same results). dtype=np.float64: the whole chain in
-    double (UpolsConvolver64; of `options` it reads split_workgroups alone), float64 out."""
+    double (UpolsConvolver64; of `options` it reads split_workgroups alone), float64 out; with
+    batch=True in batched passes (UpolsConvolver64.set_batch), the default is the loop of steps.
+    `batch` belongs to float64 alone."""
+    if batch and not _f64(dtype):
+        raise ValueError("batch=True takes dtype=np.float64 (the float32 path chooses its passes by `options`)")
     if _f64(dtype):
         sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float64)))
         ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float64)))
@@ -1212,6 +1248,8 @@ def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, m
         conv = UpolsConvolver64(C, block_size, num_partitions(ir.shape[1], block_size), device, method=method,
                                 split_workgroups=int((options or {}).get("split_workgroups", 0)))
         conv.set_impulse(ir, normalize=True)
+        if batch:
+            conv.set_batch(True)
         nb = -(-N // block_size)
         chunk = max(1, (1 << 25) // (C * block_size))  # <= 2^25 doubles per upload
         out = np.empty_like(sig)

@@ -1,0 +1,28 @@
+#!/usr/bin/env python3
+"""Writes tests/golden/upols_f64_batch_case.bin, the float64 fixture of tests/cpp/test_f64_batch.cpp:
+tests/golden/upols_f64_case.bin's layout with enough blocks for two batched passes and a remainder
+(35 = 2 x 16 + 3) and a filter longer than a pass (21 partitions), and its numpy truth
+(tests/upols_f64_truth.py). Little-endian: int64 C, B, P, nb, L; then float64 ir [C][L], x [C][nb B],
+y_upols [C][nb B], y_upola [C][nb B] (the filter is uniform_partition of ir, not normalized)."""
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import upols_f64_truth as T  # noqa: E402
+
+C, B, P, nb = 3, 64, 21, 35
+rng = np.random.default_rng(641664)
+ir = rng.standard_normal((C, P * B - 3))
+x = rng.standard_normal((C, nb * B))
+H = T.partition(ir, B)
+ys = [T.blockwise(x, H, m) for m in ("upols", "upola")]
+assert all(T.peak_err(y, T.whole(x, ir)) < 1e-13 for y in ys)
+out = os.path.join(REPO, "tests", "golden", "upols_f64_batch_case.bin")
+with open(out, "wb") as f:
+    f.write(np.array([C, B, P, nb, ir.shape[1]], dtype="<i8").tobytes())
+    for a in (ir, x, *ys):
+        f.write(np.ascontiguousarray(a, dtype="<f8").tobytes())
+print(out, os.path.getsize(out), "bytes")
