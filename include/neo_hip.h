@@ -39,6 +39,10 @@
  *   - ONE CONVOLVER HANDLE, OVERLAP STAGE OR GROUP is for one thread at a time, as the
  *     reference's stateful convolvers are: its calls carry state from block to block and take
  *     no lock on the step path. A caller that moves one between threads orders the calls.
+ *     One handle's process calls on DIFFERENT streams are the caller's to order as well (an
+ *     event from one stream to the next); setup and destroy calls wait for the handle's calls
+ *     on every stream they ran on (those streams, never the device) before they free,
+ *     reallocate or rewrite a buffer, so they may follow a queued call with no wait between.
  *   - neo_hip_last_error() is per thread: the message of the calling thread's last failed call.
  */
 #ifndef NEO_HIP_H
@@ -718,7 +722,8 @@ NEO_HIP_API int neo_hip_matrix_reset(neo_hip_matrix* m);
  * be ordered with it (after every earlier process call, before every later one): the update reads
  * the delay lines those calls write (overlap-add) and writes the bank the later ones read. Device
  * pointer: asynchronous on `stream` (NULL = the HIP null stream). Host pointer: staged on `stream`
- * (NULL = the handle's stream, as host process calls), returns when the bank is written.
+ * (NULL = the handle's stream, as host process calls) after the handle's earlier steps on any
+ * stream; returns when the bank is written.
  * EINVAL, the handle unchanged: before a filter is set, fade_blocks < 1, curve not 0 (linear) or 1
  * (raised cosine), or while a fade has blocks left. set_filter / set_impulse cancel a running fade
  * (and free the second bank: the route list may change); set_batch / set_offline keep it. */

@@ -912,6 +912,16 @@ int matrix_set_end(matrix_t* m, int rc)
     return rc;
 }
 
+// the call's stream noted; a host filter's call is synchronous, so it also comes after the handle's
+// earlier steps on every stream: they write the delay lines and tails the fade is armed from
+// (overlap-add), and the last step of an earlier fade may still read the spare bank
+int matrix_update_begin(matrix_t* m, bool is_device, hipStream_t s)
+{
+    if (!is_device)
+        if (int rc = m->used.join()) return rc;
+    return m->used.note(s);
+}
+
 // an update call after its load (rc): the fade armed; host memory: complete on return
 int matrix_update_end(matrix_t* m, int rc, bool is_device, int fade_blocks, int curve, hipStream_t s)
 {
@@ -1092,7 +1102,7 @@ NEO_HIP_API int neo_hip_matrix_update_filter(neo_hip_matrix* m, const void* filt
     device_guard g(m->device);
     if (g.rc) return g.rc;
     hipStream_t s = matrix_stream(m, is_device, stream);
-    if (int rc = m->used.note(s)) return rc;
+    if (int rc = matrix_update_begin(m, is_device != 0, s)) return rc;
     if (int rc = matrix_fade_buffers(m)) return rc;
     return matrix_update_end(m, matrix_load_filter(m, filter, is_device != 0, m->H2, s), is_device != 0, fade_blocks, curve, s);
 }
@@ -1105,7 +1115,7 @@ NEO_HIP_API int neo_hip_matrix_update_impulse(neo_hip_matrix* m, const float* ir
     device_guard g(m->device);
     if (g.rc) return g.rc;
     hipStream_t s = matrix_stream(m, is_device, stream);
-    if (int rc = m->used.note(s)) return rc;
+    if (int rc = matrix_update_begin(m, is_device != 0, s)) return rc;
     if (int rc = matrix_fade_buffers(m)) return rc;
     return matrix_update_end(m, matrix_load_impulse(m, ir, length, normalize != 0, is_device != 0, m->H2, s), is_device != 0,
                              fade_blocks, curve, s);
