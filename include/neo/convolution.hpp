@@ -489,6 +489,25 @@ struct upols_multichannel64 {
         return r;
     }
 
+    /// what offline_info() reports
+    struct offline_report {
+        int blocks_per_pass;        ///< 128; 0 while offline windows are off
+        int segments;               ///< ceil(P / 128)
+        std::int64_t spectra_bytes; ///< device bytes of the segment spectra
+        std::int64_t extra_bytes;   ///< device bytes of the scratch, the windows' spectra and the tails
+    };
+    /// offline windows on or off (neo_hip_upols64_set_offline): a process call then runs a window
+    /// pass for every 128 blocks left, then batched passes if batch(true), then plain steps. State
+    /// stays as it is, so it may come between any two process calls.
+    auto offline(bool enable) -> void { neo::hip::check(neo_hip_upols64_set_offline(_h.get(), enable ? 1 : 0)); }
+    [[nodiscard]] auto offline_info() const -> offline_report
+    {
+        offline_report r{};
+        neo::hip::check(neo_hip_upols64_offline_info(_h.get(), &r.blocks_per_pass, &r.segments, &r.spectra_bytes,
+                                                     &r.extra_bytes));
+        return r;
+    }
+
 private:
     std::size_t _C, _B, _P;
     detail::upols64_ptr _h;
@@ -1288,15 +1307,19 @@ inline auto dense_convolve(float const* signal, std::size_t channels, std::size_
     }
 }
 
-/// the same in double (upols_multichannel64): signal, ir and out of double
+/// the same in double (upols_multichannel64): signal, ir and out of double; offline: in offline
+/// windows of 128 blocks (upols_multichannel64::offline), what is left in plain steps
 inline auto dense_convolve(double const* signal, std::size_t channels, std::size_t num_samples, double const* ir,
-                           std::size_t ir_length, std::size_t block_size, double* out, method m = method::upols) -> void
+                           std::size_t ir_length, std::size_t block_size, double* out, method m = method::upols,
+                           bool offline = false) -> void
 {
     upols_multichannel64 conv{channels, block_size, num_partitions(ir_length, block_size),
                               neo::hip::detail::default_device(), m};
     conv.impulse(ir, ir_length, true);
+    if (offline) conv.offline(true);
     std::size_t const nb = (num_samples + block_size - 1) / block_size;
-    std::size_t const chunk = std::max<std::size_t>(1, (std::size_t(1) << 25) / (channels * block_size));
+    std::size_t chunk = std::max<std::size_t>(1, (std::size_t(1) << 25) / (channels * block_size));
+    if (offline) chunk = std::max<std::size_t>(128, chunk / 128 * 128);  // whole windows
     std::vector<double> buf;
     for (std::size_t t0 = 0; t0 < nb; t0 += chunk) {
         std::size_t const t1 = std::min(nb, t0 + chunk), lo = t0 * block_size,

@@ -105,8 +105,10 @@ typedef struct neo_hip_upols neo_hip_upols;
  * 0.15.0: double-precision upols / upola convolvers (neo_hip_upols64_*) and the setup path in double
  *        (neo_hip_uniform_partition_f64, neo_hip_normalize_impulse_f64).
  * 0.16.0: batched passes on double-precision handles (neo_hip_upols64_set_batch,
- *        neo_hip_upols64_batch_info, neo_hip_upols64_batch_plan). */
-#define NEO_HIP_VERSION 1600 /* 0.16.0 */
+ *        neo_hip_upols64_batch_info, neo_hip_upols64_batch_plan).
+ * 0.17.0: offline windows on double-precision handles (neo_hip_upols64_set_offline,
+ *        neo_hip_upols64_offline_info, neo_hip_upols64_offline_plan). */
+#define NEO_HIP_VERSION 1700 /* 0.17.0 */
 NEO_HIP_API const char* neo_hip_last_error(void);
 NEO_HIP_API int neo_hip_version(void);
 NEO_HIP_API int neo_hip_device_count(int* count);
@@ -998,7 +1000,8 @@ NEO_HIP_API int neo_hip_upols64_set_impulse(neo_hip_upols64* h, const double* ir
                                             int is_device);
 NEO_HIP_API int neo_hip_upols64_reset(neo_hip_upols64* h);
 /* n = k B samples per channel, channel c at in + c*ld_in / out + c*ld_out (in == out allowed):
- * k step pairs (with batching on: whole passes, then step pairs). Strides in doubles, >= n and even
+ * k step pairs (with offline windows on: whole windows of 128 blocks first; with batching on: whole
+ * passes next; then step pairs). Strides in doubles, >= n and even
  * (16-byte rows); device bases 16-byte aligned;
  * anything else is refused without advancing state. Device memory: asynchronous on `stream`, no
  * host wait between blocks. Host memory: through pinned staging, synchronous. */
@@ -1023,6 +1026,45 @@ NEO_HIP_API int neo_hip_upols64_batch_info(neo_hip_upols64* h, int* blocks_per_p
 NEO_HIP_API int neo_hip_upols64_batch_plan(int channels, int block, int partitions, int method, int split_workgroups,
                                            int blocks, int* blocks_per_pass, int* splits, int* rows, int64_t* extra_bytes,
                                            int64_t* pass_bytes);
+/* Offline windows, the third gear, for calls of 128 blocks and more (a whole file to render): off
+ * by default, enable 0 or 1 (anything else: NEO_HIP_EINVAL), any P >= 1. While on, process_samples
+ * runs a window pass for every 128 blocks left, then batched passes if batching is on, then plain
+ * steps; all three share the ring and the previous block / tail, so they mix freely at block
+ * boundaries, across calls and across toggling.
+ * The rule, per channel and bin (packed rows of B complex doubles, bin 0 = {DC, Nyquist}): a window
+ * is 128 consecutive blocks at write position w; block j's spectrum is the fresh scratch row N[j].
+ * Window row e, the spectrum of the block e blocks after the window's first, is N[e] for e >= 0, the
+ * ring row (w + e) mod P as it stood before the pass for -P < e < 0, and zero for e <= -P (such rows
+ * meet only the zero padding of the last filter segment; the ring stays at exactly P rows). With
+ * nseg = ceil(P / 128),
+ *   Y[j], j = 0..127 = samples 128 + j of IDFT256( sum over q < nseg of
+ *                      DFT256(rows -128 (q + 1) .. -128 q + 127) . HF[q] ),
+ * HF[q] = DFT256 along the partition axis of filter rows 128 q .. 128 q + 127 (zero past P, zero
+ * padded to 256), accumulated in the fixed order q = 0, 1, ..; no atomics, equal calls give equal
+ * bits. A pass is three launches, four for overlap-add: the 128 window transforms; per 8 bins of a
+ * channel the pairs from the newest back (every ring row read once), the products and one inverse
+ * transform; per block the c2r, the output and, for the last min(128, P) blocks, the ring commit;
+ * the overlap chain. The segment spectra are rebuilt on the stream of the first window pass after
+ * set_filter / set_impulse / set_offline(1). in == out holds as for the other gears.
+ * Memory, from the device pool, given back by set_offline(0) and destroy: the spectra
+ * [C][nseg][256][B] (16 C nseg 256 B bytes, about twice the filter), and extra_bytes: the scratch
+ * and Y [C][128][B] complex double each and (overlap-add) the tails [C][128][B] double. If the pool
+ * cannot give them: NEO_HIP_ENOMEM, the handle as it was. A setup call: it waits for the handle's
+ * queued work.
+ * Inf / NaN: a non-finite input block makes every output block of every window whose pairs hold it
+ * non-finite, on that channel: the window that contains it and the windows after it up to the last
+ * one that starts at a block t_W with t_W - 128 nseg <= that block; overlap-add adds the block after
+ * those. Other channels, and earlier windows of that channel, are untouched bit for bit. */
+NEO_HIP_API int neo_hip_upols64_set_offline(neo_hip_upols64* h, int enable);
+/* blocks per window pass (128; 0 while off), segments nseg, bytes of the segment spectra, bytes of
+ * scratch + Y + tails (all 0 while off) */
+NEO_HIP_API int neo_hip_upols64_offline_info(neo_hip_upols64* h, int* blocks_per_pass, int* segments,
+                                             int64_t* spectra_bytes, int64_t* extra_bytes);
+/* the same for a shape, host only (bad shapes refused before any device call): also the algorithmic
+ * bytes of one window pass */
+NEO_HIP_API int neo_hip_upols64_offline_plan(int channels, int block, int partitions, int method, int* blocks_per_pass,
+                                             int* segments, int64_t* spectra_bytes, int64_t* extra_bytes,
+                                             int64_t* pass_bytes);
 
 /* -- one-shot full convolution (extra/python/src/neo/__init__.py:43-48) ----
  * out has n + m - 1 samples; n == 0 or m == 0 is a no-op (empty result).

@@ -11,7 +11,8 @@
 //   neo_hip_upols64           the handle; the plan is an upols64_shape (upols_f64_plan.hpp, host only)
 // A block is the plain two-launch step: no last-arriver fusion, no atomics; equal calls give equal bits.
 // With batching on (neo_hip_upols64_set_batch, upols_f64_batch.hip) a call's whole passes of T blocks
-// go first and its remainder runs as plain steps, on the same ring and prev.
+// go first and its remainder runs as plain steps, on the same ring and prev; with offline windows on
+// (neo_hip_upols64_set_offline, upols_f64_offline.hip) its whole windows of 128 blocks go before both.
 #include "upols_f64_handle.hpp"
 
 #include <algorithm>
@@ -341,12 +342,6 @@ int setup_join64(neo_hip_upols64* h, bool device_input)
     return NEO_HIP_OK;
 }
 
-}  // namespace neo_hip
-
-namespace {
-
-using upols64_t = neo_hip_upols64;
-
 // the double twiddle tables of block B (B-point, then 2B-point) on the current device, shared by every
 // handle and setup call there, never freed
 int shared_tw64(const cd** out, int B)
@@ -370,6 +365,12 @@ int shared_tw64(const cd** out, int B)
     *out = d;
     return NEO_HIP_OK;
 }
+
+}  // namespace neo_hip
+
+namespace {
+
+using upols64_t = neo_hip_upols64;
 
 int partition64(const double* d_ir, int C, int64_t L, int B, bool packed, cd* out, const cd* tw, hipStream_t s)
 {
@@ -415,6 +416,7 @@ void destroy64(upols64_t* h)
     dfree(h->part);
     dfree(h->prev);
     batch_free64(h);
+    offline_free64(h);
     dfree(h->samples_dev);
     hfree(h->samples_host);
     delete h;  // h->stream is shared (dmem.hip)
@@ -424,6 +426,7 @@ void destroy64(upols64_t* h)
 // does (uniform_partitioned_convolver.hpp:37-45), the stream is joined and the scratch goes back
 int set_end64(upols64_t* h, int rc, std::initializer_list<void*> scratch)
 {
+    h->ospectra_stale = true;  // the offline windows' segment spectra: rebuilt by the next window pass
     if (!rc) rc = reset_state64(h, h->stream);
     if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = fail(NEO_HIP_ERUNTIME, "sync failed");
     for (void* p : scratch) dfree(p);
@@ -455,12 +458,16 @@ int launch_step64(upols64_t* h, const double* in, int64_t ld_in, double* out, in
     return NEO_HIP_OK;
 }
 
-// n = k B samples of every channel on s, no host wait in between: with batching on, the whole
-// passes of T blocks first; what is left (all of it with batching off), one step pair per block
+// n = k B samples of every channel on s, no host wait in between: with offline windows on, the
+// whole windows of 128 blocks first; with batching on, the whole passes of T blocks next; what is
+// left (all of it with both off), one step pair per block
 int process64(upols64_t* h, const double* in, int64_t ld_in, double* out, int64_t ld_out, int64_t n, hipStream_t s)
 {
     if (int rc = h->used.note(s)) return rc;
     int64_t done = 0;
+    if (h->offline)
+        for (const int64_t pass = int64_t(kOff64W) * h->shape.B; done + pass <= n; done += pass)
+            if (int rc = launch_window64(h, in + done, ld_in, out + done, ld_out, s)) return rc;
     if (h->batch.T > 1)
         for (const int64_t pass = int64_t(h->batch.T) * h->shape.B; done + pass <= n; done += pass)
             if (int rc = launch_pass64(h, in + done, ld_in, out + done, ld_out, s)) return rc;

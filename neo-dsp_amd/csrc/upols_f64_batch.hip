@@ -282,6 +282,50 @@ int launch_pass64(neo_hip_upols64* h, const double* in, int64_t ld_in, double* o
     return NEO_HIP_OK;
 }
 
+// Launches 1 and 3 (+ 4) on their own, for the window passes (upols_f64_offline.hip): TB blocks, the
+// fresh rows in N [C][TB][B], one slab row per block in `slab` [C][TB][B], the tails in `tails`.
+template<int B>
+static int launch_bwindow_of(neo_hip_upols64* h, const double* in, int64_t ld_in, cd* N, int TB, hipStream_t s)
+{
+    const dim3 ct(unsigned(h->shape.C), unsigned(TB));
+    if (h->shape.ola) hipLaunchKernelGGL((k_upols64_bwindow<B, true>), ct, dim3(256), 0, s, in, ld_in, h->prev, N, h->tw);
+    else hipLaunchKernelGGL((k_upols64_bwindow<B, false>), ct, dim3(256), 0, s, in, ld_in, h->prev, N, h->tw);
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+template<int B>
+static int launch_bfinish_of(neo_hip_upols64* h, const cd* slab, const cd* N, double* tails, int TB, const double* in,
+                             int64_t ld_in, double* out, int64_t ld_out, hipStream_t s)
+{
+    const upols64_shape& sh = h->shape;
+    const dim3 ct(unsigned(sh.C), unsigned(TB));
+    if (sh.ola) {
+        hipLaunchKernelGGL((k_upols64_bfinish<B, true>), ct, dim3(256), 0, s, slab, N, h->fdl, in, ld_in, h->prev, out,
+                           ld_out, tails, h->tw, sh.P, 1, h->wpos);
+        NEO_HIP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(k_upols64_bola, ct, dim3(256), 0, s, out, ld_out, tails, h->prev, B);
+    } else {
+        hipLaunchKernelGGL((k_upols64_bfinish<B, false>), ct, dim3(256), 0, s, slab, N, h->fdl, in, ld_in, h->prev, out,
+                           ld_out, tails, h->tw, sh.P, 1, h->wpos);
+    }
+    NEO_HIP_LAUNCH_CHECK();
+    return NEO_HIP_OK;
+}
+
+int launch_bwindow64(neo_hip_upols64* h, const double* in, int64_t ld_in, cd* N, int TB, hipStream_t s)
+{
+    NEO_UPOLS_DISPATCH(h->shape.B, return launch_bwindow_of<BB>(h, in, ld_in, N, TB, s))
+    return NEO_HIP_OK;
+}
+
+int launch_bfinish64(neo_hip_upols64* h, const cd* slab, const cd* N, double* tails, int TB, const double* in,
+                     int64_t ld_in, double* out, int64_t ld_out, hipStream_t s)
+{
+    NEO_UPOLS_DISPATCH(h->shape.B, return launch_bfinish_of<BB>(h, slab, N, tails, TB, in, ld_in, out, ld_out, s))
+    return NEO_HIP_OK;
+}
+
 }  // namespace neo_hip
 
 using namespace neo_hip;

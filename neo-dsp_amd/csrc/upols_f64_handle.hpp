@@ -1,7 +1,8 @@
 // upols_f64_handle.hpp — what the two translation units of the double-precision UPOLS / UPOLA
-// convolvers share: the per-B geometry, the handle and the calls across the file boundary.
-//   upols_f64.hip        the plain two-launch step, the setup path, the C ABI of the handle
-//   upols_f64_batch.hip  batched passes: T blocks per read of the filter and the delay line
+// convolvers share: the per-B geometry, the handle and the calls across the file boundaries.
+//   upols_f64.hip          the plain two-launch step, the setup path, the C ABI of the handle
+//   upols_f64_batch.hip    batched passes: T blocks per read of the filter and the delay line
+//   upols_f64_offline.hip  offline windows: 128 blocks per pass, 256-point transforms along the blocks
 #pragma once
 
 #include "common.hpp"
@@ -53,6 +54,15 @@ struct neo_hip_upols64 {
     neo_hip::cd* bscratch = nullptr;     // fresh spectra N [C][T][B]
     neo_hip::cd* bpart = nullptr;        // slabs [C][S_b][T][B]
     double* btail = nullptr;             // overlap-add: tails [C][T][B]
+    // offline windows (upols_f64_offline.hip): off until set_offline; only the spectra outlive a pass
+    bool offline = false;
+    bool ospectra_stale = true;             // the filter changed since k_upols64_ohf last ran
+    neo_hip::upols64_offline_shape oshape;  // nseg == 0: off
+    neo_hip::cd* ospectra = nullptr;        // HF [C][nseg][256][B]
+    neo_hip::cd* oscratch = nullptr;        // fresh spectra N [C][128][B]
+    neo_hip::cd* oy = nullptr;              // Y [C][128][B], the one slab of k_upols64_bfinish
+    double* otail = nullptr;                // overlap-add: tails [C][128][B]
+    const neo_hip::cd* otw = nullptr;       // twiddles of the 256-point transform
 };
 
 namespace neo_hip {
@@ -62,5 +72,15 @@ int setup_join64(neo_hip_upols64* h, bool device_input);
 // one pass of h->batch.T blocks of every channel on s (upols_f64_batch.hip)
 int launch_pass64(neo_hip_upols64* h, const double* in, int64_t ld_in, double* out, int64_t ld_out, hipStream_t s);
 void batch_free64(neo_hip_upols64* h);
+// the pass's launches 1 and 3 (+ 4, overlap-add) for TB blocks with one slab per block, on buffers
+// of the caller's: the window passes' transforms and finish (upols_f64_batch.hip)
+int launch_bwindow64(neo_hip_upols64* h, const double* in, int64_t ld_in, cd* N, int TB, hipStream_t s);
+int launch_bfinish64(neo_hip_upols64* h, const cd* slab, const cd* N, double* tails, int TB, const double* in,
+                     int64_t ld_in, double* out, int64_t ld_out, hipStream_t s);
+// the double twiddle tables of block B (B-point, then 2B-point) on the current device (upols_f64.hip)
+int shared_tw64(const cd** out, int B);
+// one window pass of 128 blocks of every channel on s (upols_f64_offline.hip)
+int launch_window64(neo_hip_upols64* h, const double* in, int64_t ld_in, double* out, int64_t ld_out, hipStream_t s);
+void offline_free64(neo_hip_upols64* h);
 
 }  // namespace neo_hip

@@ -8,6 +8,9 @@
 // and of its batched passes (upols_f64_batch.hip; tests/cpp/upols_f64_batch_plan_main.cpp):
 //   upols64_window_src, upols64_commit_row   the two index rules of a pass, host and device
 //   upols64_batch_shape, make_upols64_batch_shape   blocks per pass, splits, byte counts
+// and of its offline windows (upols_f64_offline.hip; tests/cpp/upols_f64_offline_plan_main.cpp):
+//   upols64_offline_src                                  where a window row comes from: scratch, ring or zero
+//   upols64_offline_shape, make_upols64_offline_shape    segments and byte counts
 #pragma once
 
 #include "upols_plan.hpp"
@@ -153,6 +156,65 @@ inline const char* make_upols64_batch_shape(const upols64_shape& sh, int blocks,
                      2 * out.slab_bytes + 2 * int64_t(sh.C) * std::min(out.T, sh.P) * row +
                      int64_t(sh.C) * sh.B * 8 * (int64_t(out.T) * (sh.ola ? 6 : 3) + 1);
     return nullptr;
+}
+
+// ---- offline windows (upols_f64_offline.hip) ----
+// A window is kOff64W = 128 consecutive blocks of every channel at write position w, computed per
+// bin with 256-point transforms along the block axis. Window row e is the spectrum of the block e
+// blocks after the window's first: the fresh scratch row N[e] for e >= 0, the ring row (w + e) mod P
+// as it stood before the pass for -P < e < 0, and ZERO for e <= -P: such rows meet only the zero
+// padding of the last filter segment and the ring, exactly P rows, never held them. With
+// nseg = ceil(P / 128), per channel and bin
+//   Y[j], j = 0..127 = samples 128 + j of IDFT256( sum over q < nseg, ascending, of
+//                      DFT256(rows -128 (q + 1) .. -128 q + 127) . HF[q] )
+// HF[q] = DFT256 along the partition axis of filter rows 128 q .. 128 q + 127 (zero past P, zero
+// padded to 256), [C][nseg][256][B]. The last min(128, P) fresh rows then go to the ring
+// (upols64_commit_row(j, 128, P, w)) and w moves on by 128 mod P.
+constexpr int kOff64W = 128;  // blocks per window
+constexpr int kOff64F = 256;  // transform length along the block axis
+
+// where window row e of a window pass comes from
+enum upols64_offline_kind { kOff64Scratch = 0, kOff64Ring = 1, kOff64Zero = 2 };
+struct upols64_offline_row {
+    int kind;  // upols64_offline_kind
+    int row;   // scratch or ring row; 0 for a zero row
+};
+NEO_F64_HD inline upols64_offline_row upols64_offline_src(int e, int w, int P)
+{
+    if (e >= 0) return {kOff64Scratch, e};
+    if (e <= -P) return {kOff64Zero, 0};
+    const int r = w + e;
+    return {kOff64Ring, r < 0 ? r + P : r};
+}
+
+struct upols64_offline_shape {
+    int nseg = 0;               // 128-partition segments, ceil(P / 128)
+    int64_t spectra_bytes = 0;  // HF [C][nseg][256][B]
+    int64_t scratch_bytes = 0, y_bytes = 0, tail_bytes = 0;  // N [C][128][B], Y [C][128][B], tails [C][128][B] double
+    int64_t extra_bytes = 0;    // scratch + Y + tails (the spectra are counted apart)
+    int64_t pass_bytes = 0;     // algorithmic bytes of one window pass
+};
+
+// The plan of the window passes of a handle of shape sh: any P >= 1.
+inline upols64_offline_shape make_upols64_offline_shape(const upols64_shape& sh)
+{
+    upols64_offline_shape o;
+    o.nseg = (sh.P + kOff64W - 1) / kOff64W;
+    const int64_t crow = int64_t(sh.C) * sh.B * 16;  // one packed row of every channel
+    o.spectra_bytes = crow * o.nseg * kOff64F;
+    o.scratch_bytes = crow * kOff64W;
+    o.y_bytes = crow * kOff64W;
+    o.tail_bytes = sh.ola ? int64_t(sh.C) * kOff64W * sh.B * 8 : 0;
+    o.extra_bytes = o.scratch_bytes + o.y_bytes + o.tail_bytes;
+    // a pass writes the scratch; loads the pair rows that are not zero (the 128 fresh rows and the
+    // ring rows -min(128 nseg, P - 1) .. -1, each once); reads 256 nseg spectrum rows; writes and
+    // reads Y; copies min(128, P) rows into the ring; and moves the samples as a batched pass does
+    // (3 rows per block overlap-save, 6 overlap-add, one more per channel for the next prev / overlap)
+    const int64_t ring_rows = std::min(kOff64W * o.nseg, sh.P - 1);
+    o.pass_bytes = crow * (kOff64W + (kOff64W + ring_rows) + int64_t(kOff64F) * o.nseg + 2 * kOff64W +
+                           2 * std::min(kOff64W, sh.P)) +
+                   int64_t(sh.C) * sh.B * 8 * (int64_t(kOff64W) * (sh.ola ? 6 : 3) + 1);
+    return o;
 }
 
 // The I/O contract of process_samples on a handle of block B: n samples per channel, channel c at

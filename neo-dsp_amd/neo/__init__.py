@@ -7,7 +7,7 @@ is libneo_hip.so (include/neo_hip.h). Put `<repo>/neo-dsp_amd` on sys.path.
 from . import _native
 from . import convolution
 from . import fft
-from .convolution import (UpolsConvolver, UpolsConvolver64, upols64_plan, upols64_batch_plan, UpolsMultiConvolver, convolve, dense_convolve, direct_convolve, fft_convolve,
+from .convolution import (UpolsConvolver, UpolsConvolver64, upols64_plan, upols64_batch_plan, upols64_offline_plan, UpolsMultiConvolver, convolve, dense_convolve, direct_convolve, fft_convolve,
                           host_register, host_unregister, memory_info, memory_trim, normalize_impulse, overlap_add, overlap_save, OverlapStage, UpolsGroup,
                           num_partitions, split_upola_convolver, split_upols_convolver, uniform_partition,
                           upola_convolver, upola_convolver_v2, upols_convolver,
@@ -28,6 +28,7 @@ __all__ = [
     "UpolsConvolver64",
     "upols64_plan",
     "upols64_batch_plan",
+    "upols64_offline_plan",
     "UpolsMultiConvolver",
     "upols_convolver",
     "split_upols_convolver",

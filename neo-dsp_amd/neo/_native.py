@@ -228,6 +228,11 @@ SIGNATURES = {
     "neo_hip_upols64_batch_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64)]),
     "neo_hip_upols64_batch_plan": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i),
                                         ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
+    "neo_hip_upols64_set_offline": (_i, [_vp, _i]),
+    "neo_hip_upols64_offline_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
+                                          ctypes.POINTER(_i64)]),
+    "neo_hip_upols64_offline_plan": (_i, [_i, _i, _i, _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i64),
+                                          ctypes.POINTER(_i64), ctypes.POINTER(_i64)]),
     "neo_hip_fft_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_direct_convolve": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
     "neo_hip_fft_convolve_f64": (_i, [_vp, _i64, _vp, _i64, _vp, _i, _i]),
@@ -237,7 +242,7 @@ SIGNATURES = {
     "neo_hip_stft_f64": (_i, [_vp, _i, _i64, _i, _i, _i, _vp, _vp, _i, _i]),
 }
 
-ABI_VERSION = 1600 # include/neo_hip.h NEO_HIP_VERSION
+ABI_VERSION = 1700 # include/neo_hip.h NEO_HIP_VERSION
 _lib = None
 _lock = threading.Lock()
 

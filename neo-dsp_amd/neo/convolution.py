@@ -81,6 +81,7 @@ __all__ = [
     "UpolsConvolver64",
     "upols64_plan",
     "upols64_batch_plan",
+    "upols64_offline_plan",
 ]
 
 
@@ -782,6 +783,22 @@ class UpolsConvolver64:
         _native.check(_native.load().neo_hip_upols64_batch_info(self._h, ctypes.byref(t), ctypes.byref(s), ctypes.byref(b)))
         return {"blocks_per_pass": t.value, "splits": s.value, "extra_bytes": b.value}
 
+    def set_offline(self, enable=True) -> None:
+        """Offline windows on or off (neo_hip_upols64_set_offline): a call then runs a window pass of
+        128 blocks (256-point transforms along the block axis) for every 128 blocks left, then batched
+        passes if set_batch is on, then plain steps. Filter and state stay as they are, so it may come
+        between any two process calls. It holds the segment spectra (about twice the filter) and
+        offline_info()['extra_bytes'] more until it is turned off or the convolver is closed."""
+        _native.check(_native.load().neo_hip_upols64_set_offline(self._h, int(enable)))
+
+    def offline_info(self) -> dict:
+        """blocks per window pass (128; 0 while off), segments = ceil(P / 128), the bytes of the segment
+        spectra and of the scratch, the windows' spectra and the tails (0 while off)."""
+        t, g, sb, eb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        _native.check(_native.load().neo_hip_upols64_offline_info(self._h, ctypes.byref(t), ctypes.byref(g), ctypes.byref(sb),
+                                                                  ctypes.byref(eb)))
+        return {"blocks_per_pass": t.value, "segments": g.value, "spectra_bytes": sb.value, "extra_bytes": eb.value}
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             _native.check(_native.load().neo_hip_upols64_destroy(self._h))
@@ -816,6 +833,21 @@ def upols64_batch_plan(channels: int, block_size: int, partitions: int, method: 
                                                             int(split_workgroups), int(blocks), ctypes.byref(t),
                                                             ctypes.byref(s), ctypes.byref(r), ctypes.byref(e), ctypes.byref(b)))
     return {"blocks_per_pass": t.value, "splits": s.value, "rows": r.value, "extra_bytes": e.value, "pass_bytes": b.value}
+
+
+def upols64_offline_plan(channels: int, block_size: int, partitions: int, method: str = "upols") -> dict:
+    """The offline windows of a UpolsConvolver64 of this shape, without a device
+    (neo_hip_upols64_offline_plan): what offline_info() reports once set_offline() is on, and the
+    algorithmic bytes of one window pass."""
+    methods = {"upols": 0, "upola": 1}
+    if method not in methods:
+        raise ValueError(f"method must be 'upols' or 'upola', got {method!r}")
+    t, g, sb, eb, pb = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    _native.check(_native.load().neo_hip_upols64_offline_plan(int(channels), int(block_size), int(partitions), methods[method],
+                                                              ctypes.byref(t), ctypes.byref(g), ctypes.byref(sb),
+                                                              ctypes.byref(eb), ctypes.byref(pb)))
+    return {"blocks_per_pass": t.value, "segments": g.value, "spectra_bytes": sb.value, "extra_bytes": eb.value,
+            "pass_bytes": pb.value}
 
 
 class UpolsMultiConvolver:
@@ -1227,15 +1259,17 @@ class upola_convolver_v2(upols_convolver):
 
 
 def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, method: str = "upols",
-                   options: dict | None = None, *, dtype=np.float32, batch: bool = False) -> np.ndarray:
+                   options: dict | None = None, *, dtype=np.float32, batch: bool = False,
+                   offline: bool = False) -> np.ndarray:
     """dense_convolve<upols_convolver | upola_convolver> (DenseConvolution.hpp:39-70): normalize
     the IR matrix, partition it, run every block (tail zero-padded), output truncated to N.
     `options`: UpolsConvolver code-path choices (same results). dtype=np.float64: the whole chain in
     double (UpolsConvolver64; of `options` it reads split_workgroups alone), float64 out; with
-    batch=True in batched passes (UpolsConvolver64.set_batch), the default is the loop of steps.
-    `batch` belongs to float64 alone."""
-    if batch and not _f64(dtype):
-        raise ValueError("batch=True takes dtype=np.float64 (the float32 path chooses its passes by `options`)")
+    batch=True in batched passes (UpolsConvolver64.set_batch), with offline=True in offline windows of
+    128 blocks (UpolsConvolver64.set_offline; what is left of a chunk goes by batch), the default is
+    the loop of steps. `batch` and `offline` belong to float64 alone."""
+    if (batch or offline) and not _f64(dtype):
+        raise ValueError("batch=True / offline=True take dtype=np.float64 (the float32 path chooses its passes by `options`)")
     if _f64(dtype):
         sig = np.ascontiguousarray(np.atleast_2d(np.asarray(signal, dtype=np.float64)))
         ir = np.ascontiguousarray(np.atleast_2d(np.asarray(impulse_response, dtype=np.float64)))
@@ -1250,8 +1284,12 @@ def dense_convolve(signal, impulse_response, block_size: int, device: int = 0, m
         conv.set_impulse(ir, normalize=True)
         if batch:
             conv.set_batch(True)
+        if offline:
+            conv.set_offline(True)
         nb = -(-N // block_size)
         chunk = max(1, (1 << 25) // (C * block_size))  # <= 2^25 doubles per upload
+        if offline:
+            chunk = max(128, chunk // 128 * 128)  # whole windows
         out = np.empty_like(sig)
         for t0 in range(0, nb, chunk):
             t1 = min(nb, t0 + chunk)
